@@ -9,7 +9,10 @@ of the per-pose blocked-ray counts (RCCL over xGMI when N > 1), then the argmin.
 value = ray-hit tests/s: sample queries the reference would execute (samples up to and
 including the first hit, else all), summed over all ranks, / max-over-ranks wall time.
 Inputs (terrain index, direction tables, poses) are resident in HBM before timing starts.
-The same line carries the rest of the metric ("+ candidate poses/sec (whole node)"):
+A plain run does that and no more: set-up, W warm-up steps, the K timed steps, the outputs of
+the last step to DIR when --dump-outputs DIR is given (seeded inputs: the same arguments give
+the same files), the result line.  Everything below is measured after it, with --full only.
+With --full the same line carries the rest of the metric ("+ candidate poses/sec (whole node)"):
 poses_per_s_reference_mode (runOptimization over the excavation cells, virtual_lidar.cpp:
 454-548) and c3 (crop + voxel + transform frame, BASELINE configs[2]), each its own timed loop
 of K steps, and CPU baselines (the oracle restatement, 1 thread and the host's CPU share) for
@@ -17,7 +20,11 @@ all three on rank 0 at N = 1.  With N > 1 the line also carries c4 (BASELINE con
 poses strong-scaled over the N ranks, oracle-checked on a sample); at N = 1 it carries c1 and
 c5 (configs[0] / configs[4]: the per-frame chain through the C++ node cores).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode all|fan|filter|cells|c1|c4|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+                    [--mode all|fan|filter|cells|c1|c4|c5]
+
+A --mode other than all is one workload asked for by name and reports all it did before,
+with or without --full.
 
 --gpus N without WORLD_SIZE starts N ranks itself (one process per GPU).  The rank processes
 never import torch (their control plane is hostgroup.py's helper), so libpcp runs on the HIP
@@ -402,6 +409,24 @@ def _timed(step, args, dist, sync):
     return dt, units, res
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _dump_outputs(folder, arrays) -> None:
+    """--dump-outputs: what the last timed step handed its caller, one <name>.npy each, as
+    float64 (the counts are below 2**53, so nothing is rounded).  The inputs are seeded, so two
+    builds run with the same arguments can be compared file by file."""
+    folder = Path(folder)
+    folder.mkdir(parents=True, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        total += a.nbytes
+        if total > DUMP_LIMIT_BYTES:
+            raise SystemExit(f"bench.py --dump-outputs: more than {DUMP_LIMIT_BYTES} bytes")
+        np.save(folder / f"{name}.npy", a)
+
+
 def _profiled(ctx, step, reps, names):
     """Per-launch event times of `names` over `reps` extra steps run AFTER the timed loop: the
     library's event instrumentation (ctx.profile) stays out of the timed region."""
@@ -617,7 +642,8 @@ def _cells_roofline(ctx, cposes, zx5, params, n_cells, kern):
 def _fan_stepper(ctx, poses, fan, lo, P_total, dist, backend):
     """One step of the pose-sharded fan search for this rank's poses [lo, lo + len(poses)) of
     P_total -> (step() -> (ray-hit tests of this rank, blocked counts), best {"fan": argmin},
-    the all-poses blocked vector the step fills).  N > 1 over RCCL: libpcp's own communicator --
+    the all-poses blocked vector the step fills, this rank's per-pose ray-hit tests the step
+    fills).  N > 1 over RCCL: libpcp's own communicator --
     the per-pose keys (blocked << 32) | pose are written into the context's device vector, ONE
     ncclAllReduce(MIN) runs on the library's stream, only the reduced vector comes back
     (pcp_raycast_fan_allreduce).  The gloo rehearsal (ranks sharing one GPU) reduces a host
@@ -646,7 +672,7 @@ def _fan_stepper(ctx, poses, fan, lo, P_total, dist, backend):
                 blocked_all[:P_total] = np.asarray(keys[:P_total], np.uint32)
             best["fan"] = b   # ^ the one collective
             return int(units_h[:poses.shape[0]].sum()), keys
-    return fan_step, best, blocked_all
+    return fan_step, best, blocked_all, units_h
 
 
 C4_POSES = 4096   # BASELINE configs[3]: 4096 candidate poses sharded over the GPUs
@@ -700,7 +726,7 @@ def run_c4(args, dist, world, rank, local, backend, ctx=None, scene=None):
     poses_all, nc = _poses_for(ctx, _grid_bbox(scene.area), scene.zx120_pose5, C4_POSES)
     lo, hi = pd.shard(C4_POSES, world, rank)
     poses = np.ascontiguousarray(poses_all[lo:hi])
-    step, best, blocked_all = _fan_stepper(ctx, poses, fan, lo, C4_POSES, dist, backend)
+    step, best, blocked_all, _ = _fan_stepper(ctx, poses, fan, lo, C4_POSES, dist, backend)
     dt, units_all, _ = _timed(step, args, dist, ctx.synchronize)
     shards = [pd.shard(C4_POSES, world, r) for r in range(world)]
     res = {"workload": "C4 (configs[3]): 4096 candidate poses strong-scaled over the ranks, "
@@ -734,9 +760,9 @@ def run_c4(args, dist, world, rank, local, backend, ctx=None, scene=None):
 
 
 def run_all(args, dist, world, rank, local, backend):
-    """Default line: the C2 fan (value), reference-mode scoring of the same node
-    (runOptimization, poses/s) and the C3 filter frame, each timed as its own loop of K steps
-    with the barrier / max-over-ranks discipline; CPU baselines on rank 0 at N = 1."""
+    """Default line: the C2 fan (value); with args.full also reference-mode scoring of the same
+    node (runOptimization, poses/s) and the C3 filter frame, each timed as its own loop of K
+    steps with the barrier / max-over-ranks discipline; CPU baselines on rank 0 at N = 1."""
     import numpy as np
 
     from pointcloud_processor_amd import _abi, synth
@@ -755,18 +781,19 @@ def run_all(args, dist, world, rank, local, backend):
     fan = _abi.fan_params(n_az=args.n_az, n_el=args.n_el)
 
     # ---- C2: the fan (the headline) --------------------------------------------------------
-    fan_step, best, blocked_all = _fan_stepper(ctx, poses, fan, lo, P_total, dist, backend)
+    fan_step, best, blocked_all, units_step = _fan_stepper(ctx, poses, fan, lo, P_total, dist,
+                                                           backend)
     own_comm = backend == "rccl"
     dt, units_all, _ = _timed(fan_step, args, dist, ctx.synchronize)
+    if args.dump_outputs and rank == 0:   # the last timed step's results, before anything reruns
+        _dump_outputs(args.dump_outputs, {"blocked": blocked_all[:P_total],
+                                          "units": units_step[:poses.shape[0]],
+                                          "best_pose": np.array([best["fan"]])})
     units_h = np.zeros(max(poses.shape[0], 1), np.uint64)
     collective = None
     if own_comm:
-        ms = []
-        for _ in range(max(args.steps, 3)):   # after the timed loop: events around the collective
-            ms.append(ctx.raycast_fan_allreduce(poses, fan, lo, P_total, blocked_all, units_h,
-                                                timed=True)[1])
         collective = {"op": "ncclAllReduce(ncclUint64, ncclMin)", "backend": "rccl (libpcp)",
-                      "bytes": 8 * P_total, "collective_ms": float(np.median(ms)),
+                      "bytes": 8 * P_total,
                       "path": "device keys in libpcp's vector (written by k_fan_reduce), libpcp's "
                               "own RCCL communicator on its stream (pcp_raycast_fan_allreduce), "
                               "the reduced vector and the shard's units landed by one copy "
@@ -778,13 +805,6 @@ def run_all(args, dist, world, rank, local, backend):
     elif dist is not None:
         collective = {"op": "all_reduce(MIN) int64", "backend": backend, "bytes": 8 * P_total,
                       "path": "host vector (gloo rehearsal: ranks share devices)"}
-    k_avg = _profiled(ctx, fan_step, max(args.steps, 3), ["raycast_fan"])["raycast_fan"]
-    # the kernel's launch time: the same launch 20 times back-to-back between two events on the
-    # library's stream (the per-step events of the synchronous loop also hold the idle queue's
-    # wake-up before each launch; kept below as event_avg_ms_in_loop)
-    burst_ms = ctx.raycast_fan_burst(poses, fan, reps=20)
-    avg_kernel_s = burst_ms * 1e-3
-    units_per_launch = units_all / max(world, 1) / max(args.steps, 1)
     out = {
         "metric": METRIC,
         "value": units_all / dt,
@@ -809,14 +829,30 @@ def run_all(args, dist, world, rank, local, backend):
         # each rank's own time for its 256 poses: the N = 1-comparable figure of a SCALE line
         "ms_per_step_per_rank": [t / max(args.steps, 1) * 1e3 for t in _timed.per_rank_s],
         "best_pose": best["fan"],
-        "roofline": _fan_roofline(ctx, poses, fan, avg_kernel_s, units_per_launch),
     }
-    out["roofline"]["kernel_time_source"] = ("HIP events around 20 back-to-back launches "
-                                             "(pcp_raycast_fan_burst)")
-    out["roofline"]["event_avg_ms_in_loop"] = k_avg
     if dist is not None and backend == "gloo":
         out["rehearsal"] = (f"{world} ranks on {_abi.device_count()} GPU(s): collective "
                             "over gloo, ranks share devices")
+    if not args.full:   # a plain run: the headline alone (everything below is --full's)
+        ctx.close()
+        return out
+    if own_comm:
+        ms = []
+        for _ in range(max(args.steps, 3)):   # after the timed loop: events around the collective
+            ms.append(ctx.raycast_fan_allreduce(poses, fan, lo, P_total, blocked_all, units_h,
+                                                timed=True)[1])
+        collective["collective_ms"] = float(np.median(ms))
+    k_avg = _profiled(ctx, fan_step, max(args.steps, 3), ["raycast_fan"])["raycast_fan"]
+    # the kernel's launch time: the same launch 20 times back-to-back between two events on the
+    # library's stream (the per-step events of the synchronous loop also hold the idle queue's
+    # wake-up before each launch; kept below as event_avg_ms_in_loop)
+    burst_ms = ctx.raycast_fan_burst(poses, fan, reps=20)
+    avg_kernel_s = burst_ms * 1e-3
+    units_per_launch = units_all / max(world, 1) / max(args.steps, 1)
+    out["roofline"] = _fan_roofline(ctx, poses, fan, avg_kernel_s, units_per_launch)
+    out["roofline"]["kernel_time_source"] = ("HIP events around 20 back-to-back launches "
+                                             "(pcp_raycast_fan_burst)")
+    out["roofline"]["event_avg_ms_in_loop"] = k_avg
     if dist is not None:   # configs[3]: the 4096-pose search strong-scaled over these ranks
         out["c4"] = run_c4(args, dist, world, rank, local, backend, ctx=ctx, scene=scene)
     host = _host_cpu()
@@ -1355,8 +1391,9 @@ def main():
     ap.add_argument("--mode", choices=["all", "fan", "filter", "cells", "c1", "c4", "c5",
                                        "launch-check"],
                     default="all",
-                    help="all (default): the fan line with reference-mode scoring and C3 as "
-                         "extra keys; fan: the fan alone (profiling); filter: C3 with PCIe and "
+                    help="all (default): the fan line, with --full also reference-mode scoring "
+                         "and C3 as extra keys; fan: the fan alone (profiling); filter: C3 with "
+                         "PCIe and "
                          "stage breakdown; cells: reference mode alone; c4: 4096 poses strong-"
                          "scaled over the ranks (configs[3]); c1 / c5: the streaming chain "
                          "(configs[0] / configs[4], replicas)")
@@ -1368,7 +1405,20 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pcie", action="store_true",
                     help="filter mode: skip the host-buffer (PCIe-inclusive) measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="mode all: after the headline's timed steps also measure everything "
+                         "else the line can carry (the collective's and the kernel's own times, "
+                         "the roofline, c4 or c1 + c5, reference mode, C3, the CPU baselines and "
+                         "oracle checks); without it the run ends with the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="mode all / fan / cells: write what the headline's last timed step "
+                         "returned (per-pose blocked counts, this rank's per-pose ray-hit tests, "
+                         "the best pose) as DIR/<name>.npy, float64")
     args = ap.parse_args()
+    if args.dump_outputs and args.mode not in ("all", "fan", "cells"):
+        ap.error("--dump-outputs writes the fan search's outputs: --mode all, fan or cells")
+    if args.mode != "all":   # a mode asked for by name reports all it did before
+        args.full = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(_self_launch(args.gpus))
     args.fan_only = args.mode == "fan"

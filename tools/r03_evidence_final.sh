@@ -6,6 +6,8 @@ set -u
 cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 bash tools/r03_final.sh A || exit $?
-timeout -k 10 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_default -o run --output-format csv -- python3 bench.py > gpurun_out/rocprof_default.log 2>&1 || { echo "rocprof rc=$?"; exit 1; }
+OUT=${OUT:-prof_out}
+mkdir -p "$OUT"
+timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof_default" -o run --output-format csv -- python3 bench.py --full > "$OUT/rocprof_default.log" 2>&1 || { echo "rocprof rc=$?"; exit 1; }
 bash tools/pmc_filter_traffic.sh r03c || exit 1
 echo "=== evidence done"

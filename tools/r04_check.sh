@@ -22,12 +22,12 @@ test)
   step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
   ;;
 bench)
-  step bench 600 python bench.py
+  step bench 600 python bench.py --full
   ;;
 all)
   step pytest_gpu 900 python -u -m pytest tests -v -m gpu -rf --timeout 300 --timeout-method thread ${K:+-k "$K"}
   step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-  step bench 600 python bench.py
+  step bench 600 python bench.py --full
   ;;
 esac
 echo "=== done"

@@ -7,6 +7,7 @@
 # Each GPU step has its own limit; a crash or timeout ends the script.
 set -u
 cd "$(dirname "$0")/.."
+OUT=${OUT:-prof_out}   # the traced bench.py --full run writes its kernel stats here
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 step() {  # name, seconds, command...
@@ -23,12 +24,12 @@ case "${1:-A}" in
 A)
   step pytest_gpu 900 python -u -m pytest tests -v -m gpu -rf -s --timeout 300 --timeout-method thread
   step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-  step bench 600 python bench.py
+  step bench 600 python bench.py --full
   FRAMES=200 step replay 600 bash tools/replay.sh
   step top2 600 python tools/c5_top2.py 8 gpurun_out/r04_c5_top2_gaps.json
   ;;
 B)
-  step rocprof_default 900 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_default -o run --output-format csv -- python3 bench.py
+  step rocprof_default 900 rocprofv3 --kernel-trace --stats -d "$OUT/prof_default" -o run --output-format csv -- python3 bench.py --full
   step pmc_fan 300 bash tools/pmc_fan_traffic.sh r04
   step pmc_flt 300 bash tools/pmc_filter_traffic.sh r04
   step gather_cal 300 bash tools/gather_cal.sh

@@ -11,6 +11,7 @@
 #   A: every GPU test + smoke, the default bench line
 set -u
 cd "$(dirname "$0")/.."
+OUT=${OUT:-prof_out}   # the traced bench.py --full run writes its kernel stats here
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 step() {  # name, seconds, command...
@@ -42,12 +43,12 @@ C)
   step c5_trace 300 env FRAMES=30 bash tools/replay_trace.sh
   ;;
 S)
-  step rocprof_default 900 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_default -o run --output-format csv -- python3 bench.py
+  step rocprof_default 900 rocprofv3 --kernel-trace --stats -d "$OUT/prof_default" -o run --output-format csv -- python3 bench.py --full
   ;;
 A)
   step pytest_gpu 900 python -u -m pytest tests -v -m gpu -rf -s --timeout 300 --timeout-method thread
   step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-  step bench 600 python bench.py
+  step bench 600 python bench.py --full
   ;;
 esac
 done

@@ -18,6 +18,7 @@
 #   python3 tools/pmc_traffic.py cells "k_score_cells<" gpurun_out/pmccr06_fetch gpurun_out/pmccr06_write per_dispatch r06_pmc_traffic.json
 set -u
 cd "$(dirname "$0")/.."
+OUT=${OUT:-prof_out}   # the traced bench.py --full run writes its kernel stats here
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 step() {  # name, seconds, command...
@@ -45,18 +46,18 @@ C)
   step c5_trace 300 env FRAMES=30 bash tools/replay_trace.sh
   ;;
 S)
-  step rocprof_default 900 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_default -o run --output-format csv -- python3 bench.py
+  step rocprof_default 900 rocprofv3 --kernel-trace --stats -d "$OUT/prof_default" -o run --output-format csv -- python3 bench.py --full
   ;;
 A)
   step pytest_gpu 900 python -u -m pytest tests -v -m gpu -rf -s --timeout 300 --timeout-method thread
   step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-  step bench 600 python bench.py
+  step bench 600 python bench.py --full
   ;;
 N)
   step bench_n2 600 python bench.py --gpus 2 --mode cells --steps 5 --warmup 2 --no-cpu-baseline
   ;;
 R)
-  step bench_rccl_n1 600 env WORLD_SIZE=1 RANK=0 LOCAL_RANK=0 PCP_DIST_FORCE=1 python bench.py --gpus 1
+  step bench_rccl_n1 600 env WORLD_SIZE=1 RANK=0 LOCAL_RANK=0 PCP_DIST_FORCE=1 python bench.py --gpus 1 --full
   ;;
 esac
 done
