@@ -509,6 +509,16 @@ int pcp_multi_score_poses(pcp_multi *m, const double *poses5, uint64_t n,
                           uint8_t *cell_flags, double *total_score, int32_t *covered,
                           pcp_vl_report *rep);
 
+/* The longest step table a query may march: max_distance up to about 1,229 m.  pcp_raycast_fan*,
+ * pcp_score_poses*, pcp_score_matrix and pcp_generate_and_score return PCP_E_INVALID, before
+ * anything is launched, when max_distance - 0.08 gives more samples.  first_hit (int16) would
+ * hold 32,767; the bound is lower because the march probes sample k's cell as one float fma
+ * A + D k per axis: D's rounding grows with k to ~2e-4 m at k = 4,096 and the probed coordinate's
+ * own to ~1e-4 m, together still inside the 1 mm margin of the index's windows that makes a
+ * skipped sample a certain miss ("Float probes"); at 32,767 samples they
+ * would pass it.  pcp_step_table itself is not bounded by it. */
+#define PCP_MAX_STEPS 4096
+
 /* The march's sample distances: s_0 = 0.5, s_{k+1} = s_k + 0.3 (repeated double addition,
  * :765-796) while s_k < end.  Returns the count in *n (writes min(cap, n) values). */
 int pcp_step_table(double end, double *steps, uint64_t cap, uint64_t *n);

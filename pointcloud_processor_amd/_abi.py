@@ -22,6 +22,8 @@ PCP_E_CAPACITY = -3
 PCP_E_STATE = -4
 PCP_E_NOMEM = -5
 
+MAX_STEPS = 4096   # PCP_MAX_STEPS of include/pcp_abi.h: the longest step table a query marches
+
 PCP_MEM_DEVICE_IN = 1
 PCP_MEM_DEVICE_OUT = 2
 

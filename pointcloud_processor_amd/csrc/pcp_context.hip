@@ -661,7 +661,19 @@ int pcp_create(int device, pcp_ctx **out) {
     if (const char *ne = std::getenv("PCP_NORMALS_EXACT")) ctx->normals_exact = std::atoi(ne) != 0;
     if (const char *sw = std::getenv("PCP_SCORE_WIDE")) ctx->score_wide = std::atoi(sw) != 0;
     if (const char *wr = std::getenv("PCP_SCORE_WIDE_RAYS")) ctx->score_wide_rays = std::atoll(wr);
-    if (const char *wg = std::getenv("PCP_SCORE_WIDE_G")) ctx->score_wide_g = std::atoi(wg);
+    if (const char *wg = std::getenv("PCP_SCORE_WIDE_G")) {
+        // the instantiated widths only: no context exists to carry the message, so it goes to
+        // stderr and the creation fails (no silent fall-back to the default)
+        char *end = nullptr;
+        const long v = std::strtol(wg, &end, 10);
+        if (end == wg || *end != '\0' || !(v == 2 || v == 4 || v == 8 || v == 16)) {
+            std::fprintf(stderr, "libpcp: pcp_create: PCP_SCORE_WIDE_G=\"%s\" is not one of 2, 4, 8, 16\n",
+                         wg);
+            delete ctx;
+            return PCP_E_INVALID;
+        }
+        ctx->score_wide_g = (int)v;
+    }
     if (const char *co = std::getenv("PCP_CELLS_ORDER_FREE")) ctx->cells_all_ordered = std::atoi(co) == 0;
     if (const char *nbk = std::getenv("PCP_NB_BLOCKS")) ctx->nb_blocks = std::atoi(nbk);
     if (const char *sp = std::getenv("PCP_SCAN_ONEPASS")) ctx->scan_onepass = std::atoi(sp) != 0;

@@ -1704,11 +1704,27 @@ int pcp_generate_candidates(pcp_ctx *ctx, const double bb[6], const pcp_vl_param
     return PCP_OK;
 }
 
+// PCP_MAX_STEPS (include/pcp_abi.h): a longer table is refused before anything is launched,
+// whether or not first hits are asked for.  A table certainly past the bound is not even built
+// (s_k = 0.5 + 0.3 k to ~1e-9 at these k); the sample in doubt is settled by counting.  The
+// cached table has passed already.
+static int steps_within_bound(pcp_ctx *ctx, double end) {
+    if (ctx->steps_end == end) return PCP_OK;
+    if (end > 0.5 + kRayStep * (double)(PCP_MAX_STEPS + 1) ||
+        step_table(end).size() > (size_t)PCP_MAX_STEPS)
+        return set_err(ctx, PCP_E_INVALID,
+                       "max_distance %.17g: the march's step table would pass PCP_MAX_STEPS = %d "
+                       "samples", end + kVisRadius, PCP_MAX_STEPS);
+    return PCP_OK;
+}
+
+// (a refused table leaves the cached one as it was)
 static int ensure_steps(pcp_ctx *ctx, double end, int *K) {
     if (ctx->steps_end == end) {
         *K = ctx->steps_K;
         return PCP_OK;
     }
+    if (int rc = steps_within_bound(ctx, end)) return rc;
     std::vector<double> s = step_table(end);
     PCP_HIP(ctx, ctx->steps_d.ensure((s.size() + 1) * sizeof(double)));
     if (!s.empty()) {
@@ -1735,7 +1751,11 @@ static void launch_score_cells(hipStream_t st, pcp_ctx *ctx, const VisEnv &E, in
     const uint64_t wide_rays = ctx->score_wide_rays >= 0 ? (uint64_t)ctx->score_wide_rays
                                                          : (uint64_t)kWideMaxRays;
     const bool wide = (uint64_t)(P + 1) * (uint64_t)C <= wide_rays && ctx->score_wide;
-    const int G = ctx->score_wide_g ? ctx->score_wide_g : kWideG;
+    // the lanes per ray of the kernel that IS launched size its grid: PCP_SCORE_WIDE_G (2 / 4 /
+    // 8 / 16, validated by pcp_create) with the step table in LDS, the default width past it
+    // (the only instantiation there)
+    const int Gq = ctx->score_wide_g;
+    const int G = (E.K <= kStepLds && (Gq == 2 || Gq == 4 || Gq == 8)) ? Gq : kWideG;
     const dim3 gw((unsigned)(((uint64_t)C * G + kT - 1) / kT), (unsigned)(P + 1));
     const double *cx = ctx->cells_xyz.as<const double>();
     const float *cn = ctx->cells_nrm.as<const float>();
@@ -2044,6 +2064,8 @@ int pcp_generate_and_score(pcp_ctx *ctx, const double bb[6], const pcp_vl_params
     if (!bb || !p || !zx || !n_out || !rep || (cap && !poses5) ||
         ((pend ? ctx->cells_cap : ctx->n_cells) && !cell_flags))
         return set_err(ctx, PCP_E_INVALID, "pcp_generate_and_score: null argument");
+    // (before the candidates are launched: the scoring behind them would refuse the table)
+    if (int rc = steps_within_bound(ctx, p->max_distance - kVisRadius)) return rc;
     PCP_HIP(ctx, hipSetDevice(ctx->device));
     *n_out = 0;
     const int gs = (int)std::ceil(std::sqrt((double)p->num_candidates));

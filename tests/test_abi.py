@@ -45,6 +45,16 @@ def test_binding_covers_the_header():
     assert sorted(_abi.ABI_SYMBOLS) == declared_symbols()
 
 
+def test_binding_mirrors_the_step_table_bound():
+    """PCP_MAX_STEPS of the header == the binding's MAX_STEPS, at most what an int16 first hit
+    indexes; pcp_step_table itself (host only) is not bounded by it."""
+    m = re.search(r"^#define\s+PCP_MAX_STEPS\s+(\d+)\s*$", HEADER.read_text(), flags=re.M)
+    assert m and int(m.group(1)) == _abi.MAX_STEPS
+    assert 365 < _abi.MAX_STEPS <= 32767
+    end = 0.5 + 0.3 * _abi.MAX_STEPS + 0.15     # s_MAX < end <= s_{MAX + 1}
+    assert _abi.step_table(end).size == _abi.MAX_STEPS + 1
+
+
 def test_host_only_entry_points():
     lib = _abi.load_library()
     assert lib.pcp_abi_version() == 2

@@ -2,9 +2,12 @@
 
 Bar (BASELINE.json north_star): crop indices, voxel keys/counts, ray first-hit indices, cell
 flags/covered counts and best-pose indices bit-exact; voxel centroids <= 1e-5 m; transformed
-xyz exact (same float evaluation order); per-pose score totals (double, through ocml acos/sin vs
-glibc) within 4 ulps each and at most max(2, 25 %) of them not bit-identical; candidate pitch/yaw
-(correctly rounded atan2) at most 2 values one ulp off (tests/parity.py).
+xyz exact (same float evaluation order); per-pose score totals (double, correctly rounded acos /
+sin against glibc's) bit-identical on the 91-candidate tick, the C5 frames and the long-range
+scene (parity.assert_totals_exact), elsewhere within 2 ulps each and at most max(2, 5 %) of them
+not bit-identical (parity.assert_totals); per-cell scores at most max(5, 0.4 %) of the positive
+ones off, by at most 8 ulps (parity.cell_bar); candidate pitch/yaw (correctly rounded atan2) at
+most 2 values one ulp off (tests/parity.py).
 All calls go through the C ABI (pointcloud_processor_amd/_abi.py -> libpcp.so).
 """
 import ctypes
@@ -912,9 +915,9 @@ def test_terrain_replaced_after_block_copy(oracle, small_scene, scene):
 
 
 def _rel_close(a, b):
-    """The totals' parity bar (tests/parity.py): every value within 2 ulps of the oracle's and
-    at most max(5, 10 %) of them not bit-identical -- the census's 3-5 %, <= 2 ulps (was a
-    1e-12 relative tolerance, ~2,600x looser than the kernels' results)."""
+    """The totals' loose parity bar (tests/parity.py: totals_match): every value within 2 ulps of
+    the oracle's and at most max(2, 5 %) of them not bit-identical.  The censused cases (the
+    91-candidate tick, the C5 frames, the long-range scene) use the exact bar instead."""
     return parity.totals_match(a, b)
 
 
@@ -951,10 +954,12 @@ def test_parity_bar_catches_one_ulp(oracle, loaded, scene, cells, aux):
                                              np.zeros(cells.xyz.shape[0], np.uint8))
     prod = parity.totals_report(res["prod"][1], r_tot)
     print("parity bar: production", prod)
-    assert parity.totals_match(res["prod"][1], r_tot), prod
+    parity.assert_totals_exact(res["prod"][1], r_tot)   # 0 of 91 differ
     for tag in ("perturbed", "perturbed8"):   # every cell / every 8th cell one ulp up
         bad = parity.totals_report(res[tag][1], r_tot)
         print("parity bar:", tag, bad)
+        assert not parity.totals_exact(res[tag][1], r_tot), (tag, bad)
+        # (this tick's drifts are large enough for the loose bar as well: 61 and 10 of 91)
         assert not parity.totals_match(res[tag][1], r_tot), (tag, bad)
         np.testing.assert_array_equal(res[tag][2], r_cov)
         assert res[tag][3] == r_rep.best_idx == res["prod"][3]
@@ -972,11 +977,12 @@ def test_score_poses_matches_reference_loop(gpu, oracle, loaded, scene, cells):
                                              scene.zx120_pose5, oracle.vl_params(), flags_r)
     np.testing.assert_array_equal(flags_g, flags_r)
     np.testing.assert_array_equal(cov, r_cov)
-    assert _rel_close(tot, r_tot), np.max(np.abs(tot - r_tot))
+    print("91-candidate tick totals", parity.totals_report(tot, r_tot))
+    parity.assert_totals_exact(tot, r_tot)
     gd, rd = rep.as_dict(), r_rep.as_dict()
     for k in gd:
         if k in ("best_score", "zx120_total_score"):
-            assert _rel_close(gd[k], rd[k]), k
+            parity.assert_totals_exact(gd[k], rd[k])
         else:
             assert gd[k] == rd[k], k
     srt = np.sort(r_tot)[::-1]
@@ -1972,16 +1978,24 @@ def test_parity_bar_per_cell(oracle, loaded, scene, cells, aux):
             ctx.set_aux_cloud(aux, point_step=32)
             ctx.set_cells(cells.xyz, cells.normals)
             poses = ctx.generate_candidates(cells.grid_bbox, params, scene.zx120_pose5)
-            res[tag] = (poses, ctx.score_matrix(poses, zx, params))
+            sm_sz = ctx.score_matrix(poses, zx, params)
+            tot, _, _ = ctx.score_poses(poses, zx, params, np.zeros(cells.xyz.shape[0], np.uint8))
+            res[tag] = (poses, sm_sz, tot)
     poses = res["prod"][0]
     r_sm, r_sz = oracle.score_matrix(T, A, cells.xyz, cells.normals, poses, scene.zx120_pose5,
                                      oracle.vl_params())
+    r_tot, _ = oracle.score_totals(T, A, cells.xyz, cells.normals, poses, scene.zx120_pose5,
+                                   oracle.vl_params())
     for tag in res:
         np.testing.assert_array_equal(res[tag][0], poses)
         cen = _cell_census(*res[tag][1], r_sm, r_sz)
-        print("cell census", tag, cen, parity.cell_bar(cen))
+        print("cell census", tag, cen, parity.cell_bar(cen), "totals",
+              parity.totals_report(res[tag][2], r_tot))
         assert cen["zero_mismatch"] == 0
         assert parity.cell_bar(cen) == (tag == "prod"), (tag, cen)
+        # the same tick's totals under the exact bar: the cells that differ (glibc's near ties)
+        # do not reach a total's bits, either drift does
+        assert parity.totals_exact(res[tag][2], r_tot) == (tag == "prod"), tag
 
 
 def test_score_stats_and_burst(loaded, scene, cells, aux):
@@ -2049,6 +2063,454 @@ def test_fan_keys_wait_stream_then_fan(gpu, loaded, scene, oracle):
             ctx.dev_free(keys)
         finally:
             ctx.stream_destroy(st)
+
+
+# ------------------------------------------------- long range: step tables up to and past LDS
+# max_distance -> the step table's length K: 77.3 is the last table the kernels read from LDS
+# (kStepLds = 256), 77.6 the first they read from global memory (the <false> instantiations of
+# k_score_cells / _wide / _stats and the fan's fall-back from the XCD-chunked kernels), 110.0 a
+# LiDAR's real range.
+LONG_K = {77.3: 256, 77.6: 257, 110.0: 365}
+LONG_MD = tuple(LONG_K)
+LONG_EL_DEG = 6.0
+# (PCP_TERRAIN_BLOCKS, PCP_TERRAIN_FINE, PCP_FINE_TILE, layout) of LAYOUTS below: the fine
+# windows with FN 4 / 1 / 8 records, 2 x 2 x 2 blocks, per-cell runs
+LONG_LAYOUTS = [("2", "2", "1", "fine"), ("2", "2", "0", "fine"), ("2", "2", "2", "fine"),
+                ("2", "3", "2", "fine"), ("2", "0", "1", "blocks"), ("0", "3", "1", "cells")]
+
+
+def _long_range_scene(seed=5):
+    """A 112 m corridor, 150 k points of 16 bytes: a thin ground slab over x in [-2, 110],
+    y in [-8, 8]; 0.3 m wall slabs at x = 60 (y < -3), x = 85 (0 < y < 3) and x = 104 (full
+    width); one slab over x in [76.9, 77.5] (-3 < y < 0), which the samples k = 255 (77.0 m) and
+    k = 256 (77.3 m) of the near poses' rays fall into.  Eight fan poses: seven near x = 0 at
+    various y, z, pitch and yaw, one at the far end facing back.  600 scoring cells float over
+    x in [70, 103] (behind the walls or in the gaps between them); the scoring poses are three
+    of the near ones, the far one and one among the cells (in range at max_distance 15 too)."""
+    from types import SimpleNamespace
+
+    rng = np.random.default_rng(seed)
+
+    def slab(n, x0, x1, y0, y1, z0, z1):
+        return rng.uniform([x0, y0, z0], [x1, y1, z1], (n, 3))
+
+    parts = [slab(84_000, -2.0, 110.0, -8.0, 8.0, -0.02, 0.02),
+             slab(12_000, 59.85, 60.15, -8.0, -3.0, 0.0, 3.2),
+             slab(9_000, 76.9, 77.5, -3.0, 0.0, 0.0, 3.2),
+             slab(8_000, 84.85, 85.15, 0.0, 3.0, 0.0, 3.2),
+             slab(37_000, 103.85, 104.15, -8.0, 8.0, 0.0, 4.0)]
+    cloud = np.zeros((sum(p.shape[0] for p in parts), 4), np.float32)
+    cloud[:, :3] = np.concatenate(parts)
+    cloud = np.ascontiguousarray(cloud[rng.permutation(cloud.shape[0])])
+    near = np.array([[0.0, 0.0, 1.5, 0.0, 0.0], [-0.4, -1.7, 2.0, -0.01, 0.02],
+                     [0.3, 1.1, 1.2, 0.01, -0.03], [0.13, -5.5, 2.4, 0.0, 0.05],
+                     [-1.0, 4.5, 1.8, 0.005, -0.04], [0.45, -0.9, 1.0, 0.015, 0.0],
+                     [-0.2, 6.0, 2.2, -0.005, -0.06]])
+    far = np.array([[108.0, 0.5, 1.6, 0.0, np.pi]])
+    mid = np.array([[86.0, 5.0, 1.6, 0.0, np.pi]])
+    xyz = rng.uniform([70.0, -8.0, 0.5], [103.0, 8.0, 3.0], (600, 3))
+    nrm = rng.normal(size=(600, 3)).astype(np.float32)
+    nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
+    many = np.column_stack([rng.uniform(-1.0, 1.0, 60), rng.uniform(-7.0, 7.0, 60),
+                            rng.uniform(1.0, 2.5, 60), rng.uniform(-0.02, 0.02, 60),
+                            rng.uniform(-0.06, 0.06, 60)])
+    return SimpleNamespace(cloud=cloud, fan_poses=np.concatenate([near, far]),
+                           score_poses=np.concatenate([near[:3], far, mid]), n_near=3,
+                           many_poses=many, xyz=xyz, nrm=nrm,
+                           zx=np.array([1.0, 2.0, 1.4, 0.0, 0.0]),
+                           # (its centre below the sensor height: the candidates look slightly
+                           # up from straight down, so the cells 30-100 m away are in their FOV)
+                           cand_bbox=np.array([-4.0, 40.0, -8.0, 8.0, -3.0, 1.0]))
+
+
+@pytest.fixture(scope="module")
+def long_range(oracle):
+    """The long-range scene, its oracle tree and a cache of the oracle's results: every
+    reference is computed once, shared by the tests below and never written to."""
+    lr = _long_range_scene()
+    lr.T = oracle.Cloud(lr.cloud)
+    lr.ref = {}
+    return lr
+
+
+def _long_fan_ref(oracle, lr, md, n_az, n_el):
+    """(blocked, units, first hits) of the oracle for the scene's eight fan poses."""
+    key = ("fan", md, n_az, n_el)
+    if key not in lr.ref:
+        el = math.radians(LONG_EL_DEG)
+        r = oracle.raycast_fan(lr.T, lr.fan_poses, n_az, n_el, -el, el, md)
+        for a in r:
+            a.setflags(write=False)
+        lr.ref[key] = r
+    return lr.ref[key]
+
+
+def _long_score_ref(oracle, lr, md, poses_name="score_poses"):
+    """The oracle's scoring of the scene at max_distance md: two ticks whose flags carry over
+    (the second with the poses reversed), the per-cell matrix with and without the terrain."""
+    key = ("score", md, poses_name)
+    if key not in lr.ref:
+        poses = getattr(lr, poses_name)
+        p = oracle.vl_params(max_distance=md)
+        fl = np.zeros(lr.xyz.shape[0], np.uint8)
+        ticks = []
+        oracle.set_threads(8)
+        try:
+            for ps in (poses, poses[::-1].copy()):
+                tot, cov, rep = oracle.score_poses(lr.T, None, lr.xyz, lr.nrm, ps, lr.zx, p, fl)
+                ticks.append((tot, cov, rep.as_dict(), fl.copy()))
+            sm, sz = oracle.score_matrix(lr.T, None, lr.xyz, lr.nrm, poses, lr.zx, p)
+            sm0, _ = oracle.score_matrix(None, None, lr.xyz, lr.nrm, poses, lr.zx, p)
+        finally:
+            oracle.set_threads(1)
+        for a in (sm, sz, sm0) + tuple(x for t in ticks for x in (t[0], t[1], t[3])):
+            a.setflags(write=False)
+        lr.ref[key] = {"ticks": ticks, "sm": sm, "sz": sz, "sm0": sm0}
+    return lr.ref[key]
+
+
+def _long_fan_params(n_az, n_el, md):
+    return _abi.fan_params(n_az=n_az, n_el=n_el, el_min_deg=-LONG_EL_DEG, el_max_deg=LONG_EL_DEG,
+                           max_distance=md)
+
+
+def _set_layout_env(monkeypatch, mode, fine, tile):
+    monkeypatch.setenv("PCP_TERRAIN_BLOCKS", mode)
+    monkeypatch.setenv("PCP_TERRAIN_FINE", fine)
+    monkeypatch.setenv("PCP_FINE_TILE", tile)
+    monkeypatch.setenv("PCP_FINE_PACK", "1")
+
+
+def _assert_report_equal(got: dict, ref: dict, exact_totals=True):
+    for k in got:
+        if k in ("best_score", "zx120_total_score"):
+            parity.assert_totals(got[k], ref[k])
+            if exact_totals:
+                parity.assert_totals_exact(got[k], ref[k])
+        else:
+            assert got[k] == ref[k], k
+
+
+@pytest.mark.parametrize("n_az,n_el", [(1024, 8), (100, 37)])
+@pytest.mark.parametrize("md", LONG_MD)
+def test_long_range_fan(oracle, long_range, md, n_az, n_el, monkeypatch):
+    """The ray fan at max_distance 77.3 / 77.6 / 110 (K = 256: the last step table in LDS, 257:
+    the first in global memory, 365) on the long-range scene: first hits, blocked counts and
+    units equal the oracle's exactly, for 8 poses (P % 8 == 0: the XCD-chunked kernels at
+    K = 256, their K > kStepLds fall-back to the plain launch from K = 257) and for 3 poses, on
+    the fine-window (FN 4 / 1 / 8), block and per-cell layouts; 1024 x 8 is the uniform-ring
+    fan, 100 x 37 has rings spanning waves and a ragged last wave.  The oracle's output first
+    shows that the path is exercised (hits at k >= 256, at exactly k = 255 / 256, misses).  At
+    K = 365 the stats twin and the burst launch run once as well: deterministic counts, a
+    positive time, the next query's results unchanged bit for bit."""
+    lr = long_range
+    K = LONG_K[md]
+    assert _abi.step_table(md - 0.08).size == K
+    assert (K <= 256) == (md == 77.3)
+    fan = _long_fan_params(n_az, n_el, md)
+    r_blocked, r_units, r_fh = _long_fan_ref(oracle, lr, md, n_az, n_el)
+    # reference-only preconditions
+    assert (r_fh == -1).any() and ((r_fh >= 0) & (r_fh < 256)).any()
+    if md == 110.0:
+        assert int((r_fh >= 256).sum()) >= 50 and r_fh.max() > 300
+    elif md == 77.6:
+        assert (r_fh == 256).any() and r_fh.max() == 256
+    else:
+        assert r_fh.max() == 255
+    three = [0, 3, 7]
+    for mode, fine, tile, layout in LONG_LAYOUTS:
+        _set_layout_env(monkeypatch, mode, fine, tile)
+        with _abi.Context(0) as ctx:
+            ctx.set_terrain(lr.cloud, point_step=16)
+            blocked, units, fh, best = ctx.raycast_fan(lr.fan_poses, fan, want_first_hit=True)
+            b3, u3, fh3, best3 = ctx.raycast_fan(lr.fan_poses[three], fan, want_first_hit=True)
+            assert ctx.terrain_info()["scan_layout"] == layout
+        tag = (mode, fine, tile)
+        bad = int(np.count_nonzero(fh != r_fh))
+        assert bad == 0, (tag, f"{bad} of {fh.size} first hits differ")
+        np.testing.assert_array_equal(blocked, r_blocked, err_msg=str(tag))
+        np.testing.assert_array_equal(units, r_units, err_msg=str(tag))
+        assert best == int(np.argmin(r_blocked)), tag
+        np.testing.assert_array_equal(fh3, r_fh[three], err_msg=str(tag))
+        np.testing.assert_array_equal(b3, r_blocked[three], err_msg=str(tag))
+        np.testing.assert_array_equal(u3, r_units[three], err_msg=str(tag))
+        assert best3 == int(np.argmin(r_blocked[three])), tag
+    if md != 110.0:
+        return
+    for name in ("PCP_TERRAIN_BLOCKS", "PCP_TERRAIN_FINE", "PCP_FINE_TILE", "PCP_FINE_PACK"):
+        monkeypatch.delenv(name)
+    with _abi.Context(0) as ctx:   # the defaults
+        ctx.set_terrain(lr.cloud, point_step=16)
+        b0, u0, fh0, _ = ctx.raycast_fan(lr.fan_poses, fan, want_first_hit=True)
+        np.testing.assert_array_equal(fh0, r_fh)
+        st = ctx.raycast_fan_stats(lr.fan_poses, fan)
+        assert st == ctx.raycast_fan_stats(lr.fan_poses, fan)
+        assert st["samples_visited"] >= st["scanned_stencils"] > 0 and st["point_tests"] > 0
+        assert ctx.raycast_fan_burst(lr.fan_poses, fan, reps=3) > 0.0
+        b1, u1, fh1, _ = ctx.raycast_fan(lr.fan_poses, fan, want_first_hit=True)
+        np.testing.assert_array_equal(fh1, fh0)
+        np.testing.assert_array_equal(b1, b0)
+        np.testing.assert_array_equal(u1, u0)
+        np.testing.assert_array_equal(b1, r_blocked)
+        np.testing.assert_array_equal(u1, r_units)
+
+
+def _long_score_preconditions(lr, ref, md):
+    """Reference-only: at 110 m every near pose sees, past 77.5 m (k >= 256), at least 100
+    cells and has at least 100 more hidden by the terrain alone."""
+    if md != 110.0:
+        return
+    poses = lr.score_poses[:lr.n_near]
+    d = np.linalg.norm(lr.xyz[None, :, :] - poses[:, None, :3], axis=2)
+    far = d > 77.5
+    vis = ((ref["sm"][:lr.n_near] > 0) & far).sum(1)
+    blk = ((ref["sm0"][:lr.n_near] > 0) & (ref["sm"][:lr.n_near] == 0) & far).sum(1)
+    assert vis.min() >= 100 and blk.min() >= 100, (vis, blk)
+
+
+def _long_score_check(ctx, lr, ref, md, poses, exact_totals=True, tag=""):
+    """Two ticks whose flags carry over and the per-cell matrix against the cached oracle
+    results: flags, covered counts, best index and report counters exact, totals under the
+    bars of tests/parity.py, cells under cell_bar with no zero / positive mismatch."""
+    params = _abi.default_vl_params(max_distance=md)
+    fg = np.zeros(lr.xyz.shape[0], np.uint8)
+    for t, ps in enumerate((poses, poses[::-1].copy())):
+        r_tot, r_cov, r_rep, r_fl = ref["ticks"][t]
+        tot, cov, rep = ctx.score_poses(ps, lr.zx, params, fg)
+        print("long range", tag, "md", md, "tick", t, "totals", parity.totals_report(tot, r_tot))
+        np.testing.assert_array_equal(fg, r_fl)
+        np.testing.assert_array_equal(cov, r_cov)
+        parity.assert_totals(tot, r_tot)
+        if exact_totals:
+            parity.assert_totals_exact(tot, r_tot)
+        _assert_report_equal(rep.as_dict(), r_rep, exact_totals)
+    srt = np.sort(ref["ticks"][0][0])[::-1]
+    assert (srt[0] - srt[1]) > 1e-9 * srt[0]     # the argmax is decidable
+    sm, sz = ctx.score_matrix(poses, lr.zx, params)
+    cen = _cell_census(sm, sz, ref["sm"], ref["sz"])
+    print("long range", tag, "md", md, "cell census", cen)
+    assert cen["zero_mismatch"] == 0, cen
+    assert parity.cell_bar(cen), cen
+    return cen
+
+
+@pytest.mark.parametrize("wide", ["1", "0"])
+@pytest.mark.parametrize("md", LONG_MD)
+def test_long_range_score(oracle, long_range, md, wide, monkeypatch):
+    """Reference-mode scoring at K = 256 / 257 / 365 on the long-range scene, 600 cells x 6
+    rows: k_score_cells_wide<SL, 16> (the default for so few rays) and, with PCP_SCORE_WIDE=0,
+    k_score_cells<SL> -- SL false from K = 257.  Flags, covered counts, best index and report
+    counters exact over two ticks; no cell positive on one side only; cells under cell_bar;
+    totals bit-identical to the oracle's: the first run on an MI355X showed 0 differing totals
+    in every case (both ticks, and the 12 candidates' of pcp_generate_and_score), so all are
+    held to the exact bar.  Cells differing there, one ulp each, the same with either kernel:
+    1 of 1,018 positive ones at K = 256, 2 of 1,031 at K = 257, 7 of 1,996 at K = 365.
+    At K = 365 the stats twin (k_score_cells_stats<false>) runs too, and
+    pcp_generate_and_score is compared with the two calls and with the oracle's candidates."""
+    lr = long_range
+    assert _abi.step_table(md - 0.08).size == LONG_K[md]
+    ref = _long_score_ref(oracle, lr, md)
+    _long_score_preconditions(lr, ref, md)
+    monkeypatch.setenv("PCP_SCORE_WIDE", wide)
+    poses = lr.score_poses
+    assert (poses.shape[0] + 1) * lr.xyz.shape[0] <= 1 << 15   # the wide kernel's range
+    params = _abi.default_vl_params(max_distance=md)
+    with _abi.Context(0) as ctx:
+        ctx.set_terrain(lr.cloud, point_step=16)
+        ctx.set_cells(lr.xyz, lr.nrm)
+        _long_score_check(ctx, lr, ref, md, poses, tag=f"wide={wide}")
+        if md != 110.0:
+            return
+        C = lr.xyz.shape[0]
+        t0, c0, r0 = ctx.score_poses(poses, lr.zx, params, np.zeros(C, np.uint8))
+        st = ctx.score_poses_stats(poses, lr.zx, params)
+        assert st == ctx.score_poses_stats(poses, lr.zx, params)
+        assert st["probes"] >= st["walk_starts"] > 0 and st["point_tests"] > 0
+        assert st["directory_loads"] == 0
+        st2 = ctx.score_poses_stats(np.concatenate([poses, poses]), lr.zx, params)
+        assert st2["probes"] > st["probes"]
+        assert ctx.score_poses_burst(poses, lr.zx, params, reps=3) > 0.0
+        t1, c1, r1 = ctx.score_poses(poses, lr.zx, params, np.zeros(C, np.uint8))
+        np.testing.assert_array_equal(t1.view(np.uint64), t0.view(np.uint64))
+        np.testing.assert_array_equal(c1, c0)
+        assert r1.as_dict() == r0.as_dict()
+        # one round trip against the two calls, and both against the oracle
+        gp = _abi.default_vl_params(max_distance=md, num_candidates=16)
+        op = oracle.vl_params(max_distance=md, num_candidates=16)
+        fa, fb, fr = (np.zeros(C, np.uint8) for _ in range(3))
+        cand = ctx.generate_candidates(lr.cand_bbox, gp, lr.zx)
+        tot, cov, rep = ctx.score_poses(cand, lr.zx, gp, fa)
+        p2, tot2, cov2, rep2 = ctx.generate_and_score(lr.cand_bbox, gp, lr.zx, fb)
+        np.testing.assert_array_equal(p2, cand)
+        np.testing.assert_array_equal(tot2.view(np.uint64), tot.view(np.uint64))
+        np.testing.assert_array_equal(cov2, cov)
+        np.testing.assert_array_equal(fb, fa)
+        assert rep2.as_dict() == rep.as_dict()
+        r_cand = oracle.generate_candidates(lr.T, lr.cand_bbox, op, lr.zx)
+        assert cand.shape == r_cand.shape and cand.shape[0] >= 8
+        np.testing.assert_array_equal(cand[:, :3], r_cand[:, :3])
+        parity.assert_angles(cand[:, 3:], r_cand[:, 3:])
+        r_tot, r_cov, r_rep = oracle.score_poses(lr.T, None, lr.xyz, lr.nrm, cand, lr.zx, op, fr)
+        print("long range generate_and_score totals", parity.totals_report(tot2, r_tot))
+        np.testing.assert_array_equal(fb, fr)
+        np.testing.assert_array_equal(cov2, r_cov)
+        parity.assert_totals_exact(tot2, r_tot)
+        assert rep2.best_idx == r_rep.best_idx and r_cov.max() > 100
+
+
+def test_long_range_score_many_poses(oracle, long_range):
+    """60 poses x 600 cells (61 rows: past kWideMaxRays) with no knob set: the production choice
+    at max_distance 110 is k_score_cells<false>, one lane per ray, the step table in global
+    memory.  Same assertions as test_long_range_score, the totals under the exact bar (first
+    MI355X run: 0 of 60 totals differ on either tick; 47 of 20,436 positive cells do, 26 up and
+    21 down, the largest by 8 ulps)."""
+    lr = long_range
+    md = 110.0
+    assert (lr.many_poses.shape[0] + 1) * lr.xyz.shape[0] > 1 << 15
+    ref = _long_score_ref(oracle, lr, md, "many_poses")
+    with _abi.Context(0) as ctx:
+        ctx.set_terrain(lr.cloud, point_step=16)
+        ctx.set_cells(lr.xyz, lr.nrm)
+        _long_score_check(ctx, lr, ref, md, lr.many_poses, tag="60 poses")
+
+
+def test_long_range_step_table_cache(oracle, long_range):
+    """ensure_steps caches the step table by its end, shares the device buffer between the fan
+    and the scoring and regrows it: on ONE context, queries at max_distance 15 -> 110 -> 15 ->
+    77.6 -> 110, fan and scoring taking turns at being the first to ask for a new table, each
+    compared with the oracle -- a stale or short table shows as wrong first hits or flags."""
+    lr = long_range
+    n_az, n_el = 100, 37
+
+    def fan_q(ctx, md):
+        r_blocked, r_units, r_fh = _long_fan_ref(oracle, lr, md, n_az, n_el)
+        blocked, units, fh, _ = ctx.raycast_fan(lr.fan_poses, _long_fan_params(n_az, n_el, md),
+                                                want_first_hit=True)
+        np.testing.assert_array_equal(fh, r_fh, err_msg=f"fan {md}")
+        np.testing.assert_array_equal(blocked, r_blocked, err_msg=f"fan {md}")
+        np.testing.assert_array_equal(units, r_units, err_msg=f"fan {md}")
+
+    def score_q(ctx, md):
+        r_tot, r_cov, r_rep, r_fl = _long_score_ref(oracle, lr, md)["ticks"][0]
+        fg = np.zeros(lr.xyz.shape[0], np.uint8)
+        tot, cov, rep = ctx.score_poses(lr.score_poses, lr.zx,
+                                        _abi.default_vl_params(max_distance=md), fg)
+        np.testing.assert_array_equal(fg, r_fl, err_msg=f"score {md}")
+        np.testing.assert_array_equal(cov, r_cov, err_msg=f"score {md}")
+        parity.assert_totals_exact(tot, r_tot)
+        _assert_report_equal(rep.as_dict(), r_rep)
+
+    assert _abi.step_table(15.0 - 0.08).size == 49
+    assert _long_score_ref(oracle, lr, 15.0)["ticks"][0][1].max() > 20   # cells in range at 15 m
+    with _abi.Context(0) as ctx:
+        ctx.set_terrain(lr.cloud, point_step=16)
+        ctx.set_cells(lr.xyz, lr.nrm)
+        for what, md in (("fan", 15.0), ("score", 15.0), ("score", 110.0), ("fan", 110.0),
+                         ("fan", 15.0), ("score", 15.0), ("score", 77.6), ("fan", 77.6),
+                         ("fan", 110.0), ("score", 110.0)):
+            (fan_q if what == "fan" else score_q)(ctx, md)
+
+
+@pytest.mark.parametrize("md", [15.0, 110.0])
+@pytest.mark.parametrize("g", ["2", "4", "8", "16"])
+def test_score_wide_lane_counts(oracle, long_range, g, md, monkeypatch):
+    """PCP_SCORE_WIDE_G = 2 / 4 / 8 / 16 selects k_score_cells_wide<true, G> while the step
+    table fits LDS (max_distance 15); past it (max_distance 110) only the 16-lane kernel exists
+    and the launcher sizes its grid from the width it launches.  600 cells, so a grid sized for
+    G < 16 lanes but run by the 16-lane kernel would score C G / 16 cells only.  The launcher
+    did that before: at max_distance 110 this test failed on it for G = 2 / 4 / 8, with 1,020 /
+    859 / 589 of the 3,000 pose cells and 303 / 255 / 177 of the 600 zx120 cells positive on
+    one side only, in every row.  Every cell and row of pcp_score_matrix, and the totals, flags
+    and covered counts of pcp_score_poses, against the oracle; totals under the exact bar
+    (first MI355X run: 0 differ for every G; cells: 1 of 448 at 15 m, 7 of 1,996 at 110 m)."""
+    lr = long_range
+    ref = _long_score_ref(oracle, lr, md)
+    monkeypatch.setenv("PCP_SCORE_WIDE_G", g)
+    assert lr.xyz.shape[0] * 2 // 16 < lr.xyz.shape[0]
+    with _abi.Context(0) as ctx:
+        ctx.set_terrain(lr.cloud, point_step=16)
+        ctx.set_cells(lr.xyz, lr.nrm)
+        params = _abi.default_vl_params(max_distance=md)
+        sm, sz = ctx.score_matrix(lr.score_poses, lr.zx, params)
+        bad_m, bad_z = (sm > 0) != (ref["sm"] > 0), (sz > 0) != (ref["sz"] > 0)
+        rows = np.flatnonzero(bad_m.any(1))
+        assert rows.size == 0 and not bad_z.any(), (rows, int(bad_m.sum()), int(bad_z.sum()))
+        _long_score_check(ctx, lr, ref, md, lr.score_poses, tag=f"G={g}")
+
+
+@pytest.mark.parametrize("g", ["3", "32", "-1", "x", "0", "4x", ""])
+def test_score_wide_lane_count_rejected(g, monkeypatch, capfd):
+    """A PCP_SCORE_WIDE_G that is not one of the instantiated widths never reaches a launch:
+    pcp_create returns PCP_E_INVALID and names the variable on stderr (no context exists to
+    carry the message); with the variable unset again a context is created as usual."""
+    monkeypatch.setenv("PCP_SCORE_WIDE_G", g)
+    with pytest.raises(_abi.PcpError) as e:
+        _abi.Context(0)
+    assert e.value.code == _abi.PCP_E_INVALID
+    assert "PCP_SCORE_WIDE_G" in capfd.readouterr().err
+    monkeypatch.delenv("PCP_SCORE_WIDE_G")
+    with _abi.Context(0) as ctx:
+        assert ctx.cells_count() == 0
+
+
+def test_step_table_upper_limit(oracle):
+    """PCP_MAX_STEPS (include/pcp_abi.h): a max_distance whose step table is longer is refused
+    with PCP_E_INVALID by the fan and by every scoring entry point before anything is launched
+    (no terrain is set here, so nothing could march anyway) -- K = 32768, which an int16 first
+    hit cannot hold, and K = PCP_MAX_STEPS + 1 -- and the context answers normal queries
+    afterwards, the longest accepted table included."""
+    M = _abi.MAX_STEPS
+    md_of = lambda K: 0.5 + 0.3 * (K - 1) + 0.08 + 0.15   # s_{K-1} < md - 0.08 <= s_K
+    for K in (32768, M + 1, M):
+        assert _abi.step_table(md_of(K) - 0.08).size == K
+    assert M <= 32767
+    poses = np.array([[0.0, 0.0, 1.0, 0.0, 0.0], [3.0, 1.0, 2.0, 0.0, 1.0]])
+    xyz = np.array([[2.0, 0.0, 0.5], [4.0, 1.0, 0.2], [900.0, 0.0, 1.0]])
+    nrm = np.tile(np.array([[0.0, 0.0, 1.0]], np.float32), (3, 1))
+    zx = np.array([0.0, 0.0, 2.0, 0.0, 0.0])
+    bb = np.array([0.0, 4.0, -2.0, 2.0, 0.0, 1.0])
+
+    def refused(call):
+        with pytest.raises(_abi.PcpError) as e:
+            call()
+        assert e.value.code == _abi.PCP_E_INVALID and "PCP_MAX_STEPS" in str(e.value), e.value
+
+    with _abi.Context(0) as ctx:
+        ctx.set_cells(xyz, nrm)
+        fan15 = _abi.fan_params(n_az=64, n_el=2)
+        b0, u0, fh0, _ = ctx.raycast_fan(poses, fan15, want_first_hit=True)
+        for K in (32768, M + 1):
+            fan = _abi.fan_params(n_az=64, n_el=2, max_distance=md_of(K))
+            vp = _abi.default_vl_params(max_distance=md_of(K), num_candidates=9)
+            refused(lambda: ctx.raycast_fan(poses, fan, want_first_hit=True))
+            refused(lambda: ctx.raycast_fan(poses, fan))
+            refused(lambda: ctx.raycast_fan_stats(poses, fan))
+            refused(lambda: ctx.raycast_fan_burst(poses, fan, reps=1))
+            refused(lambda: ctx.score_poses(poses, zx, vp, np.zeros(3, np.uint8)))
+            refused(lambda: ctx.score_matrix(poses, zx, vp))
+            refused(lambda: ctx.score_poses_stats(poses, zx, vp))
+            refused(lambda: ctx.score_poses_burst(poses, zx, vp, reps=1))
+            refused(lambda: ctx.generate_and_score(bb, vp, zx, np.zeros(3, np.uint8)))
+            # the cached (15 m) table is still the one in use
+            b1, u1, fh1, _ = ctx.raycast_fan(poses, fan15, want_first_hit=True)
+            np.testing.assert_array_equal(fh1, fh0)
+            np.testing.assert_array_equal(u1, u0)
+        assert (fh0 == -1).all() and u0.tolist() == [64 * 2 * 49] * 2
+        # a normal scoring query, then the longest table that is accepted (md_of(M): ~1,229 m,
+        # the cell at 900 m in range)
+        fanM = _abi.fan_params(n_az=64, n_el=2, max_distance=md_of(M))
+        bM, uM, fhM, _ = ctx.raycast_fan(poses, fanM, want_first_hit=True)
+        assert bM.tolist() == [0, 0] and uM.tolist() == [64 * 2 * M] * 2 and (fhM == -1).all()
+        for md, n_cov in ((15.0, 2), (md_of(M), 3)):
+            fg = np.zeros(3, np.uint8)
+            fr = fg.copy()
+            tot, cov, rep = ctx.score_poses(poses, zx, _abi.default_vl_params(max_distance=md), fg)
+            r_tot, r_cov, r_rep = oracle.score_poses(None, None, xyz, nrm, poses, zx,
+                                                     oracle.vl_params(max_distance=md), fr)
+            np.testing.assert_array_equal(fg, fr)
+            np.testing.assert_array_equal(cov, r_cov)
+            parity.assert_totals(tot, r_tot)
+            assert r_cov.tolist() == [n_cov] * 2 and rep.total_cells == 3
 
 
 def _need_devices(devices):

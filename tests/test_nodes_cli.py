@@ -293,14 +293,15 @@ def _oracle_frame(tmp_path, pre, oracle):
 
 def test_parity_bar_catches_drift_on_c5_frames(tmp_path, oracle, scene, cells):
     """VERDICT r5 item 5 on the C5 chain's own frames: each dumped frame's totals pass
-    tests/parity.py's totals bar against the oracle chain's; then the frame's scoring inputs
+    tests/parity.py's EXACT totals bar against the oracle chain's; then the frame's scoring inputs
     (the oracle chain's terrain, zx120 cloud, cells, normals and candidates -- the chain test
     shows the device's are bit-identical) are scored per cell by the production build, the
     `make perturb` build (every cell one ulp up) and the `make perturb8` build (every 8th cell:
     partial drift), against the oracle's per-cell values: production passes the per-cell bar,
     both perturbed builds fail it.  The production build's totals are bit-identical to the
     oracle's here (the scoring rounds acos / sin as glibc does; with ocml's, 2-20 % of a frame's
-    totals differed) and pass the totals bar; the every-cell drift fails that bar too."""
+    totals differed) and pass the exact totals bar (0 differing bit patterns); the every-cell
+    and the every-8th-cell drifts fail that bar too, on every frame."""
     from test_gpu_parity import PERTURB8_LIB, PERTURB_LIB, _cell_census
 
     from pointcloud_processor_amd import _abi
@@ -318,7 +319,7 @@ def test_parity_bar_catches_drift_on_c5_frames(tmp_path, oracle, scene, cells):
         got = np.fromfile(tmp_path / (pre + "tot.f64"), np.float64)
         rep = parity.totals_report(got, tot)
         print("frame", d["frame"], "totals", rep)
-        assert parity.totals_match(got, tot), rep
+        parity.assert_totals_exact(got, tot)   # the chain's own totals: 0 differing bit patterns
         assert d["best_idx"] == best
         r_sm, r_sz = oracle.score_matrix(oracle.Cloud(inp["terrain"]), oracle.Cloud(inp["aux"]),
                                          inp["xyz"], inp["cn"], inp["poses"], inp["zx"],
@@ -337,11 +338,10 @@ def test_parity_bar_catches_drift_on_c5_frames(tmp_path, oracle, scene, cells):
             print("frame", d["frame"], tag, cen, parity.cell_bar(cen), "totals", trep)
             assert cen["zero_mismatch"] == 0, (tag, cen)
             assert parity.cell_bar(cen) == (tag == "prod"), (tag, cen)
-            # the totals bar: production passes, the every-cell drift fails it; perturb8's
-            # drift moves a total by ~0.15 ulp on average (5 of 91 on frame 0, 10 of 91 on
-            # the 91-candidate tick), which only the per-cell bar sees on every frame
-            if tag != "perturbed8":
-                assert parity.totals_match(t_lib, tot) == (tag == "prod"), (tag, trep)
+            # the exact totals bar: production passes it, the every-cell drift and the
+            # every-8th-cell drift (5 of 91 totals on frame 0, which the max(2, 5 %) bar let
+            # through) both fail it, on every frame
+            assert parity.totals_exact(t_lib, tot) == (tag == "prod"), (tag, trep)
             assert r_lib.best_idx == best
 
 
