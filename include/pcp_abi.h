@@ -101,6 +101,7 @@ enum pcp_kernel_id {
     PCP_K_EXCAV_SETUP,       /* excavation-area normals + cell grid                    */
     PCP_K_VOXEL_REDO,        /* bucket-chain frames redone by the LSD chain (a bucket past
                               * its LDS capacity); launches = frames redone             */
+    PCP_K_PLACE,             /* pcp_place_sensors' placement rounds (one launch per round)  */
     PCP_K_COUNT
 };
 int pcp_profile_enable(pcp_ctx *ctx, int enable);
@@ -363,6 +364,45 @@ int pcp_generate_and_score(pcp_ctx *ctx, const double grid_bbox[6], const pcp_vl
                            const double zx120_pose5[5], double *poses5, uint64_t cap,
                            uint64_t *n_out, uint8_t *cell_flags, double *total_score,
                            int32_t *covered, pcp_vl_report *rep);
+
+/* Greedy placement of several mobile sensors: runOptimization's "best of one" (:460-475)
+ * generalised.  A cell's combined score is the max over zx120 and every placed sensor, a pose's
+ * total the ordered sum of the positive combined scores (evaluatePosition, :627-654).  With
+ * S[p][c], Z[c] the values pcp_score_matrix returns for the same arguments, max(a, b) the
+ * reference's std::max ((a < b) ? b : a) and osum(v) the sum, in cell order from +0.0, of the
+ * elements with v[c] > 0:  base = Z, T = osum(base) (*zx120_total, pcp_vl_report's
+ * zx120_total_score), *zx120_covered = #{Z > 0}, owner[c] = Z[c] > 0 ? PCP_OWNER_ZX120 :
+ * PCP_OWNER_NONE, every pose alive.  Round r = 0 .. k_max - 1: stop when no pose is alive;
+ * t[p] = osum(max(base[c], S[p][c])) and cov[p] = #{.. > 0} for the alive poses (round_totals
+ * [r][p]; -inf for the others); b = the first maximum (strict '>', :471-474); stop unless
+ * t[b] > T (no pose adds anything); selected[r] = b, total_after[r] = T = t[b], covered_after[r]
+ * = cov[b]; every cell with base[c] < S[b][c] gets owner r and base[c] = S[b][c] (ties keep the
+ * earlier owner); b leaves the search, and with min_separation > 0 so does every pose p with
+ * dx * dx + dy * dy < min_separation * min_separation (dx = x_p - x_b, dy = y_p - y_b, double,
+ * each operation rounded).  *n_selected = rounds recorded; entries and rows from there on are not
+ * written; cell_score = base.  One synchronisation; the caller's GridCell flags are neither read
+ * nor written.  n <= 65535; PCP_E_INVALID (before any launch) for k_max outside 1 ..
+ * PCP_PLACE_MAX, reserved != 0 or a step table past PCP_MAX_STEPS.  n == 0 or no cells: PCP_OK,
+ * *n_selected = 0. */
+#define PCP_PLACE_MAX 16
+#define PCP_OWNER_ZX120 (-1)
+#define PCP_OWNER_NONE  (-2)
+typedef struct pcp_place_params {
+    int32_t k_max;          /* sensors to place, 1 .. PCP_PLACE_MAX */
+    int32_t reserved;       /* 0 */
+    double min_separation;  /* metres in XY between placed poses; <= 0: no constraint */
+} pcp_place_params;
+int pcp_place_sensors(pcp_ctx *ctx, const double *poses5, uint64_t n,
+                      const double zx120_pose5[5], const pcp_vl_params *p,
+                      const pcp_place_params *pp,
+                      int64_t *selected,        /* [k_max] pose index per round            */
+                      double *total_after,      /* [k_max] total with sensors 0..r placed   */
+                      int32_t *covered_after,   /* [k_max] covered cells, same             */
+                      double *round_totals,     /* nullable [k_max][n]                      */
+                      double *cell_score,       /* nullable [n_cells] final combined score  */
+                      int32_t *cell_owner,      /* nullable [n_cells] round index / PCP_OWNER_* */
+                      double *zx120_total, int32_t *zx120_covered, /* nullable */
+                      int32_t *n_selected);
 
 /* Dense ray fan (BASELINE configs[1]): per pose, n_az x n_el rays, ray (i, j) with local
  * direction (cos e_j cos a_i, cos e_j sin a_i, sin e_j), a_i = 2*pi*i/n_az,

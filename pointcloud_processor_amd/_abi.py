@@ -31,7 +31,7 @@ F_RANGE_Z, F_FOV_Z, F_VIS_Z, F_RANGE_M, F_FOV_M, F_VIS_M = 1, 2, 4, 8, 16, 32
 
 KERNELS = ["raycast_fan", "score_cells", "zx120_cells", "pose_sum", "cell_flags",
            "candidates", "index_build", "crop", "voxel", "transform", "filter_merge", "excavate",
-           "excav_setup", "voxel_redo"]
+           "excav_setup", "voxel_redo", "place_sensors"]
 
 
 class PcpError(RuntimeError):
@@ -75,6 +75,15 @@ class FanParams(C.Structure):
 
 
 ABI_VERSION = 2   # PCP_ABI_VERSION of include/pcp_abi.h
+
+PLACE_MAX = 16     # PCP_PLACE_MAX: sensors one pcp_place_sensors call places at most
+OWNER_ZX120 = -1   # PCP_OWNER_ZX120 / PCP_OWNER_NONE: cell owners that are no placement round
+OWNER_NONE = -2
+
+
+class PlaceParams(C.Structure):
+    """pcp_place_params."""
+    _fields_ = [("k_max", C.c_int32), ("reserved", C.c_int32), ("min_separation", C.c_double)]
 
 
 class IndexInfo(C.Structure):
@@ -166,6 +175,8 @@ _SIGS = [
                                             C.POINTER(VlReport), C.POINTER(C.c_double)]),
     ("pcp_score_poses_stats", C.c_int, [_P, _P, C.c_uint64, _P, C.POINTER(VlParams), _P]),
     ("pcp_score_matrix", C.c_int, [_P, _P, C.c_uint64, _P, C.POINTER(VlParams), _P, _P]),
+    ("pcp_place_sensors", C.c_int, [_P, _P, C.c_uint64, _P, C.POINTER(VlParams),
+                                    C.POINTER(PlaceParams), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("pcp_debug_exclusive_scan", C.c_int, [_P, _P, C.c_uint64, _P]),
     ("pcp_score_poses_burst", C.c_int, [_P, _P, C.c_uint64, _P, C.POINTER(VlParams), C.c_int,
                                         C.POINTER(C.c_double)]),
@@ -856,6 +867,43 @@ class Context:
         self._check(self.lib.pcp_score_matrix(self.h, _ptr(poses), P, _ptr(zx), C.byref(params),
                                               _ptr(sm), _ptr(sz)), "pcp_score_matrix")
         return sm[:P, :C_].copy(), sz[:C_].copy()
+
+    def place_sensors(self, poses5, zx120_pose5, params: VlParams, k_max: int,
+                      min_separation: float = 0.0, want_round_totals: bool = False,
+                      want_cells: bool = False, reserved: int = 0) -> dict:
+        """pcp_place_sensors: up to k_max of the poses placed greedily (a cell's combined score
+        is the max over zx120 and the placed sensors; each round takes the pose with the highest
+        ordered total while it adds anything).  -> dict: n_selected, selected / total_after /
+        covered_after [n_selected], zx120_total, zx120_covered, and on request round_totals
+        [n_selected, P] (-inf at poses out of the search), cell_score / cell_owner [n_cells]."""
+        poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 5)
+        zx = np.ascontiguousarray(zx120_pose5, np.float64)
+        P = poses.shape[0]
+        pp = PlaceParams(int(k_max), int(reserved), float(min_separation))
+        kk = max(min(int(k_max), PLACE_MAX), 1)
+        sel = np.full(kk, -1, np.int64)
+        tot = np.zeros(kk, np.float64)
+        cov = np.zeros(kk, np.int32)
+        rt = np.zeros((kk, max(P, 1)), np.float64) if want_round_totals else None
+        C_ = self.cells_count() if want_cells else 0
+        cs = np.zeros(max(C_, 1), np.float64) if want_cells else None
+        co = np.zeros(max(C_, 1), np.int32) if want_cells else None
+        zt, zc, ns = C.c_double(), C.c_int32(), C.c_int32()
+        self._check(self.lib.pcp_place_sensors(self.h, _ptr(poses) if P else None, P, _ptr(zx),
+                                               C.byref(params), C.byref(pp), _ptr(sel), _ptr(tot),
+                                               _ptr(cov), _ptr(rt), _ptr(cs), _ptr(co),
+                                               C.byref(zt), C.byref(zc), C.byref(ns)),
+                    "pcp_place_sensors")
+        n = ns.value
+        out = {"n_selected": n, "selected": sel[:n].copy(), "total_after": tot[:n].copy(),
+               "covered_after": cov[:n].copy(), "zx120_total": zt.value,
+               "zx120_covered": zc.value}
+        if want_round_totals:
+            out["round_totals"] = rt[:n, :P].copy()
+        if want_cells:
+            out["cell_score"] = cs[:C_].copy()
+            out["cell_owner"] = co[:C_].copy()
+        return out
 
     def score_poses_stats(self, poses5, zx120_pose5, params: VlParams) -> dict:
         """pcp_score_poses_stats: the gather lane-loads of the query's visibility rays

@@ -5,6 +5,8 @@
 //   pcp_nodes_cli merge   ROBOT.f32 RN ZX.f32 ZN TR(7) TZ(7) OUT.f32        (t xyz, q xyzw)
 //   pcp_nodes_cli vlidar  TERRAIN.f32 TN AUX.f32 AN CELLS.f64 NORMALS.f32 CN BBOX(6) ZXT(3) NUMC
 //                         MAXD OUT_TOTALS.f64 OUT_FLAGS.u8 OUT_REPORT.txt [TICKS]
+//   pcp_nodes_cli place   TERRAIN.f32 TN AUX.f32 AN CELLS.f64 NORMALS.f32 CN BBOX(6) ZXT(3) NUMC
+//                         MAXD KMAX MINSEP OUT_SELECTED.i64 OUT_TOTALS.f64 OUT_REPORT.txt
 //   pcp_nodes_cli drivable IN.f32 N STEP TF(7) R1(2) R2(2) OUT.i8
 //   pcp_nodes_cli replay  TERRAIN.f32 TN CELLS.f64 NORMALS.f32 CN BBOX(6) FRAMES POINTS
 //
@@ -22,6 +24,7 @@
 #include <vector>
 
 #include "pcp_nodes.hpp"
+#include "pcp_placement.hpp"
 
 using namespace pcp;
 
@@ -178,6 +181,60 @@ static int cmd_vlidar(Device &dev, char **a, int argc) {
                 "\"devices\": %d, \"rccl\": %d}\n",
                 r.candidates.size(), (long long)r.report.best_idx, r.best.x, r.best.y, r.best.z,
                 md ? md->size() : 1, md && md->usesRccl() ? 1 : 0);
+    return 0;
+}
+
+// one tick of the virtual-LiDAR node (vlidar's inputs), then KMAX mobile sensors placed greedily
+// among its candidates: the selected candidates, the totals after each and the placement's table
+static int cmd_place(Device &dev, char **a) {
+    const auto t = read_file(a[0]), ax = read_file(a[2]), c = read_file(a[4]),
+               nr = read_file(a[5]);
+    const size_t tn = std::strtoull(a[1], nullptr, 10), an = std::strtoull(a[3], nullptr, 10),
+                 cn = std::strtoull(a[6], nullptr, 10);
+    const auto bbox = tuple(a[7]), zxt = tuple(a[8]);
+    SimplifiedDualLidarOptimizer::Params p;
+    p.num_candidates = std::atoi(a[9]);
+    p.max_distance = std::strtod(a[10], nullptr);
+    MobileLidarPlacement::Params pp;
+    pp.num_mobile_lidars = std::atoi(a[11]);
+    pp.min_separation = std::strtod(a[12], nullptr);
+    SimplifiedDualLidarOptimizer node(dev, p);
+    Transform zx;
+    zx.t[0] = zxt[0];
+    zx.t[1] = zxt[1];
+    zx.t[2] = zxt[2];
+    node.terrainCallback(cloud_from(t, tn, 32, "map"));
+    node.zx120PointsCallback(cloud_from(ax, an, 32, "velodyne_link"));
+    std::vector<double> xyz(cn * 3);
+    std::vector<float> nrm(cn * 3);
+    std::memcpy(xyz.data(), c.data(), xyz.size() * 8);
+    std::memcpy(nrm.data(), nr.data(), nrm.size() * 4);
+    node.setExcavationGrid(xyz, nrm, bbox.data());
+    const auto tick = node.runOptimization(&zx);
+    if (!tick.ran) {
+        std::fprintf(stderr, "place: %s\n", node.lastError().c_str());
+        return 1;
+    }
+    MobileLidarPlacement placement(pp);
+    if (placement.place(dev, SimplifiedDualLidarOptimizer::Result{}, p).ran) return 3;   // no tick
+    const auto r = placement.place(dev, tick, p);
+    if (!r.ran) {
+        std::fprintf(stderr, "place: %s\n", placement.lastError().c_str());
+        return 1;
+    }
+    std::vector<int64_t> sel;
+    std::vector<double> tot;
+    for (const auto &q : r.rounds) {
+        sel.push_back(q.candidate);
+        tot.push_back(q.total);
+    }
+    write_file(a[13], sel.data(), sel.size() * 8);
+    write_file(a[14], tot.data(), tot.size() * 8);
+    write_file(a[15], r.log.data(), r.log.size());
+    std::printf("{\"n_candidates\": %zu, \"n_selected\": %zu, \"zx120_total\": %.17g, "
+                "\"zx120_covered\": %d, \"total_cells\": %d}\n",
+                tick.candidates.size(), r.rounds.size(), r.zx120_total, r.zx120_covered,
+                r.total_cells);
     return 0;
 }
 
@@ -549,13 +606,14 @@ int main(int argc, char **argv) {
         if (!hp || std::atoi(hp) != 0) setenv("HSA_ENABLE_INTERRUPT", "0", 0);
     }
     if (argc < 2) {
-        std::fprintf(stderr, "usage: pcp_nodes_cli filter|merge|vlidar|area|drivable|replay ...\n");
+        std::fprintf(stderr, "usage: pcp_nodes_cli filter|merge|vlidar|place|area|drivable|replay ...\n");
         return 2;
     }
     const std::string cmd = argv[1];
     const int need = cmd == "filter"   ? 8
                      : cmd == "merge"  ? 7
                      : cmd == "vlidar" ? 14
+                     : cmd == "place"  ? 16
                      : cmd == "area"   ? 10
                      : cmd == "drivable" ? 7
                      : cmd == "replay" ? 8
@@ -569,6 +627,7 @@ int main(int argc, char **argv) {
         if (cmd == "filter") return cmd_filter(dev, argv + 2);
         if (cmd == "merge") return cmd_merge(dev, argv + 2);
         if (cmd == "vlidar") return cmd_vlidar(dev, argv + 2, argc - 2);
+        if (cmd == "place") return cmd_place(dev, argv + 2);
         if (cmd == "area") return cmd_area(dev, argv + 2);
         if (cmd == "drivable") return cmd_drivable(dev, argv + 2);
         return cmd_replay(dev, argv + 2);

@@ -1,0 +1,55 @@
+// pcp_placement.hpp -- several mobile LiDARs: the greedy placement above pcp_place_sensors, for
+// the candidates and the zx120 pose of a SimplifiedDualLidarOptimizer tick.  A translation unit
+// of its own: pcp_nodes.cpp (the drop-in surface of the reference's nodes) does not reference it.
+#pragma once
+
+#include <string>
+#include <vector>
+
+#include "pcp_nodes.hpp"
+
+namespace pcp {
+
+class MobileLidarPlacement {
+   public:
+    struct Params {
+        int num_mobile_lidars = 2;     // sensors to place, 1 .. PCP_PLACE_MAX
+        double min_separation = 0.0;   // metres in XY between placed sensors; <= 0: none
+    };
+    struct Round {
+        int64_t candidate = -1;        // index into the tick's candidates
+        double total = 0;              // total with sensors 0 .. r placed
+        double gain = 0;               // total - the total before this sensor
+        int32_t covered = 0;           // cells with a positive combined score
+        double coverage_ratio = 0;     // covered / total cells
+    };
+    struct Result {
+        bool ran = false;              // false: the tick did not run, or the call failed
+        std::vector<SimplifiedDualLidarOptimizer::LidarPosition> placed;   // in placement order,
+                                                                            // total_score = Round::total
+        std::vector<Round> rounds;     // one per placed sensor
+        double zx120_total = 0;        // the total of the zx120 sensor alone
+        int32_t zx120_covered = 0;
+        int32_t total_cells = 0;
+        std::string log;               // a table in the style of optimization_log
+    };
+    MobileLidarPlacement() = default;
+    explicit MobileLidarPlacement(const Params &p) : p_(p) {}
+    Params &params() { return p_; }
+    const Params &params() const { return p_; }
+    // the tick's candidates placed greedily against the context's terrain, zx120 cloud and cells
+    // (the state the tick ran on); vl = the tick's parameters.  The optimizer's GridCell flags
+    // are not touched
+    Result place(Device &dev, const SimplifiedDualLidarOptimizer::Result &tick,
+                 const SimplifiedDualLidarOptimizer::Params &vl);
+    const std::string &lastError() const { return err_; }
+
+   private:
+    Params p_;
+    std::string err_;
+};
+
+// the placement's table: host arithmetic only
+std::string placement_log(const MobileLidarPlacement::Result &r);
+
+}  // namespace pcp

@@ -765,6 +765,8 @@ void pcp_destroy(pcp_ctx *ctx) {
     ctx->scan_state.release();
     ctx->carve_ctr.release();
     ctx->exc_land.release();
+    ctx->place_d.release();
+    ctx->place_host.release();
     if (ctx->area_stream) (void)hipStreamDestroy(ctx->area_stream);
     (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -878,7 +880,7 @@ const char *pcp_kernel_name(int kid) {
                                              "pose_sum",    "cell_flags",  "candidates",
                                              "index_build", "crop",        "voxel",
                                              "transform",   "filter_merge", "excavate",
-                                             "excav_setup", "voxel_redo"};
+                                             "excav_setup", "voxel_redo",  "place_sensors"};
     if (kid < 0 || kid >= PCP_K_COUNT) return "unknown";
     return names[kid];
 }

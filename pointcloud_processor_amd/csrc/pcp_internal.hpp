@@ -318,6 +318,11 @@ struct pcp_ctx {
     pcp::DevBuf stage, scratch[8];
     pcp::DevBuf fan_tab, poses_d, steps_d, out_a, out_b, out_c, out_d, stats_d;
     pcp::PinnedBuf fan_host;                 // pinned staging of poses in / counts out
+    // pcp_place_sensors (pcp_place.hip): the rounds' state, base / owner, round totals and alive
+    // mask, and the pinned landing of its one download (its own: the scoring's buffers stay as
+    // pcp_score_poses leaves and expects them)
+    pcp::DevBuf place_d;
+    pcp::PinnedBuf place_host;
     pcp::PinnedBuf res_host;                 // pinned landing of the filter chain's sizes
     pcp::PinnedBuf fm_res_host;              // pcp_filter_merge's result sizes, stored by its
                                              // kernels themselves (fixed: a graph holds it)
