@@ -434,6 +434,58 @@ int pcp_raycast_fan_stats(pcp_ctx *ctx, const double *poses5, uint64_t n,
 int pcp_raycast_fan_burst(pcp_ctx *ctx, const double *poses5, uint64_t n,
                           const pcp_fan_params *fan, int reps, double *ms_per_launch);
 
+/* The simulated scans of up to PCP_SCAN_MAX_POSES LiDAR poses: pcp_raycast_fan's fan, every
+ * blocked ray resolved to the terrain point that stopped it.  N = the input point count of the
+ * cloud the current terrain index was built from (the last non-empty pcp_set_terrain, non-finite
+ * points included: they are in no index and are never hit; 0 without an index).
+ * For pose p and ray id ray = j * n_az + i:  k = first_hit[p][j][i] as pcp_raycast_fan reports
+ * it (the same march); k < 0: no return.  Otherwise q = (float(px + dx s_k), float(py + dy s_k),
+ * float(pz + dz s_k)) with s_k the step table entry and (dx, dy, dz) = (cy lx - sy ly,
+ * sy lx + cy ly, lz) the march's doubles (no contraction); the candidates are the points with
+ * acc < r2, acc = ((0 + d0 d0) + d1 d1) + d2 d2 in float, d = q - point, r2 =
+ * float((0.08 * 0.7)^2) -- the set that made sample k blocked, never empty; the hit point is the
+ * candidate of smallest acc, ties to the lowest input index; range = (float)sqrt((ex ex + ey ey)
+ * + ez ez), e = (double)point - pose xyz, in double, every operation rounded.
+ *   returns        the blocked rays of pose 0 in ascending ray id, then pose 1's, ...: x, y, z
+ *                  the hit point's own bits (map frame), its range, the ray id, the point's input
+ *                  index.  At most returns_cap records are written.
+ *   offsets        [n + 1]: offsets[p] = where pose p's returns start, offsets[n] = the total =
+ *                  *n_returns (a pose without a blocked ray has an empty segment)
+ *   hit_point      nullable int32 [n][n_el][n_az]: the hit point's input index, or -1
+ *   range_img      nullable float, same shape: the range, or -1.0f
+ *   first_hit      nullable, as pcp_raycast_fan's
+ *   point_mask     nullable uint64 [N] (mask_cap entries available): bit p set iff some ray of
+ *                  pose p resolved to that point; every other bit and the entries of non-finite
+ *                  points are zero.  *n_points (nullable) = N.
+ *   seen_points    nullable uint32 [n]: points with bit p set
+ *   n_seen_any     nullable: points with any bit set (the other points are the blind spots)
+ * PCP_E_INVALID before any launch (nothing written) for n > PCP_SCAN_MAX_POSES and for what
+ * pcp_raycast_fan rejects (fan dimensions, a step table past PCP_MAX_STEPS).  PCP_E_CAPACITY when
+ * returns_cap < the total or (point_mask given) mask_cap < N: *n_returns, *n_points, offsets, the
+ * counts and the dense per-ray outputs are valid, no record is written past returns_cap.
+ * n == 0: PCP_OK, *n_returns = 0, offsets[0] = 0, the mask all zero.  Deterministic: two calls
+ * give identical bytes.  One host synchronisation per call; the caller's GridCell flags and the
+ * other queries' device buffers are not touched. */
+#define PCP_SCAN_MAX_POSES 64
+typedef struct pcp_scan_return {
+    float x, y, z;       /* the hit terrain point (its own bits) */
+    float range;         /* metres from the pose */
+    uint32_t ray;        /* j * n_az + i */
+    uint32_t point;      /* input index of the hit point in the terrain cloud */
+} pcp_scan_return;
+int pcp_simulate_scan(pcp_ctx *ctx, const double *poses5, uint64_t n, const pcp_fan_params *fan,
+                      pcp_scan_return *returns, uint64_t returns_cap, uint64_t *n_returns,
+                      uint64_t *offsets, int32_t *hit_point, float *range_img,
+                      int16_t *first_hit, uint64_t *point_mask, uint64_t mask_cap,
+                      uint64_t *n_points, uint32_t *seen_points, uint64_t *n_seen_any);
+
+/* Kernel timing of pcp_simulate_scan (the timing tool only): ms[0] = the query's production fan
+ * kernel per launch (`reps` launches between two stream events, as pcp_raycast_fan_burst),
+ * ms[1] = its resolve phase -- clears, wave-base scan, k_scan_resolve (records and mask, no dense
+ * images), mask counts -- per repetition, `reps` repetitions between two events.  n >= 1. */
+int pcp_simulate_scan_burst(pcp_ctx *ctx, const double *poses5, uint64_t n,
+                            const pcp_fan_params *fan, int reps, double ms[2]);
+
 /* Diagnostic build with s_memtime stamps (shader clock) per wave: stamps[(p*W + w)*4 + i],
  * W = ceil(n_az*n_el/64), i = 0 start, 1 after direction setup, 2 after the march, 3 end.
  * For locating where wave lifetime goes; never used for timing. */

@@ -86,6 +86,20 @@ class PlaceParams(C.Structure):
     _fields_ = [("k_max", C.c_int32), ("reserved", C.c_int32), ("min_separation", C.c_double)]
 
 
+SCAN_MAX_POSES = 64   # PCP_SCAN_MAX_POSES: poses one pcp_simulate_scan call casts (mask bits)
+
+
+class ScanReturn(C.Structure):
+    """pcp_scan_return: one blocked ray's hit (24 bytes)."""
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("range", C.c_float),
+                ("ray", C.c_uint32), ("point", C.c_uint32)]
+
+
+# the same record as a NumPy structured dtype (Context.simulate_scan's `returns`)
+SCAN_RETURN_DTYPE = np.dtype([("x", np.float32), ("y", np.float32), ("z", np.float32),
+                              ("range", np.float32), ("ray", np.uint32), ("point", np.uint32)])
+
+
 class IndexInfo(C.Structure):
     _fields_ = [("n_points", C.c_uint64), ("cell", C.c_double), ("nx", C.c_int32),
                 ("ny", C.c_int32), ("nz", C.c_int32), ("bmin", C.c_double * 3),
@@ -177,6 +191,11 @@ _SIGS = [
     ("pcp_score_matrix", C.c_int, [_P, _P, C.c_uint64, _P, C.POINTER(VlParams), _P, _P]),
     ("pcp_place_sensors", C.c_int, [_P, _P, C.c_uint64, _P, C.POINTER(VlParams),
                                     C.POINTER(PlaceParams), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("pcp_simulate_scan", C.c_int, [_P, _P, C.c_uint64, C.POINTER(FanParams), _P, C.c_uint64,
+                                    C.POINTER(C.c_uint64), _P, _P, _P, _P, _P, C.c_uint64,
+                                    C.POINTER(C.c_uint64), _P, C.POINTER(C.c_uint64)]),
+    ("pcp_simulate_scan_burst", C.c_int, [_P, _P, C.c_uint64, C.POINTER(FanParams), C.c_int,
+                                          _P]),
     ("pcp_debug_exclusive_scan", C.c_int, [_P, _P, C.c_uint64, _P]),
     ("pcp_score_poses_burst", C.c_int, [_P, _P, C.c_uint64, _P, C.POINTER(VlParams), C.c_int,
                                         C.POINTER(C.c_double)]),
@@ -904,6 +923,74 @@ class Context:
             out["cell_score"] = cs[:C_].copy()
             out["cell_owner"] = co[:C_].copy()
         return out
+
+    def simulate_scan(self, poses5, fan: FanParams, want_dense: bool = False,
+                      want_mask: bool = True, returns_cap: int | None = None,
+                      mask_cap: int | None = None) -> dict:
+        """pcp_simulate_scan: the fan of up to SCAN_MAX_POSES poses with every blocked ray
+        resolved to the terrain point it hit.  -> dict: returns (SCAN_RETURN_DTYPE, the poses'
+        segments in ray order), offsets [P + 1], n_points, hit_point / range / first_hit
+        [P, n_el, n_az] (want_dense, else None), point_mask uint64 [n_points] / seen_points [P] /
+        n_seen_any (want_mask, else None).  returns_cap None: n * n_az * n_el; mask_cap None: the
+        terrain cloud's size.  A short capacity raises PcpError(PCP_E_CAPACITY) whose `partial`
+        attribute holds the same dict (counts, offsets and dense outputs valid)."""
+        poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 5)
+        P = poses.shape[0]
+        rays = int(fan.n_az) * int(fan.n_el)
+        cap = P * rays if returns_cap is None else int(returns_cap)
+        ret = np.zeros(max(cap, 1), SCAN_RETURN_DTYPE)
+        offsets = np.zeros(P + 1, np.uint64)
+        shape = (P, fan.n_el, fan.n_az)
+        hp = np.empty(shape, np.int32) if want_dense else None
+        rg = np.empty(shape, np.float32) if want_dense else None
+        fh = np.empty(shape, np.int16) if want_dense else None
+        mcap = 0
+        if want_mask:
+            mcap = self.scan_points() if mask_cap is None else int(mask_cap)
+        mask = np.zeros(max(mcap, 1), np.uint64) if want_mask else None
+        seen = np.zeros(max(P, 1), np.uint32) if want_mask else None
+        nret, npts, nany = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        rc = self.lib.pcp_simulate_scan(
+            self.h, _ptr(poses) if P else None, P, C.byref(fan), _ptr(ret), cap, C.byref(nret),
+            _ptr(offsets), _ptr(hp), _ptr(rg), _ptr(fh), _ptr(mask), mcap, C.byref(npts),
+            _ptr(seen), C.byref(nany) if want_mask else None)
+        if rc not in (PCP_OK, PCP_E_CAPACITY):
+            self._check(rc, "pcp_simulate_scan")
+        N = npts.value
+        # (views of the call's own arrays: no second copy of a scan's tens of megabytes)
+        out = {"returns": ret[:min(nret.value, cap)], "n_returns": nret.value,
+               "offsets": offsets, "n_points": N, "hit_point": hp, "range": rg, "first_hit": fh,
+               "point_mask": mask[:min(N, mcap)] if want_mask else None,
+               "seen_points": seen[:P] if want_mask else None,
+               "n_seen_any": nany.value if want_mask else None}
+        if rc == PCP_E_CAPACITY:
+            try:
+                self._check(rc, "pcp_simulate_scan")
+            except PcpError as e:
+                e.partial = out
+                raise
+        return out
+
+    def scan_points(self) -> int:
+        """N of pcp_simulate_scan: the input point count of the cloud the terrain index was built
+        from (an n == 0 query: nothing is launched)."""
+        fan = FanParams(1, 1, -0.1, 0.1, 1.0)
+        nret, npts = C.c_uint64(), C.c_uint64()
+        off = np.zeros(1, np.uint64)
+        self._check(self.lib.pcp_simulate_scan(self.h, None, 0, C.byref(fan), None, 0,
+                                               C.byref(nret), _ptr(off), None, None, None, None,
+                                               0, C.byref(npts), None, None),
+                    "pcp_simulate_scan")
+        return npts.value
+
+    def simulate_scan_burst(self, poses5, fan: FanParams, reps: int = 20):
+        """pcp_simulate_scan_burst -> (fan kernel ms per launch, resolve phase ms per repetition)."""
+        poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 5)
+        ms = np.zeros(2, np.float64)
+        self._check(self.lib.pcp_simulate_scan_burst(self.h, _ptr(poses), poses.shape[0],
+                                                     C.byref(fan), reps, _ptr(ms)),
+                    "pcp_simulate_scan_burst")
+        return float(ms[0]), float(ms[1])
 
     def score_poses_stats(self, poses5, zx120_pose5, params: VlParams) -> dict:
         """pcp_score_poses_stats: the gather lane-loads of the query's visibility rays

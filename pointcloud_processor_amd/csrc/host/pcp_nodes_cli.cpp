@@ -7,6 +7,8 @@
 //                         MAXD OUT_TOTALS.f64 OUT_FLAGS.u8 OUT_REPORT.txt [TICKS]
 //   pcp_nodes_cli place   TERRAIN.f32 TN AUX.f32 AN CELLS.f64 NORMALS.f32 CN BBOX(6) ZXT(3) NUMC
 //                         MAXD KMAX MINSEP OUT_SELECTED.i64 OUT_TOTALS.f64 OUT_REPORT.txt
+//   pcp_nodes_cli scan    TERRAIN.f32 TN POSES(5 per sensor) NAZ NEL MAXD OUT_SCANS.bin
+//                         OUT_OFFSETS.u64 OUT_BLIND.f32 OUT_MASK.u64
 //   pcp_nodes_cli drivable IN.f32 N STEP TF(7) R1(2) R2(2) OUT.i8
 //   pcp_nodes_cli replay  TERRAIN.f32 TN CELLS.f64 NORMALS.f32 CN BBOX(6) FRAMES POINTS
 //
@@ -25,6 +27,7 @@
 
 #include "pcp_nodes.hpp"
 #include "pcp_placement.hpp"
+#include "pcp_scan_node.hpp"
 
 using namespace pcp;
 
@@ -235,6 +238,56 @@ static int cmd_place(Device &dev, char **a) {
                 "\"zx120_covered\": %d, \"total_cells\": %d}\n",
                 tick.candidates.size(), r.rounds.size(), r.zx120_total, r.zx120_covered,
                 r.total_cells);
+    return 0;
+}
+
+// the simulated scans of the given sensor poses against a terrain: every sensor's returns (24-byte
+// records, the sensors' segments one after the other), the segments' offsets, the terrain's
+// blind-spot records and the per-point sensor mask
+static int cmd_scan(Device &dev, char **a) {
+    const auto t = read_file(a[0]);
+    const size_t tn = std::strtoull(a[1], nullptr, 10);
+    const auto pv = tuple(a[2]);
+    if (pv.size() % 5 != 0) {
+        std::fprintf(stderr, "scan: POSES holds %zu numbers, not 5 per sensor\n", pv.size());
+        return 2;
+    }
+    VirtualScan::Params sp;
+    sp.n_az = std::atoi(a[3]);
+    sp.n_el = std::atoi(a[4]);
+    sp.max_distance = std::strtod(a[5], nullptr);
+    SimplifiedDualLidarOptimizer node(dev, SimplifiedDualLidarOptimizer::Params{});
+    const PointCloud2 terrain = cloud_from(t, tn, 32, "map");
+    node.terrainCallback(terrain);
+    std::vector<SimplifiedDualLidarOptimizer::LidarPosition> sensors(pv.size() / 5);
+    for (size_t i = 0; i < sensors.size(); ++i) {
+        sensors[i].x = pv[5 * i];
+        sensors[i].y = pv[5 * i + 1];
+        sensors[i].z = pv[5 * i + 2];
+        sensors[i].pitch = pv[5 * i + 3];
+        sensors[i].yaw = pv[5 * i + 4];
+    }
+    VirtualScan vs(sp);
+    const auto r = vs.scan(dev, terrain, sensors);
+    if (!r.ran) {
+        std::fprintf(stderr, "scan: %s\n", vs.lastError().c_str());
+        return 1;
+    }
+    std::vector<uint8_t> all;
+    std::vector<uint64_t> off(1, 0);
+    for (const auto &m : r.scans) {
+        if (m.point_step != 24 || m.fields.size() != 6) return 3;
+        all.insert(all.end(), m.data.begin(), m.data.end());
+        off.push_back(off.back() + m.width);
+    }
+    write_file(a[6], all.data(), all.size());
+    write_file(a[7], off.data(), off.size() * 8);
+    write_file(a[8], r.blind_spots.data.data(), r.blind_spots.data.size());
+    write_file(a[9], r.point_mask.data(), r.point_mask.size() * 8);
+    std::printf("{\"n_sensors\": %zu, \"n_returns\": %llu, \"n_points\": %llu, "
+                "\"n_seen_any\": %llu, \"n_blind\": %u}\n",
+                sensors.size(), (unsigned long long)off.back(), (unsigned long long)r.n_points,
+                (unsigned long long)r.n_seen_any, r.blind_spots.width);
     return 0;
 }
 
@@ -606,7 +659,7 @@ int main(int argc, char **argv) {
         if (!hp || std::atoi(hp) != 0) setenv("HSA_ENABLE_INTERRUPT", "0", 0);
     }
     if (argc < 2) {
-        std::fprintf(stderr, "usage: pcp_nodes_cli filter|merge|vlidar|place|area|drivable|replay ...\n");
+        std::fprintf(stderr, "usage: pcp_nodes_cli filter|merge|vlidar|place|scan|area|drivable|replay ...\n");
         return 2;
     }
     const std::string cmd = argv[1];
@@ -614,6 +667,7 @@ int main(int argc, char **argv) {
                      : cmd == "merge"  ? 7
                      : cmd == "vlidar" ? 14
                      : cmd == "place"  ? 16
+                     : cmd == "scan"   ? 10
                      : cmd == "area"   ? 10
                      : cmd == "drivable" ? 7
                      : cmd == "replay" ? 8
@@ -628,6 +682,7 @@ int main(int argc, char **argv) {
         if (cmd == "merge") return cmd_merge(dev, argv + 2);
         if (cmd == "vlidar") return cmd_vlidar(dev, argv + 2, argc - 2);
         if (cmd == "place") return cmd_place(dev, argv + 2);
+        if (cmd == "scan") return cmd_scan(dev, argv + 2);
         if (cmd == "area") return cmd_area(dev, argv + 2);
         if (cmd == "drivable") return cmd_drivable(dev, argv + 2);
         return cmd_replay(dev, argv + 2);

@@ -940,6 +940,7 @@ int set_terrain_from(pcp_ctx *ctx, const pcp_cloud_view *terrain, const unsigned
     rc = build_index(ctx, ctx->terrain, *terrain, kRayRadius, true, ctx->fan_batch == 2,
                      raw ? &raw : nullptr);
     ctx->terrain_queries = 0;
+    ctx->terrain_index_n = terrain->n;
     prof_resolve(ctx);
     return rc;
 }

@@ -231,6 +231,8 @@ struct pcp_ctx {
     // virtual_lidar state
     pcp::GridIndex terrain;      // raycast index (r_q = 0.056)
     uint64_t terrain_cloud_n = 0;  // current terrain cloud size (stale-tree semantics)
+    uint64_t terrain_index_n = 0;  // input count of the cloud the current terrain index was built
+                                   // from (an empty pcp_set_terrain keeps index and count)
     pcp::GridIndex aux;          // zx120 cloud index (r_q = 0.24)
     uint64_t aux_cloud_n = 0;
     uint64_t n_cells = 0;
@@ -323,6 +325,11 @@ struct pcp_ctx {
     // pcp_score_poses leaves and expects them)
     pcp::DevBuf place_d;
     pcp::PinnedBuf place_host;
+    // pcp_simulate_scan (pcp_scan.hip): wave bases, offsets, records, dense images, point mask and
+    // counts, and the pinned landing of its downloads (its own: the fan's buffers stay as
+    // pcp_raycast_fan leaves and expects them)
+    pcp::DevBuf vscan_d;
+    pcp::PinnedBuf vscan_host;
     pcp::PinnedBuf res_host;                 // pinned landing of the filter chain's sizes
     pcp::PinnedBuf fm_res_host;              // pcp_filter_merge's result sizes, stored by its
                                              // kernels themselves (fixed: a graph holds it)
@@ -507,6 +514,11 @@ struct FanEnq {
     uint32_t rays = 0;
     size_t stats_bytes = 0;
     unsigned long long *stats_d = nullptr;
+    // the march's per-wave partials {blocked, units} left on the device, pose-major (slot =
+    // p * waves + ray / 64), and the step table's length (pcp_simulate_scan resolves from them)
+    const uint2 *wave_part = nullptr;
+    uint32_t waves = 0;
+    int K = 0;
 };
 // burst > 0: the plain kernel `burst` times back-to-back between two events, the average
 // launch time to *burst_ms (pcp_raycast_fan_burst).  host_out: k_fan_reduce stores the

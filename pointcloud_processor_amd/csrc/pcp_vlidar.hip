@@ -2395,6 +2395,9 @@ int fan_enqueue(pcp_ctx *ctx, const double *poses5, uint64_t n, const pcp_fan_pa
     o.fh_d = fh_d;
     o.rays = rays;
     o.stats_bytes = stats_bytes;
+    o.wave_part = a.wave_part;
+    o.waves = waves;
+    o.K = K;
     return PCP_OK;
 }
 }  // namespace pcp
