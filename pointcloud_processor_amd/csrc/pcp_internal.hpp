@@ -374,9 +374,15 @@ struct pcp_ctx {
     double fan_elmin = 0.0, fan_elmax = 0.0;
     double steps_end = -1e300;               // cached step table
     int steps_K = 0;
+    double steps_first = 0.0, steps_last = 0.0;   // its first and last entries (steps_K > 0)
+    std::vector<double> fan_se_h;            // host copy of the cached table's sin(elevation)
     int num_cus = 256;                       // multiprocessors of the device
     int fan_batch = 0;                       // fan kernel variant (PCP_FAN_BATCH), A/B only
     int fan_npw = 8;                         // poses per wave of the fan kernel (PCP_FAN_NPW)
+    bool fan_cull = true;                    // launch only the rings that can reach the terrain,
+                                             // leave a pose's dead rings early (PCP_FAN_CULL)
+    bool fan_horizon_first = true;           // dispatch the live rings nearest the horizon first
+                                             // (PCP_FAN_ORDER; 0: in ring order)
     bool fan_host_out = true;                // k_fan_reduce stores into the pinned landing
                                              // block, no D2H copy (PCP_FAN_HOST_OUT)
     int fm_fast = 2;                         // pcp_filter_merge's voxel chain (PCP_FM_FAST): 2 the
@@ -514,10 +520,12 @@ struct FanEnq {
     uint32_t rays = 0;
     size_t stats_bytes = 0;
     unsigned long long *stats_d = nullptr;
-    // the march's per-wave partials {blocked, units} left on the device, pose-major (slot =
-    // p * waves + ray / 64), and the step table's length (pcp_simulate_scan resolves from them)
+    // the march's per-wave partials {blocked, units} left on the device, pose-major, of the
+    // live waves only (slot = p * live_waves + ray / 64 - wave0; the waves outside [wave0, wave0
+    // + live_waves) of a pose's `waves` were culled: no ray of theirs is blocked), and the step
+    // table's length (pcp_simulate_scan resolves from them)
     const uint2 *wave_part = nullptr;
-    uint32_t waves = 0;
+    uint32_t waves = 0, wave0 = 0, live_waves = 0;
     int K = 0;
 };
 // burst > 0: the plain kernel `burst` times back-to-back between two events, the average

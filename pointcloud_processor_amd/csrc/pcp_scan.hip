@@ -51,13 +51,18 @@ struct ResolveArgs {
 // + ... + blocked[p - 1] in 64 bits (P <= 64: one thread, fixed order), the mask counts' slots
 // zeroed.  head = {offsets u64[P + 1], pad, slots u32[kSlots][kSlotWords]}
 __global__ void __launch_bounds__(kST)
-k_scan_prepare(const uint2 *__restrict__ part, uint32_t nW, uint32_t *__restrict__ cnt,
+k_scan_prepare(const uint2 *__restrict__ part, uint32_t nW, uint32_t waves, uint32_t w0,
+               uint32_t lw, uint32_t *__restrict__ cnt,
                unsigned long long *__restrict__ mask, unsigned long long n_mask,
                const uint32_t *__restrict__ blocked, uint32_t P,
                unsigned long long *__restrict__ head, uint32_t *__restrict__ slots) {
     const unsigned long long t0 = (unsigned long long)blockIdx.x * kST + threadIdx.x;
     const unsigned long long stride = (unsigned long long)gridDim.x * kST;
-    for (unsigned long long i = t0; i < nW; i += stride) cnt[i] = part[i].x;
+    // part holds the live waves [w0, w0 + lw) of each pose's `waves`; a culled wave has no return
+    for (unsigned long long i = t0; i < nW; i += stride) {
+        const uint32_t p = (uint32_t)i / waves, w = (uint32_t)i - p * waves - w0;
+        cnt[i] = w < lw ? part[(size_t)p * lw + w].x : 0u;
+    }
     // (the mask starts 16-byte aligned: two entries per store, then the odd last one)
     ulonglong2 *m2 = reinterpret_cast<ulonglong2 *>(mask);
     const unsigned long long n2 = n_mask >> 1;
@@ -288,7 +293,8 @@ int resolve_enqueue(pcp_ctx *ctx, const ScanPlan &s, const pcp_fan_params *fan, 
     {
         const uint64_t work = std::max<uint64_t>(nW, mask ? s.N / 2 : 0);
         const unsigned g = (unsigned)std::min<uint64_t>((work + kST - 1) / kST + 1, 2048);
-        hipLaunchKernelGGL(k_scan_prepare, dim3(g), dim3(kST), 0, st, o.wave_part, nW, cnt, mask,
+        hipLaunchKernelGGL(k_scan_prepare, dim3(g), dim3(kST), 0, st, o.wave_part, nW, s.waves,
+                           o.wave0, o.live_waves, cnt, mask,
                            (unsigned long long)(mask ? s.N : 0), (const uint32_t *)o.blocked_d,
                            s.P, offsets, slots);
         PCP_CHECK_LAUNCH(ctx);

@@ -15,6 +15,7 @@
 #include <hip/hip_ext.h>
 
 #include "pcp_crmath.h"
+#include "pcp_fan_cull.hpp"
 #include "pcp_internal.hpp"
 #include "pcp_stencil.hpp"
 
@@ -1326,7 +1327,8 @@ k_cand_compact(const double *__restrict__ lat, int L, double *__restrict__ out, 
 struct FanArgs {
     GridView g;
     const double *ca, *sa, *ce, *se;
-    const double *pose;    // P x 8: x, y, z, pitch, yaw, cos(yaw), sin(yaw), pad
+    const double *pose;    // P x 8: x, y, z, pitch, yaw, cos(yaw), sin(yaw), and as two uint32
+                           // the pose's live rings [j0, j1) (pcp_fan_cull.hpp)
     const double *steps;
     int K;
     int n_az;
@@ -1336,8 +1338,13 @@ struct FanArgs {
     float r2, rexit;
     int present;
     int16_t *first_hit;
+    // the launch covers the waves [w0, w0 + lw) of each pose: the others hold only rays of rings
+    // that reach the terrain from no pose of the call (Skip 4; w0 = 0, lw = waves: no culling).
+    // rev: ray block b of the launch is wave w0 + lw - 1 - b, not w0 + b
+    uint32_t w0, lw;
+    int rev;
     // per-wave partials {blocked, units}, one 8-byte store per wave (no atomics), pose-major:
-    // slot = p * waves + w.  Every wave of a pose runs on one XCD (the XCD-chunk kernels: XCD
+    // slot = p * lw + w - w0.  Every wave of a pose runs on one XCD (the XCD-chunk kernels: XCD
     // p / (P / 8); the interleaved ones: XCD p % 8), so that XCD's L2 fills the pose's lines,
     // and k_fan_reduce reads each pose's partials as one contiguous run
     uint2 *wave_part;
@@ -1378,12 +1385,22 @@ __device__ __forceinline__ void fan_body(const FanArgs &a, uint32_t p0, uint32_t
     // SL: the step table in LDS (the launcher guarantees K <= kStepLds): one load per 64
     // entries per workgroup, then a candidate's step is an LDS read instead of a gather through
     // the texture path
+    // and the wave's NPW pose rows (contiguous: one coalesced load) behind the same barrier: a
+    // pose's values and its live rings are then LDS broadcasts, not a round trip through
+    // vector memory at the top of every pose
     __shared__ double s_steps[SL ? kStepLds : 1];
+    __shared__ double s_pose[SL ? 8 * NPW : 1];
     if (SL) {
         for (int q = threadIdx.x; q < a.K; q += BS) s_steps[q] = a.steps[q];
+        for (int q = threadIdx.x; q < 8 * NPW; q += BS) s_pose[q] = a.pose[8 * (size_t)p0 + q];
         __syncthreads();
     }
     const double *steps = SL ? s_steps : a.steps;
+    // UE: the wave's ring as a scalar, tested against each pose's live rings below
+    uint32_t ju = 0;
+    if (UE)
+        ju = (uint32_t)__builtin_amdgcn_readfirstlane(
+            (int)((rblock * BS + (threadIdx.x & ~63u)) / (uint32_t)a.n_az));
     if (active && a.present) {
         // UE (n_az % 64 == 0): the wave's ring is uniform, a scalar division of its first ray
         const uint32_t j = UE ? (rblock * BS + (threadIdx.x & ~63u)) / (uint32_t)a.n_az
@@ -1402,8 +1419,19 @@ __device__ __forceinline__ void fan_body(const FanArgs &a, uint32_t p0, uint32_t
     if (MODE == FAN_STAMPS) t0 = __builtin_amdgcn_s_memtime();
     int hit = -1;
     uint32_t cnt[4] = {0, 0, 0, 0};   // [3]: PCP_WALK_CENSUS builds only
-    if (active && a.present) {
-        const double *P = a.pose + 8 * (size_t)p;
+    // Skip 4, per pose: a ring outside the pose's live interval has every sample of every ray
+    // outside the clip box -- no rotation, no clip, no reductions (a uniform test: the ring
+    // and the pose's interval are scalars)
+    const double *P = SL ? s_pose + 8 * q : a.pose + 8 * (size_t)p;
+    bool dead = false;
+    if (UE) {
+        const uint2 lr = *reinterpret_cast<const uint2 *>(P + 7);
+        const uint32_t j0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)lr.x);
+        const uint32_t j1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)lr.y);
+        dead = ju < j0 || ju >= j1;
+        if (MODE == FAN_STAMPS && dead) t1 = t0;
+    }
+    if (!dead && active && a.present) {
         const double cy = P[5], sy = P[6];
         const double dx = cy * lx - sy * ly;
         const double dy = sy * lx + cy * ly;
@@ -1420,11 +1448,16 @@ __device__ __forceinline__ void fan_body(const FanArgs &a, uint32_t p0, uint32_t
         t2 = __builtin_amdgcn_s_memtime();
     }
     if (active && a.first_hit) a.first_hit[(size_t)p * a.rays + ray] = (int16_t)hit;
-    const uint64_t bal = __ballot(active && hit >= 0);
-    uint32_t u = active ? (hit >= 0 ? (uint32_t)hit + 1u : (uint32_t)a.K) : 0u;
-    u = wave_sum_u32(u);
+    uint2 part;
+    if (UE && dead) {   // (UE: every wave is full)
+        part = make_uint2(0u, 64u * (uint32_t)a.K);
+    } else {
+        const uint64_t bal = __ballot(active && hit >= 0);
+        uint32_t u = active ? (hit >= 0 ? (uint32_t)hit + 1u : (uint32_t)a.K) : 0u;
+        part = make_uint2((uint32_t)__popcll(bal), wave_sum_u32(u));
+    }
     if ((threadIdx.x & 63) == 0 && wid < a.waves) {
-        a.wave_part[(size_t)p * a.waves + wid] = make_uint2((uint32_t)__popcll(bal), u);
+        a.wave_part[(size_t)p * a.lw + (wid - a.w0)] = part;
     }
     if (MODE == FAN_STATS) {   // per-wave slots [4][P * waves], summed by k_sum_u64
         const size_t nw = (size_t)a.P * a.waves;
@@ -1456,20 +1489,24 @@ __device__ __forceinline__ void fan_body(const FanArgs &a, uint32_t p0, uint32_t
 template <int MODE, int BS = 64, bool ZB = true, int W = 7, int FN = 0, bool UE = false>
 __global__ void __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(W, W)))
 k_raycast_fan(FanArgs a, uint32_t P) {
-    fan_body<MODE, BS, ZB, FN, UE>(a, blockIdx.x % P, blockIdx.x / P);
+    fan_body<MODE, BS, ZB, FN, UE>(a, blockIdx.x % P, a.w0 + blockIdx.x / P);
 }
 
 // A/B: XCD-chunked placement (P % 8 == 0): workgroup b runs on XCD b % 8, which takes the
 // contiguous pose chunk [x P/8, (x + 1) P/8) -- neighbouring candidate poses, overlapping fans
 // -- interleaved inside the XCD as above
 // NPW > 1: each wave marches its rays for NPW consecutive poses of the chunk (one direction-
-// table load for all of them); P % (8 NPW) == 0, grid = waves * P / NPW
+// table load for all of them); P % (8 NPW) == 0, grid = lw * P / NPW (the live waves, Skip 4).
+// a.rev: the launch's last wave first.  Workgroups are dispatched in index order and the rings
+// just below the horizon march 2-3 times as long as the steep ones: dispatched last they would
+// be the launch's tail
 template <int MODE, int BS = 64, bool ZB = true, int W = 8, int FN = 1, bool UE = true, int NPW = 1>
 __global__ void __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(W, W)))
 k_raycast_fan_xcd(FanArgs a, uint32_t P) {
     const uint32_t pc = P >> 3, gpc = pc / NPW, j = blockIdx.x >> 3;
+    const uint32_t b = j / gpc;
     fan_body<MODE, BS, ZB, FN, UE, NPW, true>(a, (blockIdx.x & 7u) * pc + (j % gpc) * NPW,
-                                             j / gpc);
+                                             a.w0 + (a.rev ? a.lw - 1u - b : b));
 }
 
 // A/B: pose-major 2-D grid (blockIdx.y = pose), BS-thread workgroups
@@ -1498,12 +1535,21 @@ k_sum_u64(const unsigned long long *__restrict__ in, size_t n, unsigned long lon
 }
 
 // per-pose sums of the per-wave partials: one block per pose, fixed order (integer sums:
-// exact and deterministic)
+// exact and deterministic).  waves: the live waves the launch covered (0: none was launched);
+// the culled rays' share (Skip 4) is closed-form: none blocked, K units each = units_culled per
+// pose.  fh (nullable): their first hits, rays [0, r_lo) and [r_hi, rays) of the pose, are -1.
 __global__ void __launch_bounds__(kT)
 k_fan_reduce(const uint2 *__restrict__ part, uint32_t waves,
              uint32_t *__restrict__ blocked, unsigned long long *__restrict__ units,
-             unsigned long long *__restrict__ keys, uint32_t lo, uint32_t Pall) {
+             unsigned long long *__restrict__ keys, uint32_t lo, uint32_t Pall,
+             unsigned long long units_culled, int16_t *__restrict__ fh, uint32_t rays,
+             uint32_t r_lo, uint32_t r_hi) {
     const uint32_t p = blockIdx.x;
+    if (fh) {
+        int16_t *row = fh + (size_t)p * rays;
+        for (uint32_t r = threadIdx.x; r < r_lo; r += kT) row[r] = (int16_t)-1;
+        for (uint32_t r = r_hi + threadIdx.x; r < rays; r += kT) row[r] = (int16_t)-1;
+    }
     if (keys)   // (FanEnq.keys) the other ranks' slots and the health word: the MIN identity
         for (uint32_t i = p * kT + threadIdx.x; i <= Pall; i += gridDim.x * kT)
             if (i < lo || i - lo >= gridDim.x) keys[i] = ~0ull;
@@ -1529,7 +1575,7 @@ k_fan_reduce(const uint2 *__restrict__ part, uint32_t waves,
     __syncthreads();
     if (threadIdx.x == 0) {
         const uint32_t bs = sb[0] + sb[1] + sb[2] + sb[3];
-        const unsigned long long us = su[0] + su[1] + su[2] + su[3];
+        const unsigned long long us = su[0] + su[1] + su[2] + su[3] + units_culled;
         blocked[p] = bs;
         units[p] = us;
         if (keys) {
@@ -1545,9 +1591,9 @@ k_fan_reduce(const uint2 *__restrict__ part, uint32_t waves,
 
 // the production fan kernel (fine tiled windows, uniform rings, XCD pose chunks) with NPW poses
 // per wave; ev0/ev1 non-null: hipExtLaunchKernelGGL's start/stop events
-static void launch_xcd(int npw, const FanArgs &a, uint32_t P, uint32_t waves, hipStream_t st,
+static void launch_xcd(int npw, const FanArgs &a, uint32_t P, hipStream_t st,
                        hipEvent_t ev0, hipEvent_t ev1) {
-    const dim3 g(waves * P / (uint32_t)npw);
+    const dim3 g(a.lw * P / (uint32_t)npw);
 #define PCP_XCD(N)                                                                             \
     do {                                                                                       \
         if (a.g.ftile == 2)                                                                    \
@@ -1734,6 +1780,8 @@ static int ensure_steps(pcp_ctx *ctx, double end, int *K) {
     }
     ctx->steps_end = end;
     ctx->steps_K = (int)s.size();
+    ctx->steps_first = s.empty() ? 0.0 : s.front();
+    ctx->steps_last = s.empty() ? 0.0 : s.back();
     *K = ctx->steps_K;
     return PCP_OK;
 }
@@ -2194,6 +2242,7 @@ int fan_enqueue(pcp_ctx *ctx, const double *poses5, uint64_t n, const pcp_fan_pa
         PCP_HIP(ctx, hipMemcpyAsync(ctx->fan_tab.p, t.data(), tab_doubles * sizeof(double),
                                     hipMemcpyHostToDevice, st));
         PCP_HIP(ctx, hipStreamSynchronize(st));
+        ctx->fan_se_h.assign(t.begin() + 2 * (size_t)fan->n_az + fan->n_el, t.end());
         ctx->fan_naz = fan->n_az;
         ctx->fan_nel = fan->n_el;
         ctx->fan_elmin = fan->el_min;
@@ -2220,6 +2269,31 @@ int fan_enqueue(pcp_ctx *ctx, const double *poses5, uint64_t n, const pcp_fan_pa
     }
     PCP_HIP(ctx, ctx->poses_d.ensure((size_t)P * 8 * sizeof(double)));
     const uint32_t waves = (rays + 63) / 64;
+    // Skip 4: each pose's live rings [j0, j1) into its eighth slot (the UE
+    // kernels leave a pose's dead rings at once), and the waves that hold a live ring of some
+    // pose: only those are launched.  The diagnostic launches and the A/B variant with
+    // 128-thread blocks keep the full grid.
+    uint32_t w0 = 0, lw = waves;
+    {
+        uint32_t *lr = reinterpret_cast<uint32_t *>(pose8 + 7);
+        const bool rule = ctx->fan_cull && ctx->terrain.present && K > 0;
+        if (rule) {
+            const GridView tv = ctx->terrain.view();
+            const FanLive L = fan_live_rings((double)tv.fb[4], (double)tv.fb[5], pose8 + 2,
+                                             (uint64_t)P, 8, ctx->fan_se_h.data(), fan->n_el,
+                                             ctx->steps_first, ctx->steps_last, lr, 16);
+            if (!stats && !stamps && ctx->fan_batch != 1) {
+                const FanWaves W = fan_live_waves(L, fan->n_az, fan->n_el);
+                w0 = W.w0;
+                lw = W.w1 - W.w0;
+            }
+        } else {
+            for (int k = 0; k < P; ++k) {
+                lr[16 * (size_t)k] = 0u;
+                lr[16 * (size_t)k + 1] = (uint32_t)fan->n_el;
+            }
+        }
+    }
     if ((uint64_t)waves * (uint64_t)P >= (1ull << 31))
         return set_err(ctx, PCP_E_INVALID, "pcp_raycast_fan: %d poses x %u rays exceed one launch",
                        P, rays);
@@ -2264,13 +2338,22 @@ int fan_enqueue(pcp_ctx *ctx, const double *poses5, uint64_t n, const pcp_fan_pa
     a.uniform_el = (fan->n_az % 64 == 0) ? 1 : 0;
     a.rays = rays;
     a.waves = waves;
+    a.w0 = w0;
+    a.lw = lw;
+    // the live rings nearest the horizon first: they are the far end of the interval when the
+    // near end is the steeper one
+    a.rev = (ctx->fan_horizon_first && lw > 0 && lw < waves &&
+             std::fabs(ctx->fan_se_h[std::min<size_t>((size_t)(w0 + lw - 1) * 64 / (size_t)fan->n_az,
+                                                      (size_t)fan->n_el - 1)]) <
+                 std::fabs(ctx->fan_se_h[(size_t)w0 * 64 / (size_t)fan->n_az]))
+                ? 1 : 0;
     a.P = (uint32_t)P;
     a.r2 = (float)(kRayRadius * kRayRadius);
     a.rexit = exit_dist(a.r2);
     a.first_hit = fh_d;
     a.wave_part = ctx->out_b.as<uint2>();
     a.stats = ctx->stats_d.as<unsigned long long>();
-    const dim3 grid1(waves * (uint32_t)P);           // 64-thread blocks, pose-interleaved
+    const dim3 grid1(lw * (uint32_t)P);   // 64-thread blocks, pose-interleaved (live waves)
     // the fine-window kernels (28 VGPRs, 8 waves per SIMD), the ring index a
     // scalar when n_az % 64 == 0 (UE); the coarse layouts' kernel otherwise
     const bool fine = a.g.frec != nullptr, ue = a.uniform_el != 0, tile = a.g.ftile != 0;
@@ -2337,6 +2420,10 @@ int fan_enqueue(pcp_ctx *ctx, const double *poses5, uint64_t n, const pcp_fan_pa
         PCP_FAN_LAUNCH(FAN_STAMPS);
         PCP_CHECK_LAUNCH(ctx);
         o.stats_d = a.stats;
+    } else if (lw == 0) {
+        // every ring is dead for every pose: no march (a zero-sized grid is not submitted);
+        // k_fan_reduce below gives the closed-form result
+        if (burst_ms) *burst_ms = 0.0;
     } else if (burst > 0) {
         // the production kernel `burst` times back-to-back between two events: the queue never
         // idles between the events, so the interval is the launches themselves (the per-call
@@ -2347,7 +2434,7 @@ int fan_enqueue(pcp_ctx *ctx, const double *poses5, uint64_t n, const pcp_fan_pa
         PCP_HIP(ctx, hipEventRecord(e0, st));
         for (int r = 0; r < burst; ++r) {
             if (fine && tile && ue && P % (8 * npw) == 0 && K <= kStepLds)
-                launch_xcd(npw, a, (uint32_t)P, waves, st, nullptr, nullptr);
+                launch_xcd(npw, a, (uint32_t)P, st, nullptr, nullptr);
             else if (fine && ue && P % 8 == 0 && K <= kStepLds)
                 hipLaunchKernelGGL((k_raycast_fan_xcd<FAN_PLAIN>), grid1, dim3(64), 0, st, a,
                                    (uint32_t)P);
@@ -2374,7 +2461,7 @@ int fan_enqueue(pcp_ctx *ctx, const double *poses5, uint64_t n, const pcp_fan_pa
             // XCD-chunked placement (each XCD's L2 serves neighbouring poses' overlapping fans):
             // 0.61 vs 0.63 ms on C2
             if (fine && tile && ue && P % (8 * npw) == 0 && K <= kStepLds)
-                launch_xcd(npw, a, (uint32_t)P, waves, st, kt.a, kt.b);
+                launch_xcd(npw, a, (uint32_t)P, st, kt.a, kt.b);
             else if (fine && ue && P % 8 == 0 && K <= kStepLds)
                 hipExtLaunchKernelGGL((k_raycast_fan_xcd<FAN_PLAIN>), grid1, dim3(64), 0, st, kt.a,
                                       kt.b, 0, a, (uint32_t)P);
@@ -2386,9 +2473,13 @@ int fan_enqueue(pcp_ctx *ctx, const double *poses5, uint64_t n, const pcp_fan_pa
     }
 #undef PCP_FAN_LAUNCH
 #undef PCP_FAN_LAUNCH_T
+    // the rays the launch covered: [r_lo, r_hi) of each pose
+    const uint32_t r_lo = w0 * 64u, r_hi = std::min<uint64_t>((uint64_t)(w0 + lw) * 64u, rays);
     hipLaunchKernelGGL(k_fan_reduce, dim3(P), dim3(kT), 0, st,
-                       (const uint2 *)a.wave_part, waves, blocked_d,
-                       units_d, o.keys, o.keys_lo, o.keys_P);
+                       (const uint2 *)a.wave_part, lw, blocked_d,
+                       units_d, o.keys, o.keys_lo, o.keys_P,
+                       (unsigned long long)(rays - (r_hi - r_lo)) * (unsigned long long)K, fh_d,
+                       rays, r_lo, r_hi);
     PCP_CHECK_LAUNCH(ctx);
     o.blocked_d = host_out ? nullptr : blocked_d;
     o.units_d = host_out ? nullptr : units_d;
@@ -2397,6 +2488,8 @@ int fan_enqueue(pcp_ctx *ctx, const double *poses5, uint64_t n, const pcp_fan_pa
     o.stats_bytes = stats_bytes;
     o.wave_part = a.wave_part;
     o.waves = waves;
+    o.wave0 = w0;
+    o.live_waves = lw;
     o.K = K;
     return PCP_OK;
 }
