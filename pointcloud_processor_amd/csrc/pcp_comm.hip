@@ -87,7 +87,7 @@ static int fan_allreduce_enqueue(pcp_ctx *ctx, const double *poses5, uint64_t n,
         o.keys = keys;
         o.keys_lo = (uint32_t)lo;
         o.keys_P = P;
-        if (int rc = fan_enqueue(ctx, poses5, n, fan, false, false, false, o)) return rc;
+        if (int rc = fan_enqueue(ctx, poses5, n, fan, o)) return rc;
         *units_out = o.units_d;
     } else {   // no poses here: the identity everywhere
         launch_fan_keys(st, nullptr, (uint32_t)lo, 0u, P + 1, keys);

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "pcp_abi.h"
+#include "pcp_fan_pick.hpp"
 
 namespace pcp {
 struct CopyPool;
@@ -528,13 +529,22 @@ struct FanEnq {
     uint32_t waves = 0, wave0 = 0, live_waves = 0;
     int K = 0;
 };
-// burst > 0: the plain kernel `burst` times back-to-back between two events, the average
-// launch time to *burst_ms (pcp_raycast_fan_burst).  host_out: k_fan_reduce stores the
-// per-pose {units u64[n], blocked u32[n]} straight into the pinned landing block
-// (ctx->fan_host past the staged poses) instead of device memory; o.*_d stay null.
+struct FanOpts {
+    bool want_fh = false;         // first hits [n][rays] to o.fh_d
+    // burst > 0: the production kernel `burst` times back-to-back between two events, the
+    // average launch time to *burst_ms (pcp_raycast_fan_burst)
+    int burst = 0;
+    double *burst_ms = nullptr;
+    // k_fan_reduce stores the per-pose {units u64[n], blocked u32[n]} straight into the pinned
+    // landing block (ctx->fan_host past the staged poses) instead of device memory; o.*_d stay
+    // null
+    bool host_out = false;
+};
+// mode: the plain query, or a diagnostic launch -- Stats: the march's four counters summed to
+// o.stats_d[0..3]; Stamps: four clock stamps per (pose, wave) at o.stats_d, o.stats_bytes long.
+// Which kernel runs on which grid is fan_pick()'s answer (pcp_fan_pick.hpp).
 int fan_enqueue(pcp_ctx *ctx, const double *poses5, uint64_t n, const pcp_fan_params *fan,
-                bool want_fh, bool stats, bool stamps, FanEnq &o, int burst = 0,
-                double *burst_ms = nullptr, bool host_out = false);
+                FanEnq &o, FanMode mode = FanMode::Plain, const FanOpts &opt = FanOpts{});
 
 // runOptimization's scoring up to the per-pose sums, enqueued on ctx->stream (pcp_vlidar.hip)
 struct ScoreEnq {

@@ -301,7 +301,7 @@ int pcp_multi_raycast_fan(pcp_multi *m, const double *poses5, uint64_t n,
     int erc = for_ranks(m, [&](int r) -> int {
         pcp_ctx *c = m->ctx[r];
         if (cnt[r])
-            if (int rc = fan_enqueue(c, poses5 + 5 * lo[r], cnt[r], fan, false, false, false, o[r]))
+            if (int rc = fan_enqueue(c, poses5 + 5 * lo[r], cnt[r], fan, o[r]))
                 return rc;
         PCP_HIP(c, hipSetDevice(c->device));
         launch_fan_keys(c->stream, o[r].blocked_d, (uint32_t)lo[r], (uint32_t)cnt[r], P,

@@ -379,7 +379,8 @@ extern "C" int pcp_simulate_scan(pcp_ctx *ctx, const double *poses5, uint64_t n,
     // the production fan query: first hits, per-wave partials and per-pose blocked counts stay
     // on the device (a step table past PCP_MAX_STEPS is refused in there, before any launch)
     FanEnq o;
-    if (int rc = fan_enqueue(ctx, poses5, n, fan, true, false, false, o)) return rc;
+    if (int rc = fan_enqueue(ctx, poses5, n, fan, o, FanMode::Plain, FanOpts{/*want_fh=*/true}))
+        return rc;
     hipStream_t st = ctx->stream;
     const uint32_t P = (uint32_t)n;
     const bool want_mask = point_mask || seen_points || n_seen_any;
@@ -462,7 +463,9 @@ extern "C" int pcp_simulate_scan_burst(pcp_ctx *ctx, const double *poses5, uint6
     // the fan kernel `reps` times between two events (first hits and partials written by each),
     // then the resolve phase `reps` times between two events
     FanEnq o;
-    if (int rc = fan_enqueue(ctx, poses5, n, fan, true, false, false, o, reps, &ms[0])) return rc;
+    if (int rc = fan_enqueue(ctx, poses5, n, fan, o, FanMode::Plain,
+                             FanOpts{/*want_fh=*/true, /*burst=*/reps, /*burst_ms=*/&ms[0]}))
+        return rc;
     hipStream_t st = ctx->stream;
     const uint64_t N = ctx->terrain.present ? ctx->terrain_index_n : 0;
     const ScanPlan s = make_plan((uint32_t)n, o.rays, o.waves, N, (uint64_t)n * o.rays, false,

@@ -22,7 +22,6 @@
 namespace pcp {
 
 constexpr int kT = 256;
-constexpr int kStepLds = 256;   // step tables up to this long are read from LDS (fan, cells)
 #ifndef PCP_CELL_PROBES
 // z-band probes issued per round in the cell-scoring march (build knob; 4 measured 130 vs 132
 // us per 256-pose k_score_cells: that march is not probe-latency bound)
@@ -1353,7 +1352,8 @@ struct FanArgs {
                                    // MODE 2: per-wave s_memtime stamps [P*waves][4]
 };
 
-enum { FAN_PLAIN = 0, FAN_STATS = 1, FAN_STAMPS = 2 };
+enum { FAN_PLAIN = (int)FanMode::Plain, FAN_STATS = (int)FanMode::Stats,
+       FAN_STAMPS = (int)FanMode::Stamps };
 
 // sum over the 64 lanes (all active): rotate-adds inside each 16-lane row (DPP row_ror 8, 4,
 // 2, 1), then the four row sums by readlane -- no LDS crossbar round trips
@@ -1509,10 +1509,10 @@ k_raycast_fan_xcd(FanArgs a, uint32_t P) {
                                              a.w0 + (a.rev ? a.lw - 1u - b : b));
 }
 
-// A/B: pose-major 2-D grid (blockIdx.y = pose), BS-thread workgroups
+// A/B: pose-major 2-D grid (blockIdx.y = pose), BS-thread workgroups (P: unused, fan_launch's)
 template <int BS, bool ZB>
 __global__ void __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(7, 7)))
-k_raycast_fan_pm(FanArgs a) {
+k_raycast_fan_pm(FanArgs a, uint32_t) {
     fan_body<FAN_PLAIN, BS, ZB>(a, blockIdx.y, blockIdx.x);
 }
 
@@ -1589,29 +1589,44 @@ k_fan_reduce(const uint2 *__restrict__ part, uint32_t waves,
     }
 }
 
-// the production fan kernel (fine tiled windows, uniform rings, XCD pose chunks) with NPW poses
-// per wave; ev0/ev1 non-null: hipExtLaunchKernelGGL's start/stop events
-static void launch_xcd(int npw, const FanArgs &a, uint32_t P, hipStream_t st,
-                       hipEvent_t ev0, hipEvent_t ev1) {
-    const dim3 g(a.lw * P / (uint32_t)npw);
-#define PCP_XCD(N)                                                                             \
-    do {                                                                                       \
-        if (a.g.ftile == 2)                                                                    \
-            hipExtLaunchKernelGGL((k_raycast_fan_xcd<FAN_PLAIN, 64, true, 8, 8, true, N>), g,   \
-                                  dim3(64), 0, st, ev0, ev1, 0, a, P);                         \
-        else                                                                                   \
-            hipExtLaunchKernelGGL((k_raycast_fan_xcd<FAN_PLAIN, 64, true, 8, 4, true, N>), g,   \
-                                  dim3(64), 0, st, ev0, ev1, 0, a, P);                         \
-    } while (0)
-    switch (npw) {
-    case 2: PCP_XCD(2); break;
-    case 4: PCP_XCD(4); break;
-    case 8: PCP_XCD(8); break;
-    case 16: PCP_XCD(16); break;
-    case 32: PCP_XCD(32); break;
-    default: PCP_XCD(1); break;
+// Every instantiated fan kernel, by what fan_pick() (pcp_fan_pick.hpp) answers (the fine-window
+// kernels: DESIGN.md §5, 28 VGPRs, 8 waves per SIMD; the coarse layouts' kernel has no UE form)
+using FanKernel = void (*)(FanArgs, uint32_t);
+template <int M, int FN, bool UE>
+constexpr FanKernel kFine = k_raycast_fan<M, 64, true, 8, FN, UE>;
+struct FanRows { FanKernel k[4][2]; };
+template <int M>
+constexpr FanRows kRows = {{{k_raycast_fan<M>}, {kFine<M, 1, false>, kFine<M, 1, true>},
+                            {kFine<M, 4, false>, kFine<M, 4, true>},
+                            {kFine<M, 8, false>, kFine<M, 8, true>}}};
+// k_raycast_fan by [MODE].k[FN 0 / 1 / 4 / 8][UE]
+constexpr FanRows kFanInterleaved[3] = {kRows<FAN_PLAIN>, kRows<FAN_STATS>, kRows<FAN_STAMPS>};
+// k_raycast_fan_xcd by [FN 1 / 4 / 8][log2 NPW]: several poses per wave over the tiled copies
+template <int FN, int NPW>
+constexpr FanKernel kXcd = k_raycast_fan_xcd<FAN_PLAIN, 64, true, 8, FN, true, NPW>;
+constexpr FanKernel kFanXcd[3][6] = {
+    {kXcd<1, 1>},   // (the untiled copy: one pose per wave only)
+    {kXcd<4, 1>, kXcd<4, 2>, kXcd<4, 4>, kXcd<4, 8>, kXcd<4, 16>, kXcd<4, 32>},
+    {kXcd<8, 1>, kXcd<8, 2>, kXcd<8, 4>, kXcd<8, 8>, kXcd<8, 16>, kXcd<8, 32>}};
+
+// The one fan launch, and its error.  ev0 / ev1: hipExtLaunchKernelGGL's start / stop events
+// (null: none).  A pick without an instantiated kernel is an error.
+static hipError_t fan_launch(const FanPick &k, FanGrid g, hipStream_t st, hipEvent_t ev0,
+                             hipEvent_t ev1, const FanArgs &a, uint32_t P) {
+    const int fn = k.FN == 8 ? 3 : k.FN == 4 ? 2 : k.FN;   // 0 / 1 / 4 / 8 -> 0 .. 3
+    FanKernel f = nullptr;
+    switch (k.family) {
+    case FanFamily::Coarse:
+    case FanFamily::Fine: f = kFanInterleaved[(int)k.mode].k[fn][k.UE ? 1 : 0]; break;
+    case FanFamily::Xcd:   // (FAN_PLAIN only, over a fine copy)
+        f = fn > 0 && k.mode == FanMode::Plain ? kFanXcd[fn - 1][__builtin_ctz(k.NPW)] : nullptr;
+        break;
+    case FanFamily::PoseMajor: f = k_raycast_fan_pm<128, true>; break;
+    case FanFamily::OccBit: f = k_raycast_fan<FAN_PLAIN, 64, false>; break;
     }
-#undef PCP_XCD
+    if (!f) return hipErrorInvalidDeviceFunction;
+    hipExtLaunchKernelGGL(f, dim3(g.x, g.y), dim3((uint32_t)k.block), 0, st, ev0, ev1, 0, a, P);
+    return hipGetLastError();
 }
 
 static VisEnv make_env(pcp_ctx *ctx, const pcp_vl_params *p, const double *steps_d, int K) {
@@ -1807,24 +1822,18 @@ static void launch_score_cells(hipStream_t st, pcp_ctx *ctx, const VisEnv &E, in
     const dim3 gw((unsigned)(((uint64_t)C * G + kT - 1) / kT), (unsigned)(P + 1));
     const double *cx = ctx->cells_xyz.as<const double>();
     const float *cn = ctx->cells_nrm.as<const float>();
-#define PCP_WIDE_LAUNCH(SL, GG)                                                                  \
-    hipLaunchKernelGGL((k_score_cells_wide<SL, GG>), gw, dim3(kT), 0, st, E, cx, cn, C, poses_k, \
-                       P, zx_k, o.comb, o.mbits, score_z, o.zbits, o.stats, P_dev, C_dev)
-    if (wide && E.K <= kStepLds) {
-        if (G == 2) PCP_WIDE_LAUNCH(true, 2);
-        else if (G == 4) PCP_WIDE_LAUNCH(true, 4);
-        else if (G == 8) PCP_WIDE_LAUNCH(true, 8);
-        else PCP_WIDE_LAUNCH(true, kWideG);
-    } else if (wide) {
-        PCP_WIDE_LAUNCH(false, kWideG);   // (a step table past LDS: the default width only)
-    } else if (E.K <= kStepLds) {
-        hipLaunchKernelGGL(k_score_cells<true>, g, dim3(kT), 0, st, E, cx, cn, C, poses_k, P, zx_k,
-                           o.comb, o.mbits, score_z, o.zbits, o.stats, P_dev, C_dev);
-    } else {
-        hipLaunchKernelGGL(k_score_cells<false>, g, dim3(kT), 0, st, E, cx, cn, C, poses_k, P,
-                           zx_k, o.comb, o.mbits, score_z, o.zbits, o.stats, P_dev, C_dev);
-    }
-#undef PCP_WIDE_LAUNCH
+    // k_score_cells_wide by [SL][G 2 / 4 / 8 / 16] (a step table past LDS: the default width
+    // only), k_score_cells by [SL]
+    using ScoreKernel = decltype(&k_score_cells<true>);
+    static constexpr ScoreKernel kWide[2][4] = {
+        {nullptr, nullptr, nullptr, k_score_cells_wide<false, kWideG>},
+        {k_score_cells_wide<true, 2>, k_score_cells_wide<true, 4>, k_score_cells_wide<true, 8>,
+         k_score_cells_wide<true, kWideG>}};
+    static constexpr ScoreKernel kNarrow[2] = {k_score_cells<false>, k_score_cells<true>};
+    const bool sl = E.K <= kStepLds;
+    const ScoreKernel f = wide ? kWide[sl][__builtin_ctz((unsigned)G) - 1] : kNarrow[sl];
+    hipLaunchKernelGGL(f, wide ? gw : g, dim3(kT), 0, st, E, cx, cn, C, poses_k, P, zx_k, o.comb,
+                       o.mbits, score_z, o.zbits, o.stats, P_dev, C_dev);
 }
 
 // runOptimization's scoring up to the per-pose sums, enqueued on ctx->stream: poses + the
@@ -2218,11 +2227,10 @@ int pcp_generate_and_score(pcp_ctx *ctx, const double bb[6], const pcp_vl_params
 namespace pcp {
 // Everything of a fan query up to the per-pose sums, enqueued on ctx->stream (no host sync
 // unless the fan tables or the step table change): poses uploaded through the pinned block,
-// the march, k_fan_reduce.  On return o.blocked_d / o.units_d (and o.fh_d when want_fh) are
+// the march, k_fan_reduce.  On return o.blocked_d / o.units_d (and o.fh_d when opt.want_fh) are
 // device results in flight; the caller synchronizes.  n > 0.
 int fan_enqueue(pcp_ctx *ctx, const double *poses5, uint64_t n, const pcp_fan_params *fan,
-                bool want_fh, bool stats, bool stamps, FanEnq &o, int burst, double *burst_ms,
-                bool host_out) {
+                FanEnq &o, FanMode mode, const FanOpts &opt) {
     if (fan->n_az <= 0 || fan->n_el <= 0 || (int64_t)fan->n_az * fan->n_el > (1ll << 30))
         return set_err(ctx, PCP_E_INVALID, "pcp_raycast_fan: bad fan size %d x %d", fan->n_az,
                        fan->n_el);
@@ -2269,20 +2277,34 @@ int fan_enqueue(pcp_ctx *ctx, const double *poses5, uint64_t n, const pcp_fan_pa
     }
     PCP_HIP(ctx, ctx->poses_d.ensure((size_t)P * 8 * sizeof(double)));
     const uint32_t waves = (rays + 63) / 64;
+    if ((uint64_t)waves * (uint64_t)P >= (1ull << 31))
+        return set_err(ctx, PCP_E_INVALID, "pcp_raycast_fan: %d poses x %u rays exceed one launch",
+                       P, rays);
+    if (int rcb = terrain_blocks_before_query(ctx)) return rcb;
+    FanArgs a{};
+    a.present = ctx->terrain.present ? 1 : 0;
+    if (a.present) {
+        a.g = ctx->terrain.view();
+        if (!a.g.occz) return set_err(ctx, PCP_E_INVALID, "pcp_raycast_fan: terrain index has no z bands");
+        if (ctx->fan_batch == 2 && !a.g.occ2)
+            return set_err(ctx, PCP_E_STATE, "pcp_raycast_fan: variant 2 needs a terrain set with PCP_FAN_BATCH=2");
+    }
+    a.uniform_el = (fan->n_az % 64 == 0) ? 1 : 0;
+    // the kernel and whether it runs on the full grid: asked once, here (pcp_fan_pick.hpp)
+    const FanPick pick = fan_pick(mode, ctx->fan_batch, a.g.frec != nullptr, a.g.ftile,
+                                  a.uniform_el != 0, P, K, ctx->fan_npw, opt.burst > 0);
     // Skip 4: each pose's live rings [j0, j1) into its eighth slot (the UE
     // kernels leave a pose's dead rings at once), and the waves that hold a live ring of some
-    // pose: only those are launched.  The diagnostic launches and the A/B variant with
-    // 128-thread blocks keep the full grid.
+    // pose: only those are launched, unless the pick needs the full grid.
     uint32_t w0 = 0, lw = waves;
     {
         uint32_t *lr = reinterpret_cast<uint32_t *>(pose8 + 7);
         const bool rule = ctx->fan_cull && ctx->terrain.present && K > 0;
         if (rule) {
-            const GridView tv = ctx->terrain.view();
-            const FanLive L = fan_live_rings((double)tv.fb[4], (double)tv.fb[5], pose8 + 2,
+            const FanLive L = fan_live_rings((double)a.g.fb[4], (double)a.g.fb[5], pose8 + 2,
                                              (uint64_t)P, 8, ctx->fan_se_h.data(), fan->n_el,
                                              ctx->steps_first, ctx->steps_last, lr, 16);
-            if (!stats && !stamps && ctx->fan_batch != 1) {
+            if (!pick.full_grid) {
                 const FanWaves W = fan_live_waves(L, fan->n_az, fan->n_el);
                 w0 = W.w0;
                 lw = W.w1 - W.w0;
@@ -2294,37 +2316,26 @@ int fan_enqueue(pcp_ctx *ctx, const double *poses5, uint64_t n, const pcp_fan_pa
             }
         }
     }
-    if ((uint64_t)waves * (uint64_t)P >= (1ull << 31))
-        return set_err(ctx, PCP_E_INVALID, "pcp_raycast_fan: %d poses x %u rays exceed one launch",
-                       P, rays);
     PCP_HIP(ctx, ctx->out_c.ensure((size_t)P * (sizeof(uint32_t) + sizeof(uint64_t)) + 64));
     PCP_HIP(ctx, ctx->out_b.ensure(((size_t)P * waves + 8) * sizeof(uint2)));
     // stamps: 4 per wave; stats: 3 per wave + the 3 sums
-    const size_t stats_bytes = stamps  ? (size_t)P * waves * 4 * sizeof(uint64_t)
-                               : stats ? ((size_t)P * waves * 4 + 4) * sizeof(uint64_t)
-                                       : 64 * sizeof(uint64_t);
+    const size_t stats_bytes =
+        mode == FanMode::Stamps  ? (size_t)P * waves * 4 * sizeof(uint64_t)
+        : mode == FanMode::Stats ? ((size_t)P * waves * 4 + 4) * sizeof(uint64_t)
+                                 : 64 * sizeof(uint64_t);
     PCP_HIP(ctx, ctx->stats_d.ensure(stats_bytes));
     if (int rc0 = copy_pinned_async(ctx, ctx->poses_d.p, pose8, (size_t)P * 8 * sizeof(double), st))
         return rc0;
     // results land in device memory, or (host_out) straight in the pinned block behind the
     // staged poses: one copy and its dispatch fewer per query
     unsigned long long *units_d =
-        host_out ? reinterpret_cast<unsigned long long *>(pose8 + 8 * (size_t)P)
-                 : ctx->out_c.as<unsigned long long>();
+        opt.host_out ? reinterpret_cast<unsigned long long *>(pose8 + 8 * (size_t)P)
+                     : ctx->out_c.as<unsigned long long>();
     uint32_t *blocked_d = reinterpret_cast<uint32_t *>(units_d + P);
     int16_t *fh_d = nullptr;
-    if (want_fh) {
+    if (opt.want_fh) {
         PCP_HIP(ctx, ctx->out_d.ensure((size_t)P * rays * sizeof(int16_t)));
         fh_d = ctx->out_d.as<int16_t>();
-    }
-    if (int rcb = terrain_blocks_before_query(ctx)) return rcb;
-    FanArgs a{};
-    a.present = ctx->terrain.present ? 1 : 0;
-    if (a.present) {
-        a.g = ctx->terrain.view();
-        if (!a.g.occz) return set_err(ctx, PCP_E_INVALID, "pcp_raycast_fan: terrain index has no z bands");
-        if (ctx->fan_batch == 2 && !a.g.occ2)
-            return set_err(ctx, PCP_E_STATE, "pcp_raycast_fan: variant 2 needs a terrain set with PCP_FAN_BATCH=2");
     }
     const double *tab = ctx->fan_tab.as<const double>();
     a.ca = tab;
@@ -2335,7 +2346,6 @@ int fan_enqueue(pcp_ctx *ctx, const double *poses5, uint64_t n, const pcp_fan_pa
     a.steps = ctx->steps_d.as<const double>();
     a.K = K;
     a.n_az = fan->n_az;
-    a.uniform_el = (fan->n_az % 64 == 0) ? 1 : 0;
     a.rays = rays;
     a.waves = waves;
     a.w0 = w0;
@@ -2353,78 +2363,21 @@ int fan_enqueue(pcp_ctx *ctx, const double *poses5, uint64_t n, const pcp_fan_pa
     a.first_hit = fh_d;
     a.wave_part = ctx->out_b.as<uint2>();
     a.stats = ctx->stats_d.as<unsigned long long>();
-    const dim3 grid1(lw * (uint32_t)P);   // 64-thread blocks, pose-interleaved (live waves)
-    // the fine-window kernels (28 VGPRs, 8 waves per SIMD), the ring index a
-    // scalar when n_az % 64 == 0 (UE); the coarse layouts' kernel otherwise
-    const bool fine = a.g.frec != nullptr, ue = a.uniform_el != 0, tile = a.g.ftile != 0;
-    const bool split = a.g.ftile == 2;
-    // poses per wave: the largest of ctx->fan_npw, ..., 2, 1 that divides the XCD pose chunk
-    int npw = ctx->fan_npw;
-    while (npw > 1 && P % (8 * npw) != 0) npw >>= 1;
-#define PCP_FAN_LAUNCH(MODE)                                                                   \
-    do {                                                                                       \
-        if (fine && split && ue)                                                               \
-            hipLaunchKernelGGL((k_raycast_fan<MODE, 64, true, 8, 8, true>), grid1, dim3(64), 0, \
-                               st, a, (uint32_t)P);                                            \
-        else if (fine && split)                                                                \
-            hipLaunchKernelGGL((k_raycast_fan<MODE, 64, true, 8, 8, false>), grid1, dim3(64), 0,\
-                               st, a, (uint32_t)P);                                            \
-        else if (fine && tile && ue)                                                           \
-            hipLaunchKernelGGL((k_raycast_fan<MODE, 64, true, 8, 4, true>), grid1, dim3(64), 0, \
-                               st, a, (uint32_t)P);                                            \
-        else if (fine && tile)                                                                 \
-            hipLaunchKernelGGL((k_raycast_fan<MODE, 64, true, 8, 4, false>), grid1, dim3(64), 0,\
-                               st, a, (uint32_t)P);                                            \
-        else if (fine && ue)                                                                   \
-            hipLaunchKernelGGL((k_raycast_fan<MODE, 64, true, 8, 1, true>), grid1, dim3(64), 0, \
-                               st, a, (uint32_t)P);                                            \
-        else if (fine)                                                                         \
-            hipLaunchKernelGGL((k_raycast_fan<MODE, 64, true, 8, 1, false>), grid1, dim3(64), 0,\
-                               st, a, (uint32_t)P);                                            \
-        else                                                                                   \
-            hipLaunchKernelGGL((k_raycast_fan<MODE>), grid1, dim3(64), 0, st, a, (uint32_t)P); \
-    } while (0)
-#define PCP_FAN_LAUNCH_T(MODE)                                                                 \
-    do {                                                                                       \
-        if (fine && split && ue)                                                               \
-            hipExtLaunchKernelGGL((k_raycast_fan<MODE, 64, true, 8, 8, true>), grid1, dim3(64), \
-                                  0, st, kt.a, kt.b, 0, a, (uint32_t)P);                       \
-        else if (fine && split)                                                                \
-            hipExtLaunchKernelGGL((k_raycast_fan<MODE, 64, true, 8, 8, false>), grid1, dim3(64),\
-                                  0, st, kt.a, kt.b, 0, a, (uint32_t)P);                       \
-        else if (fine && tile && ue)                                                           \
-            hipExtLaunchKernelGGL((k_raycast_fan<MODE, 64, true, 8, 4, true>), grid1, dim3(64), \
-                                  0, st, kt.a, kt.b, 0, a, (uint32_t)P);                       \
-        else if (fine && tile)                                                                 \
-            hipExtLaunchKernelGGL((k_raycast_fan<MODE, 64, true, 8, 4, false>), grid1, dim3(64),\
-                                  0, st, kt.a, kt.b, 0, a, (uint32_t)P);                       \
-        else if (fine && ue)                                                                   \
-            hipExtLaunchKernelGGL((k_raycast_fan<MODE, 64, true, 8, 1, true>), grid1, dim3(64), \
-                                  0, st, kt.a, kt.b, 0, a, (uint32_t)P);                       \
-        else if (fine)                                                                         \
-            hipExtLaunchKernelGGL((k_raycast_fan<MODE, 64, true, 8, 1, false>), grid1, dim3(64),\
-                                  0, st, kt.a, kt.b, 0, a, (uint32_t)P);                       \
-        else                                                                                   \
-            hipExtLaunchKernelGGL((k_raycast_fan<MODE>), grid1, dim3(64), 0, st, kt.a, kt.b, 0, \
-                                  a, (uint32_t)P);                                             \
-    } while (0)
-    if (stats) {
-        PCP_FAN_LAUNCH(FAN_STATS);
-        PCP_CHECK_LAUNCH(ctx);
+    const FanGrid grid = fan_grid(lw, (uint32_t)P, rays, pick);
+    if (mode != FanMode::Plain) {   // (the full grid: never empty)
+        PCP_HIP(ctx, fan_launch(pick, grid, st, nullptr, nullptr, a, (uint32_t)P));
         const size_t nw = (size_t)P * waves;
-        hipLaunchKernelGGL(k_sum_u64, dim3(4), dim3(1024), 0, st,
-                           (const unsigned long long *)a.stats, nw, a.stats + 4 * nw);
-        PCP_CHECK_LAUNCH(ctx);
-        o.stats_d = a.stats + 4 * nw;
-    } else if (stamps) {
-        PCP_FAN_LAUNCH(FAN_STAMPS);
-        PCP_CHECK_LAUNCH(ctx);
-        o.stats_d = a.stats;
-    } else if (lw == 0) {
+        o.stats_d = mode == FanMode::Stats ? a.stats + 4 * nw : a.stats;
+        if (mode == FanMode::Stats) {
+            hipLaunchKernelGGL(k_sum_u64, dim3(4), dim3(1024), 0, st,
+                               (const unsigned long long *)a.stats, nw, a.stats + 4 * nw);
+            PCP_CHECK_LAUNCH(ctx);
+        }
+    } else if (grid.x == 0) {
         // every ring is dead for every pose: no march (a zero-sized grid is not submitted);
         // k_fan_reduce below gives the closed-form result
-        if (burst_ms) *burst_ms = 0.0;
-    } else if (burst > 0) {
+        if (opt.burst_ms) *opt.burst_ms = 0.0;
+    } else if (opt.burst > 0) {
         // the production kernel `burst` times back-to-back between two events: the queue never
         // idles between the events, so the interval is the launches themselves (the per-call
         // events of a synchronous query also hold the queue's wake-up before the kernel)
@@ -2432,47 +2385,19 @@ int fan_enqueue(pcp_ctx *ctx, const double *poses5, uint64_t n, const pcp_fan_pa
         PCP_HIP(ctx, hipEventCreate(&e0));
         PCP_HIP(ctx, hipEventCreate(&e1));
         PCP_HIP(ctx, hipEventRecord(e0, st));
-        for (int r = 0; r < burst; ++r) {
-            if (fine && tile && ue && P % (8 * npw) == 0 && K <= kStepLds)
-                launch_xcd(npw, a, (uint32_t)P, st, nullptr, nullptr);
-            else if (fine && ue && P % 8 == 0 && K <= kStepLds)
-                hipLaunchKernelGGL((k_raycast_fan_xcd<FAN_PLAIN>), grid1, dim3(64), 0, st, a,
-                                   (uint32_t)P);
-            else
-                PCP_FAN_LAUNCH(FAN_PLAIN);
-        }
-        PCP_CHECK_LAUNCH(ctx);
+        for (int r = 0; r < opt.burst; ++r)
+            PCP_HIP(ctx, fan_launch(pick, grid, st, nullptr, nullptr, a, (uint32_t)P));
         PCP_HIP(ctx, hipEventRecord(e1, st));
         PCP_HIP(ctx, hipEventSynchronize(e1));
         float ms = 0.0f;
         PCP_HIP(ctx, hipEventElapsedTime(&ms, e0, e1));
         (void)hipEventDestroy(e0);
         (void)hipEventDestroy(e1);
-        if (burst_ms) *burst_ms = (double)ms / burst;
+        if (opt.burst_ms) *opt.burst_ms = (double)ms / opt.burst;
     } else {
         KernelTimer kt(ctx, PCP_K_RAYCAST_FAN);   // events around the kernel itself
-        // PCP_FAN_BATCH selects the A/B variants of DESIGN.md §6b
-        const dim3 grid128((rays + 127) / 128, P);
-        switch (ctx->fan_batch) {
-        case 1: hipExtLaunchKernelGGL((k_raycast_fan_pm<128, true>), grid128, dim3(128), 0, st, kt.a, kt.b, 0, a); break;
-        case 2: hipExtLaunchKernelGGL((k_raycast_fan<FAN_PLAIN, 64, false>), grid1, dim3(64), 0, st, kt.a, kt.b, 0, a, (uint32_t)P); break;
-        case 4: PCP_FAN_LAUNCH_T(FAN_PLAIN); break;   // A/B: plain pose interleaving
-        default:
-            // XCD-chunked placement (each XCD's L2 serves neighbouring poses' overlapping fans):
-            // 0.61 vs 0.63 ms on C2
-            if (fine && tile && ue && P % (8 * npw) == 0 && K <= kStepLds)
-                launch_xcd(npw, a, (uint32_t)P, st, kt.a, kt.b);
-            else if (fine && ue && P % 8 == 0 && K <= kStepLds)
-                hipExtLaunchKernelGGL((k_raycast_fan_xcd<FAN_PLAIN>), grid1, dim3(64), 0, st, kt.a,
-                                      kt.b, 0, a, (uint32_t)P);
-            else
-                PCP_FAN_LAUNCH_T(FAN_PLAIN);
-            break;
-        }
-        PCP_CHECK_LAUNCH(ctx);
+        PCP_HIP(ctx, fan_launch(pick, grid, st, kt.a, kt.b, a, (uint32_t)P));
     }
-#undef PCP_FAN_LAUNCH
-#undef PCP_FAN_LAUNCH_T
     // the rays the launch covered: [r_lo, r_hi) of each pose
     const uint32_t r_lo = w0 * 64u, r_hi = std::min<uint64_t>((uint64_t)(w0 + lw) * 64u, rays);
     hipLaunchKernelGGL(k_fan_reduce, dim3(P), dim3(kT), 0, st,
@@ -2481,8 +2406,8 @@ int fan_enqueue(pcp_ctx *ctx, const double *poses5, uint64_t n, const pcp_fan_pa
                        (unsigned long long)(rays - (r_hi - r_lo)) * (unsigned long long)K, fh_d,
                        rays, r_lo, r_hi);
     PCP_CHECK_LAUNCH(ctx);
-    o.blocked_d = host_out ? nullptr : blocked_d;
-    o.units_d = host_out ? nullptr : units_d;
+    o.blocked_d = opt.host_out ? nullptr : blocked_d;
+    o.units_d = opt.host_out ? nullptr : units_d;
     o.fh_d = fh_d;
     o.rays = rays;
     o.stats_bytes = stats_bytes;
@@ -2499,8 +2424,9 @@ extern "C" {
 
 static int raycast_fan_impl(pcp_ctx *ctx, const double *poses5, uint64_t n,
                             const pcp_fan_params *fan, uint32_t *blocked, uint64_t *units,
-                            int16_t *first_hit, int64_t *best_idx, uint64_t *stats,
-                            uint64_t *stamps, int burst = 0, double *burst_ms = nullptr) {
+                            int16_t *first_hit, int64_t *best_idx,
+                            FanMode mode = FanMode::Plain, uint64_t *diag = nullptr,
+                            int burst = 0, double *burst_ms = nullptr) {
     if (!ctx) return PCP_E_INVALID;
     if (!fan || (n && (!poses5 || !blocked)))
         return set_err(ctx, PCP_E_INVALID, "pcp_raycast_fan: null argument");
@@ -2511,19 +2437,18 @@ static int raycast_fan_impl(pcp_ctx *ctx, const double *poses5, uint64_t n,
                            fan->n_az, fan->n_el);
         return PCP_OK;
     }
-    FanEnq o;
+    FanEnq o;   // (the kernel and its poses per wave: pcp_fan_pick.hpp, mirrored by bench._fan_npw)
     const bool host_out = ctx->fan_host_out;
-    if (int rc = fan_enqueue(ctx, poses5, n, fan, first_hit != nullptr, stats != nullptr,
-                             stamps != nullptr, o, burst, burst_ms, host_out))
+    if (int rc = fan_enqueue(ctx, poses5, n, fan, o, mode,
+                             FanOpts{first_hit != nullptr, burst, burst_ms, host_out}))
         return rc;
     hipStream_t st = ctx->stream;
     const int P = (int)n;
     const uint32_t rays = o.rays;
-    if (stats)
-        PCP_HIP(ctx, hipMemcpyAsync(stats, o.stats_d, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost,
-                                    st));
-    if (stamps)
-        PCP_HIP(ctx, hipMemcpyAsync(stamps, o.stats_d, o.stats_bytes, hipMemcpyDeviceToHost, st));
+    if (diag)   // the four sums, or every wave's stamps
+        PCP_HIP(ctx, hipMemcpyAsync(diag, o.stats_d,
+                                    mode == FanMode::Stats ? 4 * sizeof(uint64_t) : o.stats_bytes,
+                                    hipMemcpyDeviceToHost, st));
     // units and blocked are adjacent on the device: one copy into the pinned block
     double *pose8 = ctx->fan_host.as<double>();
     uint64_t *u_h = reinterpret_cast<uint64_t *>(pose8 + 8 * (size_t)P);
@@ -2549,8 +2474,7 @@ static int raycast_fan_impl(pcp_ctx *ctx, const double *poses5, uint64_t n,
 
 int pcp_raycast_fan(pcp_ctx *ctx, const double *poses5, uint64_t n, const pcp_fan_params *fan,
                     uint32_t *blocked, uint64_t *units, int16_t *first_hit, int64_t *best_idx) {
-    return raycast_fan_impl(ctx, poses5, n, fan, blocked, units, first_hit, best_idx, nullptr,
-                            nullptr);
+    return raycast_fan_impl(ctx, poses5, n, fan, blocked, units, first_hit, best_idx);
 }
 
 int pcp_raycast_fan_stats(pcp_ctx *ctx, const double *poses5, uint64_t n,
@@ -2558,8 +2482,8 @@ int pcp_raycast_fan_stats(pcp_ctx *ctx, const double *poses5, uint64_t n,
     if (!ctx || !stats) return PCP_E_INVALID;
     std::vector<uint32_t> blocked(n ? n : 1);
     stats[0] = stats[1] = stats[2] = stats[3] = 0;
-    return raycast_fan_impl(ctx, poses5, n, fan, blocked.data(), nullptr, nullptr, nullptr, stats,
-                            nullptr);
+    return raycast_fan_impl(ctx, poses5, n, fan, blocked.data(), nullptr, nullptr, nullptr,
+                            FanMode::Stats, stats);
 }
 
 int pcp_raycast_fan_burst(pcp_ctx *ctx, const double *poses5, uint64_t n,
@@ -2568,7 +2492,7 @@ int pcp_raycast_fan_burst(pcp_ctx *ctx, const double *poses5, uint64_t n,
     std::vector<uint32_t> blocked(n ? n : 1);
     *ms_per_launch = 0.0;
     return raycast_fan_impl(ctx, poses5, n, fan, blocked.data(), nullptr, nullptr, nullptr,
-                            nullptr, nullptr, reps, ms_per_launch);
+                            FanMode::Plain, nullptr, reps, ms_per_launch);
 }
 
 int pcp_raycast_fan_stamps(pcp_ctx *ctx, const double *poses5, uint64_t n,
@@ -2576,7 +2500,7 @@ int pcp_raycast_fan_stamps(pcp_ctx *ctx, const double *poses5, uint64_t n,
     if (!ctx || !stamps) return PCP_E_INVALID;
     std::vector<uint32_t> blocked(n ? n : 1);
     return raycast_fan_impl(ctx, poses5, n, fan, blocked.data(), nullptr, nullptr, nullptr,
-                            nullptr, stamps);
+                            FanMode::Stamps, stamps);
 }
 
 // one rank's shard of a pose-sharded fan query whose collective the caller runs (one process
@@ -2598,7 +2522,7 @@ int pcp_raycast_fan_keys(pcp_ctx *ctx, const double *poses5, uint64_t n,
     const uint32_t *blocked_d = nullptr;
     if (n) {
         FanEnq o;
-        if (int rc = fan_enqueue(ctx, poses5, n, fan, false, false, false, o)) return rc;
+        if (int rc = fan_enqueue(ctx, poses5, n, fan, o)) return rc;
         blocked_d = o.blocked_d;
         if (units_dev)
             PCP_HIP(ctx, hipMemcpyAsync(units_dev, o.units_d, n * sizeof(uint64_t),

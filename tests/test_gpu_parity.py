@@ -761,6 +761,79 @@ def test_raycast_fan_clutter_and_odd_fans(oracle, n_az, n_el):
         ctx.close()
 
 
+_CLUTTER_POSES = np.array([[0.0, 0.0, 0.2, 0.0, 0.3], [1.5, -1.5, 1.5, 0.0, -2.0],
+                           [-4.0, 2.0, 2.5, 0.0, 1.0], [0.5, 4.0, -1.5, 0.0, 0.0],
+                           [40.0, 40.0, 0.0, 0.0, 0.0], [2.9, 0.0, 0.5, 0.0, 3.1]])
+_clutter_refs = {}
+
+
+def _clutter_reference(oracle, n_az, n_el, n_poses):
+    """The oracle's fan over _clutter_cloud() for the poses of
+    test_raycast_fan_clutter_and_odd_fans (resized cyclically to n_poses), computed once."""
+    key = (n_az, n_el, n_poses)
+    if key not in _clutter_refs:
+        poses = np.resize(_CLUTTER_POSES, (n_poses, 5))
+        fan = _abi.fan_params(n_az=n_az, n_el=n_el)
+        if "cloud" not in _clutter_refs:
+            _clutter_refs["cloud"] = _clutter_cloud()
+        T = oracle.Cloud(_clutter_refs["cloud"])
+        r = oracle.raycast_fan(T, poses, n_az, n_el, fan.el_min, fan.el_max, fan.max_distance)
+        for a in r:
+            a.setflags(write=False)
+        _clutter_refs[key] = (poses, fan) + tuple(r)
+    return (_clutter_refs["cloud"],) + _clutter_refs[key]
+
+
+@pytest.mark.parametrize("n_az,n_el", [(100, 37), (64, 3)])
+@pytest.mark.parametrize("variant", ["1", "2", "4"])
+def test_raycast_fan_batch_variants(oracle, monkeypatch, variant, n_az, n_el):
+    """The A/B launches of PCP_FAN_BATCH (1 the pose-major grid of 128-thread
+    blocks, 2 the occupancy-bit probe, 4 plain pose interleaving) on the clutter cloud of
+    test_raycast_fan_clutter_and_odd_fans: its six poses, and eight of them (a whole number of
+    XCD pose chunks).  The variable is read when the context is created (variant 2 builds its
+    occupancy bits in set_terrain).  First hits, blocked counts and ray-hit tests bit-exact."""
+    monkeypatch.setenv("PCP_FAN_BATCH", variant)
+    ctx = _abi.Context(0)
+    try:
+        for n_poses in (6, 8):
+            cloud, poses, fan, r_blocked, r_units, r_fh = _clutter_reference(oracle, n_az, n_el,
+                                                                              n_poses)
+            if n_poses == 6:
+                ctx.set_terrain(cloud)
+            blocked, units, fh, best = ctx.raycast_fan(poses, fan, want_first_hit=True)
+            np.testing.assert_array_equal(fh, r_fh)
+            np.testing.assert_array_equal(blocked, r_blocked)
+            np.testing.assert_array_equal(units, r_units)
+            assert best == int(np.argmin(r_blocked))
+            assert blocked[4] == 0 and blocked[0] > 0
+    finally:
+        ctx.close()
+
+
+def test_raycast_fan_stamps_mode(oracle):
+    """pcp_raycast_fan_stamps (the wave-lifetime diagnostic: the interleaved kernels on the full
+    grid) on the 64 x 3 fan over the clutter cloud, eight poses: four clock stamps in every
+    (pose, wave) slot, in order; the plain query after it gives what the one before it gave."""
+    cloud, poses, fan, r_blocked, r_units, r_fh = _clutter_reference(oracle, 64, 3, 8)
+    ctx = _abi.Context(0)
+    try:
+        ctx.set_terrain(cloud)
+        before = ctx.raycast_fan(poses, fan, want_first_hit=True)
+        st = ctx.raycast_fan_stamps(poses, fan)
+        after = ctx.raycast_fan(poses, fan, want_first_hit=True)
+    finally:
+        ctx.close()
+    assert st.shape == (8, (64 * 3 + 63) // 64, 4) and st.dtype == np.uint64
+    assert (st[..., 0] > 0).all()   # every slot written (the buffer starts zeroed)
+    assert (st[..., 0] <= st[..., 1]).all() and (st[..., 1] <= st[..., 2]).all()
+    assert (st[..., 2] <= st[..., 3]).all()
+    for b, a in zip(before, after):
+        np.testing.assert_array_equal(np.asarray(a), np.asarray(b))
+    np.testing.assert_array_equal(before[2], r_fh)
+    np.testing.assert_array_equal(before[0], r_blocked)
+    np.testing.assert_array_equal(before[1], r_units)
+
+
 @pytest.mark.parametrize("dz,skip", [(3000.0, "1"), (-2500.0, "1"), (3000.0, "2"),
                                      (-2500.0, "2")])
 def test_raycast_fan_far_from_origin(oracle, scene, cells, dz, skip, monkeypatch):
