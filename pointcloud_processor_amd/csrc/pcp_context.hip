@@ -688,7 +688,10 @@ int pcp_create(int device, pcp_ctx **out) {
         ctx->nb_guess_max = std::max<uint64_t>(1, std::strtoull(gw, nullptr, 10));
     if (const char *ct = std::getenv("PCP_COPY_THREADS")) ctx->copy_threads = std::atoi(ct);
     if (const char *fo = std::getenv("PCP_FM_HOST_OUT")) ctx->fm_host_out = std::atoi(fo) != 0;
-    if (const char *ff = std::getenv("PCP_FM_FAST")) ctx->fm_fast = std::atoi(ff);
+    if (const char *ff = std::getenv("PCP_FM_FAST")) {   // an unknown value is the default
+        const int v = std::atoi(ff);
+        ctx->fm_fast = (v == 0 || v == 1) ? v : 2;
+    }
     if (const char *bg = std::getenv("PCP_BK_GT")) ctx->bk_gt = std::atoi(bg);
     if (const char *sp = std::getenv("PCP_SCAN_PAIR")) ctx->scan_pair = std::atoi(sp) != 0;
     if (const char *fc = std::getenv("PCP_CARVE_FUSE_COPY")) ctx->carve_fuse_copy = std::atoi(fc) != 0;

@@ -2,14 +2,21 @@
 // (tf2::doTransform + colour + concat) on gfx950.
 //
 // Every kernel is batched over clouds: blockIdx.y = cloud, its job (input view, box, leaf,
-// scratch, transform) read from a device table, so a dual-LiDAR frame is one chain of ~12
-// launches in which every launch covers all clouds' tiles.
-//  crop    : one read of the input; stable compaction per 4096-point tile into a sparse buffer,
-//            gaps closed (and voxel keys computed) by a second, small kernel
-//  voxel   : PCL VoxelGrid<PointXYZ> keying in float exactly as applyFilter; stable LSD radix
-//            sort of (key, point) with 9-bit digits (LDS-staged, coalesced scatter); voxel
-//            heads + float centroids summed in input order
-//  merge   : Eigen float Affine3f * p = ((m0 x + m1 y) + m2 z) + t, PointXYZRGB records
+// scratch, transform) passed with the launch, so a dual-LiDAR frame is one chain of launches in
+// which every launch covers all clouds' tiles.
+//  crop    : one read of the input; stable compaction per 4096-point tile into a sparse buffer
+//  voxel   : PCL VoxelGrid<PointXYZ> keying in float exactly as applyFilter, the centroids
+//            summed in input order, by one of three chains (which one: filter_plan(),
+//            pcp_filter_plan.hpp):
+//    general : k_crop_tile<false>, k_vox_params, k_compact_keys (gaps closed, keys from the
+//              cropped bbox), stable LSD radix passes with 9-bit digits (k_radix_hist,
+//              k_radix_scatter), k_seg_count, k_seg_centroid; any box, any leaf, passthrough
+//    LSD fast: k_crop_tile<true> forms box-relative keys itself, k_hist0, k_radix_scatter0 read
+//              the crop tiles, then the remaining passes, k_seg_count, k_seg_centroid
+//    bucket  : k_crop_tile<false>, k_bk_group, k_bk_sort, k_bk_emit (the default for a bounded
+//              box; a frame that sets its redo flag runs again on another chain)
+//  merge   : Eigen float Affine3f * p = ((m0 x + m1 y) + m2 z) + t, PointXYZRGB records, written
+//            by the chain's last kernel or by a separate k_emit_rgb
 #pragma clang fp contract(off)
 
 #include <cfloat>
@@ -17,6 +24,7 @@
 #include <cstring>
 #include <vector>
 
+#include "pcp_filter_plan.hpp"
 #include "pcp_internal.hpp"
 #include "pcp_rigid.hpp"
 
@@ -27,23 +35,8 @@ constexpr int kFT = 256;            // threads per block
 #define PCP_CROP_THREADS 256
 #endif
 constexpr int kCT = PCP_CROP_THREADS;   // threads of a crop block (build knob)
-#ifndef PCP_CROP_TILE
-#define PCP_CROP_TILE 4096
-#endif
-constexpr int kCropTile = PCP_CROP_TILE;   // points per crop tile (build knob)
 constexpr int kCropItems = kCropTile / kCT;   // points per thread per crop tile
-constexpr int kST = 512;            // threads of the sort-tile kernels (8 waves)
 constexpr int kSW = kST / 64;
-#ifndef PCP_SORT_ITEMS
-#define PCP_SORT_ITEMS 8
-#endif
-constexpr int kSortItems = PCP_SORT_ITEMS;   // keys per thread per sort tile
-constexpr int kSortTile = kST * kSortItems;
-constexpr int kGroup = 16;          // sort tiles per prefix group (radix digit prefix sums)
-constexpr int kDigitBits = 9;       // radix digit: 512 bins, 3 passes for the C3 crop box
-constexpr int kBins = 1 << kDigitBits;
-constexpr int kMaxPasses = 4;       // ceil(32 / 9)
-constexpr int kMaxCloudsDev = 64;   // result slots of a call (= kMaxClouds below)
 
 // diagnostic build only (make STAMPS=1): per-tile phase times, s_memrealtime (100 MHz)
 #ifdef PCP_STAMPS
@@ -103,10 +96,6 @@ __device__ __forceinline__ void load_tile(const CloudIn &c, uint64_t base, float
         }
     }
 }
-
-struct Box {
-    double x0, x1, y0, y1, z0, z1;
-};
 
 // cropFrontArea predicate (pointcloud_filter.cpp:111-113): float promoted to double
 __device__ __forceinline__ bool in_box(const Box &b, float x, float y, float z) {
@@ -322,7 +311,7 @@ struct CloudJob {
     VoxParams *vp;
     Rigid rig;            // pcp_filter_merge's transform + colour of this cloud
     int32_t slot;         // result slot (index of the cloud in the call)
-    // the fast chain (pcp_filter_merge when every cloud certainly voxelises, enqueue_fast):
+    // the fast chain (pcp_filter_merge when every cloud certainly voxelises, apply_fast):
     // the crop forms BOX-relative voxel keys -- (floor(p * inv) - kb) per axis, mixed radix
     // kdx, kdxy -- whose order is PCL's idx order (a constant shift per axis does not change
     // the lexicographic (k, j, i) order), plus each crop tile's digit-0 counts; the first radix
@@ -344,14 +333,10 @@ struct CloudJob {
     // (the filter node's message), written by k_bk_emit; null otherwise
     float4 *keep16;
 };
-constexpr int kMaxGroupTiles = 32;   // crop tiles per pass-0 sort tile, at most
 constexpr int kS0Items = 10;         // pass-0 chunk: 5,120 items (a group of ~10 C3 crop tiles
 constexpr int kS0Tile = kST * kS0Items;   // holds ~4,000 +- 100: one chunk)
 
-// up to kBatch clouds per launch, passed BY VALUE: pointers loaded from kernel arguments are
-// known to be global (global_load, independent waits), which a table in memory would lose
-constexpr int kBatch = 8;
-struct JobBatch {
+struct JobBatch {   // by value (kBatch, pcp_filter_plan.hpp)
     CloudJob j[kBatch];
 };
 
@@ -379,12 +364,12 @@ __global__ void __launch_bounds__(kCT) PCP_CROP_ATTR k_crop_tile(const JobBatch 
             p.inv = J.kinv;
             *J.vp = p;
             res[J.slot] = 0;
-            res[kMaxCloudsDev + 2 * J.slot] = 0;
-            res[kMaxCloudsDev + 2 * J.slot + 1] = 0;
+            res[kMaxClouds + 2 * J.slot] = 0;
+            res[kMaxClouds + 2 * J.slot + 1] = 0;
         }
     }
     else if (J.bk && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0)
-        res[3 * kMaxCloudsDev] = 0;   // the bucket chain's redo flag (k_bk_* set it)
+        res[3 * kMaxClouds] = 0;   // the bucket chain's redo flag (k_bk_* set it)
     if (blockIdx.x >= J.nb) return;
     const CloudIn c = J.in;
     const Box b = J.box;
@@ -982,8 +967,8 @@ k_seg_centroid(const JobBatch jobs, uint32_t *__restrict__ res, float4 *__restri
     if (t == nact - 1 && threadIdx.x == 0) {
         res[slot] = pre + tot;
         if (J.fast) {   // no k_vox_params in the fast chain: the cropped count, no passthrough
-            res[kMaxCloudsDev + 2 * slot] = m;
-            res[kMaxCloudsDev + 2 * slot + 1] = 0;
+            res[kMaxClouds + 2 * slot] = m;
+            res[kMaxClouds + 2 * slot + 1] = 0;
         }
     }
     if (tot != 0) {   // uniform; 0: a tile inside one long voxel
@@ -1084,18 +1069,9 @@ k_seg_centroid(const JobBatch jobs, uint32_t *__restrict__ res, float4 *__restri
 //  k_bk_emit  : output offset of each bucket (voxels of the earlier buckets), the centroids
 //               copied there -- as merged records (transform + colour) for pcp_filter_merge
 // A bucket past kBkCap points (or a parameter past the sizes the host allotted) sets the redo
-// flag (res[3 * kMaxCloudsDev]); the host then runs the frame again on the LSD chain.
+// flag (res[3 * kMaxClouds]); the host then runs the frame again on the LSD chain.
 // =========================================================================================
 constexpr int kBkT = 512;                 // threads of the bucket kernels
-#ifndef PCP_BK_BITS
-#define PCP_BK_BITS 11
-#endif
-#ifndef PCP_BK_SUB
-#define PCP_BK_SUB 12
-#endif
-constexpr int kBkBits = PCP_BK_BITS;      // target: ~2^kBkBits buckets per cloud
-constexpr int kBkSubMax = PCP_BK_SUB;     // sub-key bits at most (LDS table of 2^kBkSubMax + 1)
-constexpr int kBkMax = 4096;              // buckets per cloud at most
 #ifndef PCP_BK_CAP
 #define PCP_BK_CAP 4096
 #endif
@@ -1104,15 +1080,12 @@ constexpr int kBkCap = PCP_BK_CAP;        // points per bucket at most (LDS of k
 #define PCP_BK_DENSE 512
 #endif
 constexpr int kBkDense = PCP_BK_DENSE;    // points per voxel ranked in k_bk_sort at most
-// bkv layout: [0, kBkChunkOff) per-bucket (voxels, item offset), then per-64-bucket voxel sums
-constexpr uint32_t kBkChunkOff = kBatch * kBkMax;
-constexpr int kBkGt = 15;                 // crop tiles per group at most
 constexpr int kBkGItems = 12;             // per thread and chunk in k_bk_group
 #ifndef PCP_BK_STAGE
 #define PCP_BK_STAGE 1                    // k_bk_group places a one-chunk group in LDS first
 #endif
 
-__device__ __forceinline__ void bk_redo(uint32_t *res) { res[3 * kMaxCloudsDev] = 1u; }
+__device__ __forceinline__ void bk_redo(uint32_t *res) { res[3 * kMaxClouds] = 1u; }
 
 // crop tile u of the group holding item q: the last u with cpre[u] <= q (cpre ascending)
 __device__ __forceinline__ uint32_t bk_tile_of(const uint32_t *cpre, uint32_t gt, uint32_t q) {
@@ -1218,8 +1191,8 @@ k_bk_group(const JobBatch jobs, uint32_t *__restrict__ res, uint2 *__restrict__ 
     if (g == 0 && threadIdx.x == 0) {
         *J.vp = p;
         res[J.slot] = 0;   // k_bk_emit writes it when the cloud has buckets
-        res[kMaxCloudsDev + 2 * J.slot] = tot;
-        res[kMaxCloudsDev + 2 * J.slot + 1] = 0;
+        res[kMaxClouds + 2 * J.slot] = tot;
+        res[kMaxClouds + 2 * J.slot + 1] = 0;
         if (redo) bk_redo(res);
     }
     if (p.nbk == 0) return;   // uniform: nothing cropped, or the frame is redone
@@ -1327,10 +1300,6 @@ __device__ __forceinline__ int bk_cloud_of(const JobBatch &jobs, int k, uint32_t
 // voxel's points by crop-slot position (input order), and the voxel sums in that order by the
 // voxel's first point.  The centroids land at the bucket's item offset in the cloud (sparse is
 // free after k_bk_group), (voxels, offset) in bkv[f]; k_bk_emit places them.
-#ifndef PCP_BK_T3
-#define PCP_BK_T3 512
-#endif
-constexpr int kBkT3 = PCP_BK_T3;
 // 64 VGPRs: 8 waves per SIMD, four 512-thread blocks per CU (LDS admits four); build knob
 // PCP_BK_W8=0 lets the compiler take 68 (three blocks per CU): 0.104 vs 0.101 ms per frame
 #ifndef PCP_BK_W8
@@ -1342,7 +1311,6 @@ constexpr int kBkT3 = PCP_BK_T3;
 #define PCP_BK_SORT_ATTR
 #endif
 constexpr int kBkItems3 = kBkCap / kBkT3;
-constexpr int kBkNg = kBkT3;              // groups per cloud at most (one per k_bk_sort thread)
 __global__ void __launch_bounds__(kBkT3) PCP_BK_SORT_ATTR
 k_bk_sort(const JobBatch jobs, int k, uint32_t *__restrict__ res, uint2 *__restrict__ bkv,
           int idx_out) {
@@ -1681,7 +1649,6 @@ __global__ void __launch_bounds__(kFT) k_xform_batch(XformBatch B, float4 *__res
 // transform frame runs without host round trips (and is captured into a hipGraph by
 // pcp_filter_merge when its inputs are device-resident).
 // =========================================================================================
-constexpr int kMaxClouds = 64;
 // result words of a call: counts [kMaxClouds], (cropped, passthrough) [2 kMaxClouds], the bucket
 // chain's redo flag
 constexpr int kResWords = 3 * kMaxClouds + 4;
@@ -1696,24 +1663,6 @@ static int ensure_misc(pcp_ctx *ctx, VoxParams *&vp, uint32_t *&res) {
     vp = reinterpret_cast<VoxParams *>(ctx->f_misc.as<char>());
     res = reinterpret_cast<uint32_t *>(ctx->f_misc.as<char>() + vb);
     return PCP_OK;
-}
-
-// radix passes needed for the voxel keys: from the crop box when it is finite (keys are below
-// prod((hi-lo)/leaf + 3)), else all 32 bits
-static int radix_passes(const Box &b, float leaf) {
-    const double lo[3] = {b.x0, b.y0, b.z0}, hi[3] = {b.x1, b.y1, b.z1};
-    double nv = 1.0;
-    int bits = 32;
-    bool finite = true;
-    for (int a = 0; a < 3; ++a) {
-        if (!std::isfinite(lo[a]) || !std::isfinite(hi[a])) finite = false;
-        else nv *= std::floor((hi[a] - lo[a]) / (double)leaf) + 3.0;
-    }
-    if (finite) {
-        bits = 0;
-        while (bits < 32 && std::ldexp(1.0, bits) < nv) ++bits;
-    }
-    return std::max(1, (bits + kDigitBits - 1) / kDigitBits);
 }
 
 // scratch of cloud `slot` (ctx->fbuf[slot], grow-only) and its job; the caller sized ctx->fbuf
@@ -1772,96 +1721,64 @@ static int make_job(pcp_ctx *ctx, int slot, const CloudIn &c, const Box &b, floa
     return PCP_OK;
 }
 
-// the fast chain's key geometry for job J (its box finite, leaf > 0, n > 0): box floor kb =
-// floor(lo * inv) - 2 per axis (a margin for the float product p * inv of a point just inside
-// the box), dims DX, DY, DZ past floor(hi * inv) + 1; false when the keys or the float
-// integers would not be exact (|values| >= 2^23, or DX * DY * DZ >= 2^31)
-static bool fast_geometry(pcp_ctx *ctx, int slot, CloudJob &J, int clouds = 1) {
-    if (J.in.n == 0 || !(J.leaf > 0.0f)) return false;
-    const float inv = 1.0f / J.leaf;
-    const double invd = (double)inv;
-    const double lo[3] = {J.box.x0, J.box.y0, J.box.z0}, hi[3] = {J.box.x1, J.box.y1, J.box.z1};
-    double dim[3];
-    for (int a = 0; a < 3; ++a) {
-        if (!std::isfinite(lo[a]) || !std::isfinite(hi[a])) return false;
-        const double f0 = std::floor(lo[a] * invd) - 2.0, f1 = std::floor(hi[a] * invd) + 2.0;
-        if (std::fabs(f0) >= 8388608.0 || std::fabs(f1) >= 8388608.0 || !(f1 > f0)) return false;
-        J.kb[a] = (float)f0;
-        dim[a] = f1 - f0 + 1.0;
+// a call's geometries (pcp_filter_plan.hpp: sizes only), per cloud
+struct CallGeo {
+    FastGeometry fast[kMaxClouds];
+    BucketGeometry bucket[kMaxClouds];
+};
+
+// the facts filter_plan() decides on, of the call's plain jobs
+static void plan_facts(const pcp_ctx *ctx, const std::vector<CloudJob> &jobs, FilterPlanIn &in,
+                       CallGeo &geo) {
+    const int k = (int)jobs.size();
+    in.clouds = k;
+    in.fm_fast = ctx->fm_fast;
+    in.fm_host_out = ctx->fm_host_out;
+    in.use_graphs = ctx->use_graphs;
+    for (int i = 0; i < k; ++i) {
+        const CloudJob &J = jobs[i];
+        geo.fast[i] = fast_geometry(J.box, J.leaf, J.in.n, J.nb, k, ctx->num_cus);
+        geo.bucket[i] = bucket_geometry(J.box, J.leaf, J.in.n, J.nb, k, ctx->num_cus, ctx->bk_gt,
+                                        ctx->bk_pts);
+        in.voxelises[i] = certainly_voxelises(J.box, J.leaf, J.in.n);
+        in.fast[i] = geo.fast[i].ok ? Geo::Available : Geo::Unavailable;
+        in.bucket[i] = geo.bucket[i].ok ? Geo::Available : Geo::Unavailable;
     }
-    const double nv = dim[0] * dim[1] * dim[2];
-    if (!(nv < 2147483647.0)) return false;
-    int bits = 0;
-    while (bits < 31 && std::ldexp(1.0, bits) < nv) ++bits;
-    const uint32_t nb = J.nb;
+}
+
+// a geometry into its cloud's job, its scratch reserved; false: the allocation failed
+static bool apply_fast(pcp_ctx *ctx, int slot, const FastGeometry &g, CloudJob &J) {
     CloudBufs &B = ctx->fbuf[slot];
-    if (B.skeys.ensure((size_t)nb * kCropTile * 4 + (size_t)nb * kBins * 4 + 256) != hipSuccess) {
+    if (B.skeys.ensure(g.skeys_bytes) != hipSuccess) {
         (void)hipGetLastError();
         return false;
     }
     J.fast = 1;
-    J.kinv = inv;
-    J.kdx = (uint32_t)dim[0];
-    J.kdxy = (uint32_t)dim[0] * (uint32_t)dim[1];
-    J.passes = std::max(1, (bits + kDigitBits - 1) / kDigitBits);
+    J.kinv = g.kinv;
+    for (int a = 0; a < 3; ++a) J.kb[a] = g.kb[a];
+    J.kdx = g.kdx;
+    J.kdxy = g.kdxy;
+    J.passes = g.passes;
     J.skeys = B.skeys.as<uint32_t>();
-    J.h0 = J.skeys + (size_t)nb * kCropTile;
-    // groups: every group of every cloud in one round of one-block-per-CU blocks (the pass-0
-    // scatter's LDS admits one per CU), at least 8 crop tiles each
-    const uint32_t cus = (uint32_t)std::max(ctx->num_cus, 1);
-    J.gt = std::min<uint32_t>(kMaxGroupTiles,
-                              std::max<uint32_t>(8, (nb * (uint32_t)clouds + cus - 1) / cus));
-    J.ng = (nb + J.gt - 1) / J.gt;
+    J.h0 = J.skeys + (size_t)J.nb * kCropTile;
+    J.gt = g.gt;
+    J.ng = g.ng;
     return true;
 }
-
-// the bucket chain's sizes for job J (finite box, leaf > 0, n > 0, box keys below 2^31): groups
-// of gt crop tiles (<= kBkNg per cloud), rows for the most buckets the cropped bbox can need
-static bool bucket_geometry(pcp_ctx *ctx, int slot, CloudJob &J, int clouds = 1) {
-    if (J.in.n == 0 || !(J.leaf > 0.0f)) return false;
-    const double lo[3] = {J.box.x0, J.box.y0, J.box.z0}, hi[3] = {J.box.x1, J.box.y1, J.box.z1};
-    double nv = 1.0;
-    for (int a = 0; a < 3; ++a) {
-        if (!std::isfinite(lo[a]) || !std::isfinite(hi[a])) return false;
-        nv *= std::floor((hi[a] - lo[a]) / (double)J.leaf) + 3.0;
-    }
-    if (!(nv < 2147483647.0)) return false;
-    const uint32_t nb = J.nb;
-    const uint32_t cus = (uint32_t)std::max(ctx->num_cus, 1);
-    // one round of blocks for all groups of the call, at most kBkGt tiles (< 64 Ki points) each;
-    // a frame that packs >= 8 tiles per group anyway takes 14: fewer, longer runs per bucket for
-    // k_bk_sort to gather (C3: 314 -> 304 MB per frame, same time), still one round
-    uint32_t gt = std::max<uint32_t>(1, (nb * (uint32_t)clouds + cus - 1) / cus);
-    if (gt >= 8) gt = std::max<uint32_t>(gt, 14);
-    if (ctx->bk_gt > 0) gt = (uint32_t)ctx->bk_gt;   // PCP_BK_GT (A/B)
-    gt = std::min<uint32_t>(gt, kBkGt);
-    const uint32_t ng = (nb + gt - 1) / gt;
-    if (ng > (uint32_t)kBkNg) return false;
-    // device: bs = clamp(max(bits(nvox) - kBkBits, bits(nvox) - bkpb), 0, kBkSubMax), nbk =
-    // ceil(nvox / 2^bs) <= 2^min(kBkBits, bkpb), or ceil(nvox / 2^kBkSubMax) where bs is clamped
-    int pb = 64;
-    if (ctx->bk_pts > 0) {
-        const uint64_t tgt = std::max<uint64_t>(J.in.n / (uint64_t)ctx->bk_pts, 1);
-        pb = 0;
-        while ((1ull << pb) < tgt) ++pb;
-    }
-    const double cap = std::max(std::ldexp(1.0, std::min(kBkBits, pb)),
-                                std::ceil(nv / std::ldexp(1.0, kBkSubMax)));
-    const uint32_t nbkcap = (uint32_t)std::min<double>(cap, (double)kBkMax);
+static bool apply_bucket(pcp_ctx *ctx, int slot, const BucketGeometry &g, CloudJob &J) {
     CloudBufs &B = ctx->fbuf[slot];
     // rows, and the look-back words of a call's clouds (sized here: enqueue may be capturing)
-    if (B.skeys.ensure((size_t)ng * (nbkcap + 1) * 4 + 256) != hipSuccess ||
-        ctx->bk_stat.ensure(((size_t)kBkChunkOff + kBatch * kBkMax / 64) * 8) != hipSuccess) {
+    if (B.skeys.ensure(g.skeys_bytes) != hipSuccess ||
+        ctx->bk_stat.ensure(g.stat_bytes) != hipSuccess) {
         (void)hipGetLastError();
         return false;
     }
     J.bk = 1;
-    J.bkpb = pb;
-    J.gt = gt;
-    J.ng = ng;
-    J.nbkcap = nbkcap;
+    J.bkpb = g.bkpb;
+    J.gt = g.gt;
+    J.ng = g.ng;
+    J.nbkcap = g.nbkcap;
     J.brows = B.skeys.as<uint32_t>();
-    J.fast = 0;
     return true;
 }
 
@@ -1892,69 +1809,50 @@ static std::vector<Batch> batches_of(const std::vector<CloudJob> &jobs) {
     return out;
 }
 
-// crop [-> voxel] of every cloud of one batch, on stream st
-static int enqueue_chain(pcp_ctx *ctx, const Batch &bt, uint32_t *res, hipStream_t st,
-                         float4 *emit = nullptr) {
-    const unsigned k = (unsigned)bt.k;
-    {
-        ProfScope ps(ctx, PCP_K_CROP, st);
-        if (bt.max_nb) {
-            hipLaunchKernelGGL(k_crop_tile<false>, dim3(bt.max_nb, k), dim3(kCT), 0, st, bt.jb,
-                               res);
-            PCP_CHECK_LAUNCH(ctx);
-        }
-        hipLaunchKernelGGL(k_vox_params, dim3(1, k), dim3(kFT), 0, st, bt.jb, res,
-                           res + kMaxClouds);
-        PCP_CHECK_LAUNCH(ctx);
-        if (bt.max_nb) {
-            hipLaunchKernelGGL(k_compact_keys, dim3(bt.max_nb, k), dim3(kFT), 0, st, bt.jb);
-            PCP_CHECK_LAUNCH(ctx);
-        }
-    }
-    if (bt.max_passes > 0) {
-        ProfScope ps(ctx, PCP_K_VOXEL, st);
-        // sort-tile kernels: LDS admits 8192 / kSortTile blocks per CU; the clouds share the CUs
-        const unsigned per_cu = (unsigned)std::max(1, 8192 / kSortTile);
-        const unsigned gx = std::max(1u, std::min<unsigned>(
-                                             bt.max_nt, per_cu * (unsigned)std::max(ctx->num_cus, 1) / k));
-        for (int pass = 0; pass < bt.max_passes; ++pass) {
-            hipLaunchKernelGGL(k_radix_hist, dim3(gx, k), dim3(kST), 0, st, bt.jb, pass);
-            PCP_CHECK_LAUNCH(ctx);
-            hipLaunchKernelGGL(k_radix_scatter, dim3(gx, k), dim3(kST), 0, st, bt.jb, pass);
-            PCP_CHECK_LAUNCH(ctx);
-        }
-        hipLaunchKernelGGL(k_seg_count, dim3(gx, k), dim3(kST), 0, st, bt.jb);
-        PCP_CHECK_LAUNCH(ctx);
-        hipLaunchKernelGGL(k_seg_centroid, dim3(gx, k), dim3(kST), 0, st, bt.jb, res, emit);
-        PCP_CHECK_LAUNCH(ctx);
-    }
-    return PCP_OK;
-}
-
-// the fast chain of one batch whose clouds all certainly voxelise (make_job set J.fast): keyed
-// crop -> digit-0 group counts -> pass 0 from the crop tiles -> passes 1.. -> voxels -> the
-// centroids emitted as merged records.  No k_vox_params / k_compact_keys and their passes.
-static int enqueue_fast(pcp_ctx *ctx, const Batch &bt, uint32_t *res, hipStream_t st,
-                        float4 *emit) {
+// the two LSD chains of one batch, on stream st.  General: crop -> parameters -> compaction +
+// keys -> every radix pass -> voxels.  Fast (the jobs carry apply_fast's geometry): keyed crop ->
+// digit-0 group counts -> pass 0 from the crop tiles -> passes 1.. -> voxels; no k_vox_params /
+// k_compact_keys and their passes.  emit: k_seg_centroid writes the merged records there.
+static int enqueue_lsd(pcp_ctx *ctx, const Batch &bt, uint32_t *res, hipStream_t st, float4 *emit,
+                       bool fast) {
     const unsigned k = (unsigned)bt.k;
     uint32_t max_ng = 0;
     for (int i = 0; i < bt.k; ++i) max_ng = std::max(max_ng, bt.jb.j[i].ng);
     {
         ProfScope ps(ctx, PCP_K_CROP, st);
-        hipLaunchKernelGGL(k_crop_tile<true>, dim3(std::max(bt.max_nb, 1u), k), dim3(kCT), 0, st,
-                           bt.jb, res);
-        PCP_CHECK_LAUNCH(ctx);
+        if (!fast) {
+            if (bt.max_nb) {
+                hipLaunchKernelGGL(k_crop_tile<false>, dim3(bt.max_nb, k), dim3(kCT), 0, st, bt.jb,
+                                   res);
+                PCP_CHECK_LAUNCH(ctx);
+            }
+            hipLaunchKernelGGL(k_vox_params, dim3(1, k), dim3(kFT), 0, st, bt.jb, res,
+                               res + kMaxClouds);
+            PCP_CHECK_LAUNCH(ctx);
+            if (bt.max_nb) {
+                hipLaunchKernelGGL(k_compact_keys, dim3(bt.max_nb, k), dim3(kFT), 0, st, bt.jb);
+                PCP_CHECK_LAUNCH(ctx);
+            }
+        } else {   // (always launched: it zeroes the chain's counters and result slots)
+            hipLaunchKernelGGL(k_crop_tile<true>, dim3(std::max(bt.max_nb, 1u), k), dim3(kCT), 0,
+                               st, bt.jb, res);
+            PCP_CHECK_LAUNCH(ctx);
+        }
     }
+    if (!fast && bt.max_passes <= 0) return PCP_OK;
     ProfScope ps(ctx, PCP_K_VOXEL, st);
-    hipLaunchKernelGGL(k_hist0, dim3(std::max(max_ng, 1u), k), dim3(kST), 0, st, bt.jb);
-    PCP_CHECK_LAUNCH(ctx);
+    // sort-tile kernels: LDS admits 8192 / kSortTile blocks per CU; the clouds share the CUs
     const unsigned per_cu = (unsigned)std::max(1, 8192 / kSortTile);
     const unsigned cap = per_cu * (unsigned)std::max(ctx->num_cus, 1) / k;
-    const unsigned g0 = std::max(1u, std::min<unsigned>(max_ng, cap));
-    hipLaunchKernelGGL(k_radix_scatter0, dim3(g0, k), dim3(kST), 0, st, bt.jb);
-    PCP_CHECK_LAUNCH(ctx);
     const unsigned gx = std::max(1u, std::min<unsigned>(bt.max_nt, cap));
-    for (int pass = 1; pass < bt.max_passes; ++pass) {
+    if (fast) {
+        hipLaunchKernelGGL(k_hist0, dim3(std::max(max_ng, 1u), k), dim3(kST), 0, st, bt.jb);
+        PCP_CHECK_LAUNCH(ctx);
+        const unsigned g0 = std::max(1u, std::min<unsigned>(max_ng, cap));
+        hipLaunchKernelGGL(k_radix_scatter0, dim3(g0, k), dim3(kST), 0, st, bt.jb);
+        PCP_CHECK_LAUNCH(ctx);
+    }
+    for (int pass = fast ? 1 : 0; pass < bt.max_passes; ++pass) {
         hipLaunchKernelGGL(k_radix_hist, dim3(gx, k), dim3(kST), 0, st, bt.jb, pass);
         PCP_CHECK_LAUNCH(ctx);
         hipLaunchKernelGGL(k_radix_scatter, dim3(gx, k), dim3(kST), 0, st, bt.jb, pass);
@@ -1977,7 +1875,7 @@ static int enqueue_bucket(pcp_ctx *ctx, const Batch &bt, uint32_t *res, hipStrea
         max_ng = std::max(max_ng, bt.jb.j[i].ng);
         nseq += bt.jb.j[i].nbkcap;
     }
-    if (ctx->bk_stat.cap < ((size_t)kBkChunkOff + kBatch * kBkMax / 64) * 8)   // bucket_geometry
+    if (ctx->bk_stat.cap < ((size_t)kBkChunkOff + kBatch * kBkMax / 64) * 8)   // apply_bucket
         return set_err(ctx, PCP_E_STATE, "bucket chain: bucket words not allocated");
     uint2 *bkv = ctx->bk_stat.as<uint2>();
     {
@@ -2010,59 +1908,18 @@ static int enqueue_emit(pcp_ctx *ctx, const Batch &bt, const uint32_t *res, floa
     return PCP_OK;
 }
 
-// every cloud of a one-batch call certainly voxelised: a non-empty input and a finite crop box
-// whose voxel keys fit 31 bits (then PCL's int32 guard cannot fire on the cropped points'
-// smaller bbox) -- the centroid kernel can emit the merged records itself
-static bool emit_in_centroid(const std::vector<Batch> &bts) {
-    if (bts.size() != 1) return false;
-    const Batch &bt = bts[0];
-    for (int i = 0; i < bt.k; ++i) {
-        const CloudJob &J = bt.jb.j[i];
-        if (J.in.n == 0 || !(J.leaf > 0.0f) || J.passes <= 0 ||
-            J.passes * kDigitBits > 31 + kDigitBits - 1)
-            return false;
-        const Box &b = J.box;
-        const double lo[3] = {b.x0, b.y0, b.z0}, hi[3] = {b.x1, b.y1, b.z1};
-        double nv = 1.0;
-        for (int a = 0; a < 3; ++a) {
-            if (!std::isfinite(lo[a]) || !std::isfinite(hi[a])) return false;
-            nv *= std::floor((hi[a] - lo[a]) / (double)J.leaf) + 3.0;
-        }
-        if (!(nv < 2147483647.0)) return false;
-    }
-    return true;
-}
-
-static bool all_bucket(const std::vector<Batch> &bts) {
-    if (bts.size() != 1 || bts[0].k == 0) return false;
-    for (int i = 0; i < bts[0].k; ++i)
-        if (!bts[0].jb.j[i].bk) return false;
-    return true;
-}
-
-static int enqueue_all(pcp_ctx *ctx, const std::vector<Batch> &bts, uint32_t *res,
-                       float4 *emit_out, hipStream_t st) {
-    if (all_bucket(bts)) return enqueue_bucket(ctx, bts[0], res, st, emit_out);
-    if (!emit_out && bts.size() == 1) {   // pcp_crop_voxel's fast chain (run_single)
-        bool fast = bts[0].k > 0;
-        for (int i = 0; i < bts[0].k; ++i) fast = fast && bts[0].jb.j[i].fast;
-        if (fast) return enqueue_fast(ctx, bts[0], res, st, nullptr);
-    }
-    if (emit_out && emit_in_centroid(bts)) {
-        bool fast = true;
-        for (int i = 0; i < bts[0].k; ++i) fast = fast && bts[0].jb.j[i].fast;
-        return fast ? enqueue_fast(ctx, bts[0], res, st, emit_out)
-                    : enqueue_chain(ctx, bts[0], res, st, emit_out);
-    }
-    for (const Batch &bt : bts) {
-        int rc = enqueue_chain(ctx, bt, res, st);
-        if (rc) return rc;
-    }
-    if (emit_out)
-        for (const Batch &bt : bts) {
-            int rc = enqueue_emit(ctx, bt, res, emit_out, st);
-            if (rc) return rc;
-        }
+// one attempt of the plan: its chain over the batches (Bucket, Fast and InChain: one batch, by
+// the plan), the merged records to `out` as its emit mode says
+static int enqueue_all(pcp_ctx *ctx, const FilterAttempt &a, const std::vector<Batch> &bts,
+                       uint32_t *res, float4 *out, hipStream_t st) {
+    float4 *in_chain = a.emit == FilterEmit::InChain ? out : nullptr;
+    if (a.chain == FilterChain::Bucket) return enqueue_bucket(ctx, bts[0], res, st, in_chain);
+    for (const Batch &bt : bts)
+        if (int rc = enqueue_lsd(ctx, bt, res, st, in_chain, a.chain == FilterChain::Fast))
+            return rc;
+    if (a.emit == FilterEmit::Separate)
+        for (const Batch &bt : bts)
+            if (int rc = enqueue_emit(ctx, bt, res, out, st)) return rc;
     return PCP_OK;
 }
 
@@ -2117,21 +1974,76 @@ static int read_results(pcp_ctx *ctx, const uint32_t *res_d, int k, ResultInfo *
     return PCP_OK;
 }
 
-// one host cloud through crop [-> voxel] (slot 0); results stay in ctx->fbuf[0]
-// fast_ok: the caller wants the centroids only (pcp_crop_voxel) -- a finite box then takes the
-// fast chain, whose centroid kernel stores the voxels and the result sizes straight into
-// pinned memory (J.out4 is then HOST memory): one round trip for the call
-static int run_single(pcp_ctx *ctx, const pcp_cloud_view *in, const Box &b, float leaf,
-                      bool want_idx, CloudJob &J, ResultInfo &ri, bool fast_ok = false) {
+// What the attempt loop leaves behind: the attempt whose results stand, its jobs and batches and
+// the result words it wrote (device memory, or pinned: did.sizes_pinned).
+struct FilterRun {
+    FilterAttempt did{};
+    bool capture = false;   // this attempt may run as pcp_filter_merge's captured graph
+    std::vector<CloudJob> jobs;
+    std::vector<Batch> bts;
+    uint32_t *res = nullptr;
+};
+
+// The attempt loop of every entry point, in filter_plan()'s order: the attempt's geometry into
+// the plain jobs, prep (the entry's pinned landing: run.res, the jobs' outputs), launch, the
+// sizes read back; a bucket chain that set its redo flag is counted and the next attempt runs.
+template <class Prep, class Launch>
+static int run_attempts(pcp_ctx *ctx, FilterPlanIn &in, const CallGeo &geo,
+                        const std::vector<CloudJob> &plain, uint32_t *res_dev, Prep prep,
+                        Launch launch, ResultInfo *ri, FilterRun &run) {
+    const int k = (int)plain.size();
+    FilterPlan plan = filter_plan(in);
+    for (int t = 0; t < plan.n; ++t) {
+        run.did = plan.a[t];
+        run.capture = plan.graphable && t == 0;
+        run.jobs = plain;
+        bool ok = true;
+        for (int i = 0; i < k && ok; ++i) {
+            if (run.did.chain == FilterChain::Bucket) {
+                ok = apply_bucket(ctx, i, geo.bucket[i], run.jobs[i]);
+                if (!ok) in.bucket[i] = Geo::AllocFailed;
+            } else if (run.did.chain == FilterChain::Fast) {
+                ok = apply_fast(ctx, i, geo.fast[i], run.jobs[i]);
+                if (!ok) in.fast[i] = Geo::AllocFailed;
+            }
+        }
+        if (!ok) {   // the plan without that chain, at the same position
+            plan = filter_plan(in);
+            --t;
+            continue;
+        }
+        run.res = res_dev;
+        int rc = prep(run);
+        if (rc) return rc;
+        run.bts = batches_of(run.jobs);
+        if ((rc = launch(run))) return rc;
+        uint32_t redo = 0;
+        if ((rc = read_results(ctx, run.res, k, ri, run.did.sizes_pinned, &redo))) return rc;
+        // (only the bucket chain clears and sets the flag: another chain's word is stale)
+        if (run.did.chain != FilterChain::Bucket || !redo) break;
+        prof_count(ctx, PCP_K_VOXEL_REDO);
+    }
+    return PCP_OK;
+}
+
+// one host cloud through crop [-> voxel] (slot 0); results stay in ctx->fbuf[0], or, after an
+// attempt with centroids_pinned (pcp_crop_voxel's centroids alone over a finite box), the
+// centroid kernel stored the voxels and the result sizes straight into pinned memory (J.out4 is
+// then HOST memory): one round trip for the call
+static int run_single(pcp_ctx *ctx, FilterEntry entry, const pcp_cloud_view *in, const Box &b,
+                      float leaf, bool want_idx, bool idx_out, CloudJob &J, ResultInfo &ri,
+                      FilterAttempt &did) {
     VoxParams *vp;
     uint32_t *res;
     int rc = ensure_misc(ctx, vp, res);
     if (rc) return rc;
     if (ctx->fbuf.empty()) ctx->fbuf.resize(1);
     CloudIn c;
-    // a message-sized cloud on the fast chain: read in place from the pinned ring (no DMA)
+    // a message-sized cloud that may take a quick chain: read in place from the pinned ring (no
+    // DMA; the input stays where it was staged until the last attempt)
     const uint64_t in_bytes = in->n * (uint64_t)in->point_step;
-    const bool zc = fast_ok && ctx->zc_in && ctx->fm_fast && in_bytes <= kPinDirectMax;
+    const bool zc = entry != FilterEntry::CropBox && !idx_out && ctx->zc_in && ctx->fm_fast &&
+                    in_bytes <= kPinDirectMax;
     if (zc) {
         if ((rc = stage_cloud(ctx, *in, true, ctx->f_in, 0, c))) return rc;   // fields only
         const HostPiece pc{0, in->data, in_bytes};
@@ -2144,35 +2056,33 @@ static int run_single(pcp_ctx *ctx, const pcp_cloud_view *in, const Box &b, floa
     }
     std::vector<CloudJob> jobs(1);
     if ((rc = make_job(ctx, 0, c, b, leaf, want_idx, Rigid{}, vp, jobs[0]))) return rc;
-    // the bucket chain (PCP_FM_FAST 2), else the LSD fast chain; a bucket chain that set its redo
-    // flag runs again on the LSD chain (the input stays where it was staged until then)
-    for (int mode = ctx->fm_fast; fast_ok && !want_idx && mode > 0; --mode) {
-        CloudJob F = jobs[0];
-        const bool geo = mode == 2 ? bucket_geometry(ctx, 0, F) : fast_geometry(ctx, 0, F);
-        if (!geo) continue;
+    FilterPlanIn pin{};
+    pin.entry = entry;
+    pin.want_idx = want_idx;
+    pin.idx_out = idx_out;
+    CallGeo geo;
+    plan_facts(ctx, jobs, pin, geo);
+    FilterRun run;
+    auto prep = [&](FilterRun &r) {
+        if (!r.did.centroids_pinned) return (int)PCP_OK;
         const uint64_t ncap = c.n ? c.n : 1;
         const size_t res_b = align256(kResWords * sizeof(uint32_t));
         PCP_HIP(ctx, ctx->cv_host.ensure(res_b + (ncap + 1) * sizeof(float4) + (2 * ncap + 8) * 4 + 256));
-        uint32_t *res_h = ctx->cv_host.as<uint32_t>();
+        CloudJob &F = r.jobs[0];
+        r.res = ctx->cv_host.as<uint32_t>();
         F.out4 = reinterpret_cast<float4 *>(ctx->cv_host.as<char>() + res_b);
         F.vidx = reinterpret_cast<uint32_t *>(F.out4 + ncap + 1);
         F.vcnt = F.vidx + ncap + 1;
-        std::vector<CloudJob> fj(1, F);
-        if ((rc = enqueue_all(ctx, batches_of(fj), res_h, nullptr, ctx->stream))) return rc;
-        uint32_t redo = 0;
-        if ((rc = read_results(ctx, res_h, 1, &ri, true, &redo))) return rc;
-        if (mode == 2 && redo) {
-            prof_count(ctx, PCP_K_VOXEL_REDO);
-            continue;
-        }
-        if (zc) pin_release(ctx, ctx->stream);
-        J = F;
-        return PCP_OK;
-    }
-    if ((rc = enqueue_all(ctx, batches_of(jobs), res, nullptr, ctx->stream))) return rc;
+        return (int)PCP_OK;
+    };
+    auto launch = [&](FilterRun &r) {
+        return enqueue_all(ctx, r.did, r.bts, r.res, nullptr, ctx->stream);
+    };
+    if ((rc = run_attempts(ctx, pin, geo, jobs, res, prep, launch, &ri, run))) return rc;
     if (zc) pin_release(ctx, ctx->stream);
-    J = jobs[0];
-    return read_results(ctx, res, 1, &ri);
+    J = run.jobs[0];
+    did = run.did;
+    return PCP_OK;
 }
 
 }  // namespace pcp
@@ -2193,7 +2103,10 @@ int pcp_crop_box(pcp_ctx *ctx, const pcp_cloud_view *in, const double box[6], ui
     const Box b{box[0], box[1], box[2], box[3], box[4], box[5]};
     CloudJob J;
     ResultInfo ri;
-    if ((rc = run_single(ctx, in, b, 0.0f, kept_idx != nullptr, J, ri))) return rc;
+    FilterAttempt did;
+    if ((rc = run_single(ctx, FilterEntry::CropBox, in, b, 0.0f, kept_idx != nullptr, false, J, ri,
+                         did)))
+        return rc;
     *n_kept = ri.m;
     if ((kept_idx || out_xyz16) && ri.m > cap) {
         prof_resolve(ctx);
@@ -2211,14 +2124,14 @@ int pcp_crop_box(pcp_ctx *ctx, const pcp_cloud_view *in, const double box[6], ui
     return PCP_OK;
 }
 
-static int crop_voxel_impl(pcp_ctx *ctx, const pcp_cloud_view *in, const Box &b, float leaf,
-                           float *out_xyz16, uint32_t *voxel_idx, uint32_t *voxel_count,
+static int crop_voxel_impl(pcp_ctx *ctx, FilterEntry entry, const pcp_cloud_view *in,
+                           const Box &b, float leaf, float *out_xyz16, uint32_t *voxel_idx, uint32_t *voxel_count,
                            uint64_t cap, uint64_t *n_out, uint64_t *n_cropped,
                            int32_t *passthrough) {
     CloudJob J;
     ResultInfo ri;
-    const bool fast_ok = voxel_idx == nullptr && voxel_count == nullptr;
-    int rc = run_single(ctx, in, b, leaf, false, J, ri, fast_ok);
+    FilterAttempt did;
+    int rc = run_single(ctx, entry, in, b, leaf, false, voxel_idx || voxel_count, J, ri, did);
     if (rc) return rc;
     const bool vox = leaf > 0.0f && !ri.overflow;
     if (passthrough) *passthrough = (leaf > 0.0f && ri.overflow) ? 1 : 0;
@@ -2229,8 +2142,8 @@ static int crop_voxel_impl(pcp_ctx *ctx, const pcp_cloud_view *in, const Box &b,
         return set_err(ctx, PCP_E_CAPACITY, "voxel output needs %u points, cap %llu", ri.n,
                        (unsigned long long)cap);
     }
-    if (J.fast || J.bk) {   // the fast chains (LSD or bucket) stored the voxels straight into
-                            // pinned memory (synchronised by read_results): a host copy only
+    if (did.centroids_pinned) {   // the chain stored the voxels straight into pinned memory
+                                  // (synchronised by read_results): a host copy only
         if (ri.n) host_copy(ctx, out_xyz16, J.out4, (size_t)ri.n * 16);
         prof_resolve(ctx);
         return PCP_OK;
@@ -2265,8 +2178,8 @@ int pcp_voxel_grid(pcp_ctx *ctx, const pcp_cloud_view *in, float leaf, float *ou
     if (in->n == 0) return PCP_OK;
     // only non-finite points are dropped (VoxelGrid skips !isXYZFinite points)
     const Box all{-INFINITY, INFINITY, -INFINITY, INFINITY, -INFINITY, INFINITY};
-    return crop_voxel_impl(ctx, in, all, leaf, out_xyz16, voxel_idx, voxel_count, cap, n_out,
-                           nullptr, passthrough);
+    return crop_voxel_impl(ctx, FilterEntry::VoxelGrid, in, all, leaf, out_xyz16, voxel_idx,
+                           voxel_count, cap, n_out, nullptr, passthrough);
 }
 
 int pcp_crop_voxel(pcp_ctx *ctx, const pcp_cloud_view *in, const double box[6], float leaf,
@@ -2281,8 +2194,8 @@ int pcp_crop_voxel(pcp_ctx *ctx, const pcp_cloud_view *in, const double box[6], 
     if (n_cropped) *n_cropped = 0;
     if (in->n == 0) return PCP_OK;
     const Box b{box[0], box[1], box[2], box[3], box[4], box[5]};
-    return crop_voxel_impl(ctx, in, b, leaf, out_xyz16, nullptr, nullptr, cap, n_out, n_cropped,
-                           nullptr);
+    return crop_voxel_impl(ctx, FilterEntry::CropVoxel, in, b, leaf, out_xyz16, nullptr, nullptr,
+                           cap, n_out, n_cropped, nullptr);
 }
 
 int pcp_transform_concat(pcp_ctx *ctx, int k, const pcp_cloud_view *clouds, const pcp_rigid *tf,
@@ -2438,38 +2351,30 @@ int pcp_filter_merge(pcp_ctx *ctx, int k, const pcp_cloud_view *clouds, const do
         if ((rc = make_job(ctx, i, c, b, leaf, false, make_rigid(tf[i], rgb + 3 * i), vp, jobs[i])))
             return rc;
     }
-    std::vector<Batch> bts = batches_of(jobs);
-    // the emit needs the sizes first when the output might not fit (device output only)
-    const bool emit_now = !(dev_out && upper > cap);
-    // every cloud certainly voxelises: the fast chain (PCP_FM_FAST=0: the general chain)
-    // (2: the bucket chain, the LSD fast chain when a bucket chain frame has to be redone)
-    const std::vector<CloudJob> plain = jobs;
-    auto lsd_jobs = [&]() {
-        std::vector<CloudJob> fj = plain;
-        bool all = true;
-        for (int i = 0; i < k && all; ++i) all = fast_geometry(ctx, i, fj[i], k);
-        return all ? fj : plain;
-    };
-    bool bucket = false;
-    if (emit_now && ctx->fm_fast && emit_in_centroid(bts)) {
-        std::vector<CloudJob> fj = plain;
-        bucket = ctx->fm_fast == 2;
-        for (int i = 0; i < k && bucket; ++i) bucket = bucket_geometry(ctx, i, fj[i], k);
-        jobs = bucket ? fj : lsd_jobs();
-        bts = batches_of(jobs);
-    }
-    const bool graphable = dev_in && dev_out && emit_now && ctx->use_graphs;
-    // the centroid kernel emits the records itself: no kernel reads the sizes back, so they
-    // are stored straight into pinned memory (no D2H copy per frame; PCP_FM_HOST_OUT)
-    const bool landed = emit_now && ctx->fm_host_out && emit_in_centroid(bts);
-    if (landed) {
+    FilterPlanIn pin{};
+    pin.entry = FilterEntry::FilterMerge;
+    pin.dev_in = dev_in;
+    pin.dev_out = dev_out;
+    pin.over_cap = upper > cap;
+    CallGeo geo;
+    plan_facts(ctx, jobs, pin, geo);
+    FilterRun run;
+    auto prep = [&](FilterRun &r) {
+        if (!r.did.sizes_pinned) return (int)PCP_OK;
         PCP_HIP(ctx, ctx->fm_res_host.ensure(kResWords * sizeof(uint32_t)));
-        res = ctx->fm_res_host.as<uint32_t>();
-    }
-    if (graphable) {
-        std::vector<uint8_t> key = fm_key(k, clouds, boxes, leaf, tf, rgb, out, cap, jobs);
-        key.insert(key.end(), reinterpret_cast<const uint8_t *>(&res),
-                   reinterpret_cast<const uint8_t *>(&res) + sizeof(res));
+        r.res = ctx->fm_res_host.as<uint32_t>();
+        return (int)PCP_OK;
+    };
+    // the first attempt of a device-resident call is captured into a graph and replayed while
+    // everything baked into its nodes stays the same
+    auto launch = [&](FilterRun &r) {
+        if (!r.capture) {
+            ProfScope ps(ctx, PCP_K_FILTER_MERGE);
+            return enqueue_all(ctx, r.did, r.bts, r.res, obuf, ctx->stream);
+        }
+        std::vector<uint8_t> key = fm_key(k, clouds, boxes, leaf, tf, rgb, out, cap, r.jobs);
+        key.insert(key.end(), reinterpret_cast<const uint8_t *>(&r.res),
+                   reinterpret_cast<const uint8_t *>(&r.res) + sizeof(r.res));
         if (!ctx->fm_exec || key != ctx->fm_key) {
             if (ctx->fm_exec) (void)hipGraphExecDestroy(ctx->fm_exec);
             if (ctx->fm_graph) (void)hipGraphDestroy(ctx->fm_graph);
@@ -2478,13 +2383,13 @@ int pcp_filter_merge(pcp_ctx *ctx, int k, const pcp_cloud_view *clouds, const do
             ctx->fm_key.clear();
             PCP_HIP(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
             ctx->capturing = true;
-            rc = enqueue_all(ctx, bts, res, obuf, ctx->stream);
+            const int erc = enqueue_all(ctx, r.did, r.bts, r.res, obuf, ctx->stream);
             ctx->capturing = false;
             hipGraph_t g = nullptr;
             const hipError_t e = hipStreamEndCapture(ctx->stream, &g);
-            if (rc) {
+            if (erc) {
                 if (g) (void)hipGraphDestroy(g);
-                return rc;
+                return erc;
             }
             if (e != hipSuccess) return hip_fail(ctx, e, "hipStreamEndCapture", __FILE__, __LINE__);
             ctx->fm_graph = g;
@@ -2493,24 +2398,10 @@ int pcp_filter_merge(pcp_ctx *ctx, int k, const pcp_cloud_view *clouds, const do
         }
         ProfScope ps(ctx, PCP_K_FILTER_MERGE);
         PCP_HIP(ctx, hipGraphLaunch(ctx->fm_exec, ctx->stream));
-    } else {
-        ProfScope ps(ctx, PCP_K_FILTER_MERGE);
-        rc = enqueue_all(ctx, bts, res, emit_now ? obuf : nullptr, ctx->stream);
-        if (rc) return rc;
-    }
+        return (int)PCP_OK;
+    };
     std::vector<ResultInfo> ri(k);
-    uint32_t redo = 0;
-    if ((rc = read_results(ctx, res, k, ri.data(), landed, &redo))) return rc;
-    if (bucket && redo) {   // a bucket past its LDS capacity: the frame again on the LSD chain
-        prof_count(ctx, PCP_K_VOXEL_REDO);
-        jobs = lsd_jobs();
-        bts = batches_of(jobs);
-        {
-            ProfScope ps(ctx, PCP_K_FILTER_MERGE);
-            if ((rc = enqueue_all(ctx, bts, res, obuf, ctx->stream))) return rc;
-        }
-        if ((rc = read_results(ctx, res, k, ri.data(), landed))) return rc;
-    }
+    if ((rc = run_attempts(ctx, pin, geo, jobs, res, prep, launch, ri.data(), run))) return rc;
     uint64_t total = 0;
     for (int i = 0; i < k; ++i) {
         const uint64_t ni = clouds[i].n ? ri[i].n : 0;
@@ -2523,9 +2414,9 @@ int pcp_filter_merge(pcp_ctx *ctx, int k, const pcp_cloud_view *clouds, const do
         return set_err(ctx, PCP_E_CAPACITY, "pcp_filter_merge: need %llu, cap %llu",
                        (unsigned long long)total, (unsigned long long)cap);
     }
-    if (!emit_now && total)   // deferred until the size was known to fit
-        for (const Batch &bt : bts)
-            if ((rc = enqueue_emit(ctx, bt, res, obuf, ctx->stream))) return rc;
+    if (run.did.emit == FilterEmit::None && total)   // deferred until the size was known to fit
+        for (const Batch &bt : run.bts)
+            if ((rc = enqueue_emit(ctx, bt, run.res, obuf, ctx->stream))) return rc;
     if (!dev_out && total)
         PCP_HIP(ctx, hipMemcpyAsync(out, obuf, total * 32, hipMemcpyDeviceToHost, ctx->stream));
     PCP_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -2604,45 +2495,32 @@ int pcp_filter_merge_nodes(pcp_ctx *ctx, int k, const pcp_cloud_view *clouds,
     uint32_t *res_h = reinterpret_cast<uint32_t *>(land);
     float4 *mrg = reinterpret_cast<float4 *>(land + res_b);
     auto keep = [&](int i) { return reinterpret_cast<float4 *>(land + res_b + mrg_b + koff[i]); };
+    FilterPlanIn pin{};
+    pin.entry = FilterEntry::FilterMergeNodes;
+    CallGeo geo;
+    plan_facts(ctx, jobs, pin, geo);
+    FilterRun run;
+    auto prep = [&](FilterRun &r) {   // the bucket chain's emit writes both outputs
+        if (!r.did.centroids_pinned) return (int)PCP_OK;
+        r.res = res_h;
+        for (int i = 0; i < k; ++i) r.jobs[i].keep16 = keep(i);
+        return (int)PCP_OK;
+    };
+    auto launch = [&](FilterRun &r) {
+        ProfScope ps(ctx, PCP_K_FILTER_MERGE);
+        return enqueue_all(ctx, r.did, r.bts, r.res, mrg, ctx->stream);
+    };
     std::vector<ResultInfo> ri(k);
-    bool done = false;
-    // the bucket chain with the emit writing both outputs (every cloud certainly voxelises)
-    std::vector<Batch> bts = batches_of(jobs);
-    if (ctx->fm_fast == 2 && emit_in_centroid(bts)) {
-        std::vector<CloudJob> fj = jobs;
-        bool bucket = true;
-        for (int i = 0; i < k && bucket; ++i) bucket = bucket_geometry(ctx, i, fj[i], k);
-        if (bucket) {
-            for (int i = 0; i < k; ++i) fj[i].keep16 = keep(i);
-            {
-                ProfScope ps(ctx, PCP_K_FILTER_MERGE);
-                if ((rc = enqueue_all(ctx, batches_of(fj), res_h, mrg, ctx->stream))) return rc;
-            }
-            uint32_t redo = 0;
-            if ((rc = read_results(ctx, res_h, k, ri.data(), true, &redo))) return rc;
-            if (redo) prof_count(ctx, PCP_K_VOXEL_REDO);
-            done = !redo;
-        }
-    }
-    if (!done) {   // the general chain: each cloud's result, then the transform + concat
-        std::vector<CloudJob> gj = jobs;
-        for (int i = 0; i < k; ++i) gj[i].bk = 0;
-        bts = batches_of(gj);
-        {
-            ProfScope ps(ctx, PCP_K_FILTER_MERGE);
-            for (const Batch &bt : bts)
-                if ((rc = enqueue_chain(ctx, bt, res, ctx->stream))) return rc;
-            for (const Batch &bt : bts)
-                if ((rc = enqueue_emit(ctx, bt, res, mrg, ctx->stream))) return rc;
-        }
-        if ((rc = read_results(ctx, res, k, ri.data()))) return rc;
+    if ((rc = run_attempts(ctx, pin, geo, jobs, res, prep, launch, ri.data(), run))) return rc;
+    if (!run.did.centroids_pinned) {
         // each cloud's result (centroids, or the cropped points of a passthrough cloud) down
         for (int i = 0; i < k; ++i) {
             if (!ri[i].n) continue;
+            const CloudJob &G = run.jobs[i];
             VoxParams v;
-            PCP_HIP(ctx, hipMemcpyAsync(&v, gj[i].vp, sizeof(v), hipMemcpyDeviceToHost, ctx->stream));
+            PCP_HIP(ctx, hipMemcpyAsync(&v, G.vp, sizeof(v), hipMemcpyDeviceToHost, ctx->stream));
             PCP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            const float4 *src = (v.do_voxel && !v.overflow) ? gj[i].out4 : gj[i].xyz;
+            const float4 *src = (v.do_voxel && !v.overflow) ? G.out4 : G.xyz;
             PCP_HIP(ctx, hipMemcpyAsync(keep(i), src, (size_t)ri[i].n * 16, hipMemcpyDeviceToHost,
                                         ctx->stream));
         }

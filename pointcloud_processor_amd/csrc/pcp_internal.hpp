@@ -386,8 +386,8 @@ struct pcp_ctx {
                                              // (PCP_FAN_ORDER; 0: in ring order)
     bool fan_host_out = true;                // k_fan_reduce stores into the pinned landing
                                              // block, no D2H copy (PCP_FAN_HOST_OUT)
-    int fm_fast = 2;                         // pcp_filter_merge's voxel chain (PCP_FM_FAST): 2 the
-                                             // bucket chain, 1 the LSD fast chain, 0 the general one
+    int fm_fast = 2;                         // the filter's voxel chain (PCP_FM_FAST, filter_plan()): 2
+                                             // the bucket chain, 1 the LSD fast chain, 0 the general one
     pcp::DevBuf bk_stat;                     // the bucket chain's per-bucket words
     int bk_gt = 0;                           // crop tiles per k_bk_group group (PCP_BK_GT; 0: one
                                              // round of blocks)
