@@ -23,6 +23,7 @@
 
 #include <rocprim/device/device_radix_sort.hpp>
 
+#include "pcp_fan_clear.hpp"
 #include "pcp_grid.hpp"
 #include "pcp_internal.hpp"
 
@@ -226,6 +227,66 @@ k_frec(float4 *__restrict__ wpts, const uint32_t *__restrict__ cstart, CellMap m
     }
 }
 
+// Clearance codes of the empty split records (pcp_fan_clear.hpp, DESIGN.md §5 Skip 5), three
+// passes.  lev[w]: the lowest level at which fine cell w's lowest point counts (preset to
+// 0xFFFFFFFF: no point), one atomicMin per point.
+__global__ void __launch_bounds__(kThreads)
+k_clear_level(const float4 *__restrict__ pts, uint32_t n, FineGeo f, ClearGeo cg, int rz,
+              uint32_t *__restrict__ lev) {
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n) return;
+    const float4 p = pts[i];
+    int cx, cy;
+    fine_cell(f, p.x, p.y, cx, cy);
+    atomicMin(&lev[(uint32_t)cx + (uint32_t)f.fnx * (uint32_t)cy],
+              (uint32_t)fan_clear_level(cg, (double)p.z, rz));
+}
+
+// h[iz][w]: cells along y to the column's nearest cell occupied at level iz (lev <= iz), capped
+// at 256.  One thread per cell for all its levels: the levels nest (a cell occupied at iz is
+// occupied above it), so one walk outwards with the running minimum m of lev settles, at
+// distance d, the levels [m, top) not settled nearer; it ends when level 0 is settled.
+__global__ void __launch_bounds__(kThreads)
+k_clear_col(const uint32_t *__restrict__ lev, int fnx, int fny, uint32_t nw, uint32_t rz,
+            uint16_t *__restrict__ h) {
+    const uint32_t w = blockIdx.x * kThreads + threadIdx.x;
+    if (w >= nw) return;
+    const int x = (int)(w % (uint32_t)fnx), y = (int)(w / (uint32_t)fnx);
+    uint32_t top = rz;   // the levels below top are not settled yet
+    for (int d = 0; d <= kClearMax && top > 0u; ++d) {
+        const int ya = y - d, yb = y + d;
+        const uint32_t la = ya >= 0 ? lev[(size_t)ya * fnx + x] : 0xFFFFFFFFu;
+        const uint32_t lb = yb < fny ? lev[(size_t)yb * fnx + x] : 0xFFFFFFFFu;
+        const uint32_t m = min(la, lb);
+        for (uint32_t iz = m; iz < top; ++iz) h[(size_t)iz * nw + w] = (uint16_t)d;
+        top = min(top, m);
+    }
+    for (uint32_t iz = 0; iz < top; ++iz) h[(size_t)iz * nw + w] = (uint16_t)(kClearMax + 1);
+}
+
+// D = min over dx of max(h(x + dx), |dx|), the Chebyshev distance in cells to the nearest
+// occupied cell, into the high byte of (w, iz)'s record when that record is empty.  The grid's
+// outermost cells and levels keep 0 (fan_clear_border: what a clamped probe reads).
+__global__ void __launch_bounds__(kThreads)
+k_clear_code(const uint16_t *__restrict__ h, int fnx, int fny, uint32_t nw, uint32_t tx,
+             size_t plane, uint16_t *__restrict__ fband) {
+    const uint32_t w = blockIdx.x * kThreads + threadIdx.x, iz = blockIdx.y;
+    if (w >= nw) return;
+    const uint32_t wx = w % (uint32_t)fnx, wy = w / (uint32_t)fnx;
+    if (fan_clear_border(wx, wy, iz, (uint32_t)fnx, (uint32_t)fny, gridDim.y)) return;
+    const size_t r = (size_t)iz * plane + (((size_t)((wy >> 3) * tx + (wx >> 3)) << 6) |
+                                           ((wy & 7u) << 3) | (wx & 7u));
+    if (fband[r] != 0x00FFu) return;
+    const uint16_t *row = h + (size_t)iz * nw + (size_t)wy * fnx;
+    int D = (int)row[wx];
+    for (int d = 1; d < D; ++d) {
+        const int xa = (int)wx - d, xb = (int)wx + d;
+        if (xa >= 0) D = min(D, max((int)row[xa], d));
+        if (xb < fnx) D = min(D, max((int)row[xb], d));
+    }
+    fband[r] = (uint16_t)(0x00FFu | (fan_clear_code((uint32_t)D) << 8));
+}
+
 // the fine-window entries packed to 12 bytes (x, y, z): a quarter less working set for the walks
 __global__ void __launch_bounds__(kThreads)
 k_pack3(const float4 *__restrict__ src, uint32_t n, float *__restrict__ dst) {
@@ -355,6 +416,28 @@ int build_fine(pcp_ctx *ctx, GridIndex &g) {
                        g.frec.as<uint16_t>(),
                        reinterpret_cast<uint32_t *>(g.frec.as<char>() + band_bytes));
     PCP_CHECK_LAUNCH(ctx);
+    if (tile == 2) {
+        // clearance codes into the empty records (their high byte; the table does not grow)
+        const size_t lev_bytes = ((size_t)nw * 4 + 255) & ~(size_t)255;
+        PCP_HIP(ctx, ctx->scratch[5].ensure(lev_bytes + (size_t)nw * rz * 2 + 64));
+        uint32_t *lev = ctx->scratch[5].as<uint32_t>();
+        uint16_t *hcol = reinterpret_cast<uint16_t *>(ctx->scratch[5].as<char>() + lev_bytes);
+        const double zabs = std::fmax(std::fabs(gv.oz), std::fabs(gv.oz + (double)g.nz * g.c));
+        const ClearGeo cg = fan_clear_geo(gv.oz, g.c, R, zabs);
+        PCP_HIP(ctx, hipMemsetAsync(lev, 0xFF, (size_t)nw * 4, st));
+        hipLaunchKernelGGL(k_clear_level, dim3(gridn), dim3(kThreads), 0, st, pts, n, f, cg,
+                           (int)rz, lev);
+        PCP_CHECK_LAUNCH(ctx);
+        const dim3 cgrid((unsigned)((nw + kThreads - 1) / kThreads), (unsigned)rz);
+        hipLaunchKernelGGL(k_clear_col, dim3(cgrid.x), dim3(kThreads), 0, st,
+                           (const uint32_t *)lev, (int)fnx, (int)fny, (uint32_t)nw, (uint32_t)rz,
+                           hcol);
+        PCP_CHECK_LAUNCH(ctx);
+        hipLaunchKernelGGL(k_clear_code, cgrid, dim3(kThreads), 0, st, (const uint16_t *)hcol,
+                           (int)fnx, (int)fny, (uint32_t)nw, (uint32_t)((fnx + 7) / 8), (size_t)(nrec / rz),
+                           g.frec.as<uint16_t>());
+        PCP_CHECK_LAUNCH(ctx);
+    }
     if (pack) {
         hipLaunchKernelGGL(k_pack3, dim3((unsigned)((nent + kThreads - 1) / kThreads)),
                            dim3(kThreads), 0, st, (const float4 *)went, (uint32_t)nent,

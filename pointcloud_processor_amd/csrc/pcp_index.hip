@@ -76,6 +76,9 @@ GridView GridIndex::view() const {
                    : nullptr;
     v.fus_off = (float)(rm * v.inv_c / (double)kZq);
     v.fskip = fine_ok ? fskip : 1;
+    v.fclear = (fine_ok && ftile == 2 && fan_clear) ? 1 : 0;
+    v.fclr_cf = fine_ok ? (float)(c / (double)ffine) : 0.0f;
+    v.fclr_rb = std::nextafter((float)rb, INFINITY);
     return v;
 }
 

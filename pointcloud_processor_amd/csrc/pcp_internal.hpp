@@ -150,6 +150,11 @@ struct GridView {               // POD passed to kernels by value
     int32_t fskip;
     float fzc, fzo;             // c and oz in float (the skip test)
     int32_t wpack;              // wpts entries packed to 12 bytes (x, y, z), PCP_FINE_PACK
+    // ftile 2: an empty record's high byte is its clearance code (pcp_fan_clear.hpp, DESIGN.md
+    // §5 Skip 5); fclear = 0 (PCP_FAN_CLEAR=0, or no split records) leaves the march as it was.
+    // fclr_cf = c / F, fclr_rb = r + m + 1e-6 max|coord| (rounded up)
+    int32_t fclear;
+    float fclr_cf, fclr_rb;
 };
 constexpr float kZq = 2.0f / 250.0f;   // z band step, cells (2 cells = 250 steps)
 
@@ -172,6 +177,8 @@ struct GridIndex {
     float ffine = 0.0f;
     int32_t ftile = 0;
     int32_t fskip = 1;           // walk-start skip thresholds (PCP_FINE_SKIP)
+    bool fan_clear = true;       // the march jumps by the empty records' clearance codes
+                                 // (PCP_FAN_CLEAR, set once by pcp_create; release() keeps it)
     size_t fstart_off = 0;       // ftile 2: byte offset of the start array inside frec
     bool occ2_ok = false;        // occ2 built (only indices queried by stencil_any need it)
     GridView view() const;
