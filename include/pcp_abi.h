@@ -620,6 +620,36 @@ int pcp_step_table(double end, double *steps, uint64_t cap, uint64_t *n);
  * run as one look-back pass (PCP_SCAN_ONEPASS, default 1), others as three launches. */
 int pcp_debug_exclusive_scan(pcp_ctx *ctx, const uint32_t *in, uint64_t n, uint32_t *out);
 
+/* Test infrastructure: the terrain's fine-window copy read back exactly as
+ * it lies on the device, with every value its build kernels received as a parameter.  Two calls,
+ * as elsewhere: with frec, wpts and pts all NULL it fills *geo only (the byte sizes among it);
+ * with buffers (each nullable, caps in bytes) it also copies
+ *   frec  the record buffer, frec_bytes: tiles, padding records and the split arrays as built
+ *         (tile 2: uint16 thresholds, then at start_off the uint32 walk starts; else 8-byte
+ *         {start, thresholds} records);
+ *   wpts  the entry buffer, wpts_bytes: n_entries entries of 12 (packed: x, y, z) or 16 bytes;
+ *   pts   the index's point array, pts_bytes: n_points float4 (x, y, z, original index bits),
+ * PCP_E_CAPACITY when a cap is short.  Nothing is de-tiled or unpacked.  geo->built = 0 with
+ * PCP_OK when the copy is not built (no terrain, no query yet, or past its caps): the call never
+ * builds it, launches nothing, and synchronises the context's stream before its plain copies. */
+typedef struct pcp_fine_geo {
+    int32_t built;              /* 0: no fine copy; every other field 0 */
+    int32_t tile;               /* 0 x-fastest, 1 4 x 4 tiles, 2 split records in 8 x 8 tiles */
+    int32_t skip;               /* skip thresholds of the split records' walk start: 1 or 2 */
+    int32_t packed;             /* entries of 12 bytes */
+    int32_t nx, ny, nz;         /* coarse cells */
+    int32_t F, reach, fnx, fny, rz, tsteps;
+    uint64_t n_points, n_records, n_entries;
+    uint64_t start_off;         /* tile 2: byte offset of the walk-start array in frec */
+    uint64_t frec_bytes, wpts_bytes, pts_bytes;
+    double ox, oy, oz, c, inv_c, r_q;
+    double cf, inv_cf, R2;
+    double zq;                  /* threshold step in cells (the float constant, widened) */
+    double clear_zt0, clear_c;  /* clearance levels: Zt(iz) = clear_zt0 + iz clear_c */
+} pcp_fine_geo;
+int pcp_debug_fine_copy(pcp_ctx *ctx, pcp_fine_geo *geo, void *frec, uint64_t frec_cap,
+                        void *wpts, uint64_t wpts_cap, void *pts, uint64_t pts_cap);
+
 /* diagnostics of the terrain index (cell edge, dims, points) */
 typedef struct pcp_index_info {
     uint64_t n_points;

@@ -106,6 +106,16 @@ class IndexInfo(C.Structure):
                 ("bmax", C.c_double * 3), ("scan_layout", C.c_int32), ("fine_tile", C.c_int32)]
 
 
+class FineGeo(C.Structure):
+    """pcp_fine_geo: the fine-window copy's geometry (pcp_debug_fine_copy)."""
+    _fields_ = ([(k, C.c_int32) for k in ("built", "tile", "skip", "packed", "nx", "ny", "nz", "F",
+                                          "reach", "fnx", "fny", "rz", "tsteps")] +
+                [(k, C.c_uint64) for k in ("n_points", "n_records", "n_entries", "start_off",
+                                           "frec_bytes", "wpts_bytes", "pts_bytes")] +
+                [(k, C.c_double) for k in ("ox", "oy", "oz", "c", "inv_c", "r_q", "cf", "inv_cf",
+                                           "R2", "zq", "clear_zt0", "clear_c")])
+
+
 class RuntimeInfo(C.Structure):
     _fields_ = [("hip_runtime_version", C.c_int32), ("rccl_version", C.c_int32),
                 ("hip_path", C.c_char * 512), ("rccl_path", C.c_char * 512)]
@@ -197,6 +207,8 @@ _SIGS = [
     ("pcp_simulate_scan_burst", C.c_int, [_P, _P, C.c_uint64, C.POINTER(FanParams), C.c_int,
                                           _P]),
     ("pcp_debug_exclusive_scan", C.c_int, [_P, _P, C.c_uint64, _P]),
+    ("pcp_debug_fine_copy", C.c_int, [_P, C.POINTER(FineGeo), _P, C.c_uint64, _P, C.c_uint64, _P,
+                                      C.c_uint64]),
     ("pcp_score_poses_burst", C.c_int, [_P, _P, C.c_uint64, _P, C.POINTER(VlParams), C.c_int,
                                         C.POINTER(C.c_double)]),
     ("pcp_stream_create", C.c_int, [_P, C.POINTER(_P)]),
@@ -873,6 +885,24 @@ class Context:
         self._check(self.lib.pcp_debug_exclusive_scan(self.h, _ptr(a), a.size, _ptr(out)),
                     "pcp_debug_exclusive_scan")
         return out
+
+    def debug_fine_copy(self):
+        """pcp_debug_fine_copy: the terrain's fine-window copy as built -> (geo dict, frec uint8,
+        wpts uint8, pts float32 (n, 4)), raw device bytes; the arrays are None and geo["built"]
+        is 0 when the copy is not built."""
+        geo = FineGeo()
+        self._check(self.lib.pcp_debug_fine_copy(self.h, C.byref(geo), None, 0, None, 0, None, 0),
+                    "pcp_debug_fine_copy")
+        d = {k: getattr(geo, k) for k, _ in geo._fields_}
+        if not geo.built:
+            return d, None, None, None
+        frec = np.zeros(geo.frec_bytes, np.uint8)
+        wpts = np.zeros(geo.wpts_bytes, np.uint8)
+        pts = np.zeros((geo.n_points, 4), np.float32)
+        self._check(self.lib.pcp_debug_fine_copy(self.h, C.byref(geo), _ptr(frec), frec.nbytes,
+                                                 _ptr(wpts), wpts.nbytes, _ptr(pts), pts.nbytes),
+                    "pcp_debug_fine_copy")
+        return d, frec, wpts, pts
 
     def score_matrix(self, poses5, zx120_pose5, params: VlParams):
         """pcp_score_matrix -> (score_mobile [P, C], score_zx120 [C]): evaluateCellScore per

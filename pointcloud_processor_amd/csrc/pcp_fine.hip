@@ -298,39 +298,66 @@ k_pack3(const float4 *__restrict__ src, uint32_t n, float *__restrict__ dst) {
     dst[3 * (size_t)i + 2] = p.z;
 }
 
+// Everything the build's kernels receive as a parameter, from the index and the knobs alone (the
+// read-back, pcp_debug_fine_copy, reports the same values for a built copy).
+struct FinePlan {
+    CellMap m;
+    FineGeo f;
+    ClearGeo cg;
+    int F, tile;
+    uint64_t fnx, fny, rz, nw, nrec;
+    size_t band_bytes, rec_bytes;
+    uint32_t tsteps;
+};
+
+FinePlan fine_plan(const GridIndex &g, int F, int tile) {
+    FinePlan p{};
+    const GridView gv = g.view();
+    p.m = CellMap{gv.ox, gv.oy, gv.oz, gv.inv_c, g.nx, g.ny, g.nz};
+    p.F = F;
+    p.tile = tile;
+    p.fnx = (uint64_t)F * g.nx;
+    p.fny = (uint64_t)F * g.ny;
+    p.rz = (uint64_t)(g.nz > 1 ? g.nz - 1 : 0);
+    const uint64_t T = tile == 2 ? 8 : 4;
+    p.nrec = tile ? ((p.fnx + T - 1) / T) * ((p.fny + T - 1) / T) * T * T * p.rz
+                  : p.fnx * p.fny * p.rz;
+    p.nw = p.fnx * p.fny;   // windows (the runs)
+    p.band_bytes = ((size_t)p.nrec * 2 + 255) & ~(size_t)255;
+    p.rec_bytes = tile == 2 ? p.band_bytes + (size_t)p.nrec * 4 : (size_t)p.nrec * sizeof(uint2);
+    p.f.ox = gv.ox;
+    p.f.oy = gv.oy;
+    p.f.cf = g.c / F;
+    p.f.inv_cf = F * gv.inv_c;
+    const double R = g.r_q + kQueryMargin;
+    p.f.R2 = R * R;
+    p.f.fnx = (int32_t)p.fnx;
+    p.f.fny = (int32_t)p.fny;
+    p.f.reach = (int32_t)std::ceil(R / p.f.cf);
+    p.tsteps = (uint32_t)std::ceil((g.r_q + 2e-3) / g.c / (double)kZq);
+    const double zabs = std::fmax(std::fabs(gv.oz), std::fabs(gv.oz + (double)g.nz * g.c));
+    p.cg = fan_clear_geo(gv.oz, g.c, R, zabs);
+    return p;
+}
+
 }  // namespace
 
 int build_fine(pcp_ctx *ctx, GridIndex &g) {
     if (g.fine_ok || g.fine_fail || !g.present || !g.occz_ok || g.n_pts == 0) return PCP_OK;
     hipStream_t st = ctx->stream;
     ProfScope prof(ctx, PCP_K_INDEX_BUILD);
-    const GridView gv = g.view();
-    const CellMap m{gv.ox, gv.oy, gv.oz, gv.inv_c, g.nx, g.ny, g.nz};
-    const int F = std::max(2, std::min(ctx->terrain_fine, 8));
-    const uint64_t fnx = (uint64_t)F * g.nx, fny = (uint64_t)F * g.ny;
-    const uint64_t rz = (uint64_t)(g.nz > 1 ? g.nz - 1 : 0);
+    const FinePlan plan = fine_plan(g, std::max(2, std::min(ctx->terrain_fine, 8)),
+                                    ctx->fine_tile == 2 ? 2 : ctx->fine_tile ? 1 : 0);
+    const CellMap m = plan.m;
+    const FineGeo f = plan.f;
+    const int F = plan.F, tile = plan.tile;
+    const uint64_t fnx = plan.fnx, fny = plan.fny, rz = plan.rz, nrec = plan.nrec, nw = plan.nw;
+    const size_t band_bytes = plan.band_bytes, rec_bytes = plan.rec_bytes;
     // caps: 32-bit record byte offsets (< 2^29 records), 24-bit probe multiplies, window keys
-    const int tile = ctx->fine_tile == 2 ? 2 : ctx->fine_tile ? 1 : 0;
-    const uint64_t T = tile == 2 ? 8 : 4;
-    const uint64_t nrec = tile ? ((fnx + T - 1) / T) * ((fny + T - 1) / T) * T * T * rz
-                               : fnx * fny * rz;
-    const uint64_t nw = fnx * fny;   // windows (the runs)
-    const size_t band_bytes = ((size_t)nrec * 2 + 255) & ~(size_t)255;
-    const size_t rec_bytes = tile == 2 ? band_bytes + (size_t)nrec * 4 : (size_t)nrec * sizeof(uint2);
     if (rz == 0 || nrec >= (1ull << 29) || fnx >= (1ull << 24) || fny * rz >= (1ull << 24)) {
         g.fine_fail = true;
         return PCP_OK;
     }
-    FineGeo f{};
-    f.ox = gv.ox;
-    f.oy = gv.oy;
-    f.cf = g.c / F;
-    f.inv_cf = F * gv.inv_c;
-    const double R = g.r_q + kQueryMargin;
-    f.R2 = R * R;
-    f.fnx = (int32_t)fnx;
-    f.fny = (int32_t)fny;
-    f.reach = (int32_t)std::ceil(R / f.cf);
     const uint32_t n = (uint32_t)g.n_pts;
     const unsigned gridn = (n + kThreads - 1) / kThreads;
     const float4 *pts = g.pts.as<const float4>();
@@ -407,7 +434,7 @@ int build_fine(pcp_ctx *ctx, GridIndex &g) {
     // 5. records (and the sentinels), one thread per window; two skip thresholds need a 25-bit
     // walk start
     const bool skip2 = tile == 2 && ctx->fine_skip == 2 && nent < (1ull << 25);
-    const uint32_t tsteps = (uint32_t)std::ceil((g.r_q + 2e-3) / g.c / (double)kZq);
+    const uint32_t tsteps = plan.tsteps;
     const uint64_t nthr = std::max<uint64_t>(nw, tile ? nrec / rz : 0);
     hipLaunchKernelGGL(k_frec, dim3((unsigned)((nthr + kThreads - 1) / kThreads)), dim3(kThreads), 0,
                        st, went, (const uint32_t *)cstart, m, g.c, (uint32_t)fnx,
@@ -422,8 +449,7 @@ int build_fine(pcp_ctx *ctx, GridIndex &g) {
         PCP_HIP(ctx, ctx->scratch[5].ensure(lev_bytes + (size_t)nw * rz * 2 + 64));
         uint32_t *lev = ctx->scratch[5].as<uint32_t>();
         uint16_t *hcol = reinterpret_cast<uint16_t *>(ctx->scratch[5].as<char>() + lev_bytes);
-        const double zabs = std::fmax(std::fabs(gv.oz), std::fabs(gv.oz + (double)g.nz * g.c));
-        const ClearGeo cg = fan_clear_geo(gv.oz, g.c, R, zabs);
+        const ClearGeo cg = plan.cg;
         PCP_HIP(ctx, hipMemsetAsync(lev, 0xFF, (size_t)nw * 4, st));
         hipLaunchKernelGGL(k_clear_level, dim3(gridn), dim3(kThreads), 0, st, pts, n, f, cg,
                            (int)rz, lev);
@@ -452,8 +478,65 @@ int build_fine(pcp_ctx *ctx, GridIndex &g) {
     g.ftile = tile;
     g.fskip = skip2 ? 2 : 1;
     g.fstart_off = tile == 2 ? band_bytes : 0;
+    g.fnent = nent;
     g.fine_ok = true;
     return PCP_OK;
 }
 
 }  // namespace pcp
+
+// Test infrastructure (tests/test_fine_copy_gpu.py): the terrain's built fine copy as it lies on
+// the device, with every parameter its build kernels received.  No launch and no build: the
+// stream is drained, then plain copies.
+extern "C" int pcp_debug_fine_copy(pcp_ctx *ctx, pcp_fine_geo *geo, void *frec,
+                                   uint64_t frec_cap, void *wpts, uint64_t wpts_cap, void *pts,
+                                   uint64_t pts_cap) {
+    using namespace pcp;
+    if (!ctx || !geo) return PCP_E_INVALID;
+    const GridIndex &g = ctx->terrain;
+    *geo = pcp_fine_geo{};
+    if (!g.present || !g.fine_ok) return PCP_OK;   // built = 0
+    const FinePlan p = fine_plan(g, (int)g.ffine, g.ftile);
+    geo->built = 1;
+    geo->tile = g.ftile;
+    geo->skip = g.fskip;
+    geo->packed = g.wpack;
+    geo->nx = g.nx;
+    geo->ny = g.ny;
+    geo->nz = g.nz;
+    geo->F = p.F;
+    geo->reach = p.f.reach;
+    geo->fnx = p.f.fnx;
+    geo->fny = p.f.fny;
+    geo->rz = (int32_t)p.rz;
+    geo->tsteps = (int32_t)p.tsteps;
+    geo->n_points = g.n_pts;
+    geo->n_records = p.nrec;
+    geo->n_entries = g.fnent;
+    geo->start_off = g.fstart_off;
+    geo->frec_bytes = p.rec_bytes;
+    geo->wpts_bytes = g.fnent * (g.wpack ? 12u : 16u);
+    geo->pts_bytes = g.n_pts * sizeof(float4);
+    geo->ox = p.m.ox;
+    geo->oy = p.m.oy;
+    geo->oz = p.m.oz;
+    geo->c = g.c;
+    geo->inv_c = p.m.inv_c;
+    geo->r_q = g.r_q;
+    geo->cf = p.f.cf;
+    geo->inv_cf = p.f.inv_cf;
+    geo->R2 = p.f.R2;
+    geo->zq = (double)kZq;
+    geo->clear_zt0 = p.cg.zt0;
+    geo->clear_c = p.cg.c;
+    if (!frec && !wpts && !pts) return PCP_OK;     // the sizes only
+    if ((frec && frec_cap < geo->frec_bytes) || (wpts && wpts_cap < geo->wpts_bytes) ||
+        (pts && pts_cap < geo->pts_bytes))
+        return set_err(ctx, PCP_E_CAPACITY, "pcp_debug_fine_copy: a buffer is too small");
+    PCP_HIP(ctx, hipSetDevice(ctx->device));
+    PCP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (frec) PCP_HIP(ctx, hipMemcpy(frec, g.frec.p, geo->frec_bytes, hipMemcpyDeviceToHost));
+    if (wpts) PCP_HIP(ctx, hipMemcpy(wpts, g.wpts.p, geo->wpts_bytes, hipMemcpyDeviceToHost));
+    if (pts) PCP_HIP(ctx, hipMemcpy(pts, g.pts.p, geo->pts_bytes, hipMemcpyDeviceToHost));
+    return PCP_OK;
+}

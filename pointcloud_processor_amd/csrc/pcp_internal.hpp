@@ -180,6 +180,7 @@ struct GridIndex {
     bool fan_clear = true;       // the march jumps by the empty records' clearance codes
                                  // (PCP_FAN_CLEAR, set once by pcp_create; release() keeps it)
     size_t fstart_off = 0;       // ftile 2: byte offset of the start array inside frec
+    uint64_t fnent = 0;          // entries of wpts, sentinels included (pcp_debug_fine_copy)
     bool occ2_ok = false;        // occ2 built (only indices queried by stencil_any need it)
     GridView view() const;
     void release() {

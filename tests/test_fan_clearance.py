@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+import fine_ref
 from pointcloud_processor_amd import _abi, synth
 
 pytestmark = pytest.mark.gpu
@@ -52,6 +53,7 @@ def _run(oracle, terrain, poses, fan, stats=False):
             b2, u2, _, _ = ctx.raycast_fan(poses, fan)   # (the benchmark's call: no first hits)
             if stats:
                 counters[clear] = ctx.raycast_fan_stats(poses, fan)
+                counters["copy" + clear] = ctx.debug_fine_copy()
         finally:
             ctx.close()
         np.testing.assert_array_equal(fh, rfh, err_msg=f"PCP_FAN_CLEAR={clear}")
@@ -100,6 +102,14 @@ def test_standard(oracle, small_scene):
     assert st["1"]["samples_visited"] < st["0"]["samples_visited"]
     assert st["1"]["scanned_stencils"] == st["0"]["scanned_stencils"]
     assert st["1"]["point_tests"] == st["0"]["point_tests"]
+    # the knob changes the march alone: both contexts built the same copy, byte for byte, and
+    # the jump had codes to read -- a share of the empty interior records carries one
+    (g1, frec1, wpts1, _), (g0, frec0, wpts0, _) = st["copy1"], st["copy0"]
+    assert g1 == g0 and g1["built"] == 1 and g1["tile"] == 2
+    assert np.array_equal(frec1, frec0) and np.array_equal(wpts1, wpts0)
+    f = fine_ref.features(g1, frec1)
+    assert f["empty_interior"] > 0 and f["code_ge1"] / f["empty_interior"] > 0.0
+    assert f["code_ge2"] > 0
 
 
 def test_one_pose_per_wave(oracle, small_scene):
