@@ -423,7 +423,10 @@ int pcp_raycast_fan(pcp_ctx *ctx, const double *poses5, uint64_t n, const pcp_fa
 /* Diagnostic build of the same march (not for timing): stats[0] = samples probed after the
  * exact clip, stats[1] = samples whose 2x2x2 stencil survives the z-band probe and is scanned,
  * stats[2] = point records loaded (12 B each), stats[3] = block directory entries loaded.
- * Used to state the roofline's requested bytes. */
+ * Over the split fine records stats[1] counts the walk starts actually loaded (a candidate that
+ * its window's pivot settles loads none, DESIGN.md section 5 Skip 6) and stats[2] every exact
+ * point test, the pivot tests included: stats[0] + stats[1] + stats[2] is the launch's gather
+ * lane-load count.  Used to state the roofline's requested bytes. */
 int pcp_raycast_fan_stats(pcp_ctx *ctx, const double *poses5, uint64_t n,
                           const pcp_fan_params *fan, uint64_t stats[4]);
 
@@ -650,11 +653,36 @@ typedef struct pcp_fine_geo {
 int pcp_debug_fine_copy(pcp_ctx *ctx, pcp_fine_geo *geo, void *frec, uint64_t frec_cap,
                         void *wpts, uint64_t wpts_cap, void *pts, uint64_t pts_cap);
 
+/* Test infrastructure: the pivot table of the fine-window copy (Skip 6) read
+ * back as it lies on the device: one 12-byte (x, y, z) float record per slot of the padded
+ * plane of tx x ty tiles of 8 x 8 fine cells, slot of cell (wx, wy) =
+ * ((wy / 8) tx + wx / 8) 64 + (wy % 8) 8 + wx % 8.  A cell's record is the point of its window
+ * nearest the cell's centre (ox + (wx + 0.5) cf, oy + (wy + 0.5) cf) in xy; an empty window and
+ * every padding slot hold (NaN, NaN, -inf).  Two calls as pcp_debug_fine_copy: piv NULL fills
+ * *geo only; with a buffer (cap in bytes, PCP_E_CAPACITY when short) it copies the table.
+ * geo->built = 0 with PCP_OK when there is no table (no fine copy, or one without split
+ * records).  The table does not depend on PCP_FAN_PIVOT (geo->enabled reports the knob).  The
+ * call never builds, launches nothing, and synchronises the context's stream before its copy;
+ * pcp_debug_fine_copy's output is what it was. */
+typedef struct pcp_fine_pivot_geo {
+    int32_t built;              /* 0: no table; every other field 0 */
+    int32_t enabled;            /* the fan march reads the table (PCP_FAN_PIVOT, default 1) */
+    int32_t fnx, fny;           /* fine cells per axis */
+    int32_t tx, ty;             /* tiles per axis */
+    uint64_t n_slots;           /* tx ty 64 */
+    uint64_t bytes;             /* n_slots 12 */
+    double ox, oy, cf;
+} pcp_fine_pivot_geo;
+int pcp_debug_fine_pivot(pcp_ctx *ctx, pcp_fine_pivot_geo *geo, void *piv, uint64_t piv_cap);
+
 /* diagnostics of the terrain index (cell edge, dims, points) */
 typedef struct pcp_index_info {
     uint64_t n_points;
     double cell;
     int32_t nx, ny, nz;
+    /* 1: the fine-window copy carries its pivot table (DESIGN.md §5 Skip 6; with fine_tile 2).
+       This field sits in what was the padding ahead of bmin: size and offsets are unchanged */
+    int32_t fine_pivot;
     double bmin[3], bmax[3];
     /* the layout the terrain scans walk: 0 per-cell runs, 1 2x2x2 block copy, 2 fine-window
        copy (the copies are built at the second query after pcp_set_terrain) */

@@ -102,7 +102,8 @@ SCAN_RETURN_DTYPE = np.dtype([("x", np.float32), ("y", np.float32), ("z", np.flo
 
 class IndexInfo(C.Structure):
     _fields_ = [("n_points", C.c_uint64), ("cell", C.c_double), ("nx", C.c_int32),
-                ("ny", C.c_int32), ("nz", C.c_int32), ("bmin", C.c_double * 3),
+                ("ny", C.c_int32), ("nz", C.c_int32), ("fine_pivot", C.c_int32),
+                ("bmin", C.c_double * 3),
                 ("bmax", C.c_double * 3), ("scan_layout", C.c_int32), ("fine_tile", C.c_int32)]
 
 
@@ -114,6 +115,13 @@ class FineGeo(C.Structure):
                                            "frec_bytes", "wpts_bytes", "pts_bytes")] +
                 [(k, C.c_double) for k in ("ox", "oy", "oz", "c", "inv_c", "r_q", "cf", "inv_cf",
                                            "R2", "zq", "clear_zt0", "clear_c")])
+
+
+class FinePivotGeo(C.Structure):
+    """pcp_fine_pivot_geo: the pivot table's geometry (pcp_debug_fine_pivot)."""
+    _fields_ = ([(k, C.c_int32) for k in ("built", "enabled", "fnx", "fny", "tx", "ty")] +
+                [(k, C.c_uint64) for k in ("n_slots", "bytes")] +
+                [(k, C.c_double) for k in ("ox", "oy", "cf")])
 
 
 class RuntimeInfo(C.Structure):
@@ -209,6 +217,7 @@ _SIGS = [
     ("pcp_debug_exclusive_scan", C.c_int, [_P, _P, C.c_uint64, _P]),
     ("pcp_debug_fine_copy", C.c_int, [_P, C.POINTER(FineGeo), _P, C.c_uint64, _P, C.c_uint64, _P,
                                       C.c_uint64]),
+    ("pcp_debug_fine_pivot", C.c_int, [_P, C.POINTER(FinePivotGeo), _P, C.c_uint64]),
     ("pcp_score_poses_burst", C.c_int, [_P, _P, C.c_uint64, _P, C.POINTER(VlParams), C.c_int,
                                         C.POINTER(C.c_double)]),
     ("pcp_stream_create", C.c_int, [_P, C.POINTER(_P)]),
@@ -732,7 +741,7 @@ class Context:
                 "dims": (info.nx, info.ny, info.nz),
                 "bmin": tuple(info.bmin), "bmax": tuple(info.bmax),
                 "scan_layout": ("cells", "blocks", "fine")[info.scan_layout],
-                "fine_tile": int(info.fine_tile)}
+                "fine_tile": int(info.fine_tile), "fine_pivot": int(info.fine_pivot)}
 
     def generate_candidates(self, grid_bbox, params: VlParams, zx120_pose5, cap=None):
         bb = np.ascontiguousarray(grid_bbox, np.float64)
@@ -903,6 +912,20 @@ class Context:
                                                  _ptr(wpts), wpts.nbytes, _ptr(pts), pts.nbytes),
                     "pcp_debug_fine_copy")
         return d, frec, wpts, pts
+
+    def debug_fine_pivot(self):
+        """pcp_debug_fine_pivot: the fine copy's pivot table as built -> (geo dict, float32
+        (n_slots, 3) records in tile order); (geo, None) with geo["built"] 0 when there is none."""
+        geo = FinePivotGeo()
+        self._check(self.lib.pcp_debug_fine_pivot(self.h, C.byref(geo), None, 0),
+                    "pcp_debug_fine_pivot")
+        d = {k: getattr(geo, k) for k, _ in geo._fields_}
+        if not geo.built:
+            return d, None
+        piv = np.zeros((geo.n_slots, 3), np.float32)
+        self._check(self.lib.pcp_debug_fine_pivot(self.h, C.byref(geo), _ptr(piv), piv.nbytes),
+                    "pcp_debug_fine_pivot")
+        return d, piv
 
     def score_matrix(self, poses5, zx120_pose5, params: VlParams):
         """pcp_score_matrix -> (score_mobile [P, C], score_zx120 [C]): evaluateCellScore per
@@ -1167,6 +1190,11 @@ class Multi:
 
 
 def _fan_stats(self, poses5, fan):
+    """pcp_raycast_fan_stats: the fan launch's gather lane-loads by kind.  Over the split fine
+    records: samples_visited = probes (2-byte threshold loads); scanned_stencils = walk starts
+    actually loaded (a candidate settled by its window's pivot loads none, DESIGN.md §5 Skip 6);
+    point_tests = every exact point test, the pivot tests included; their sum is the launch's
+    gather count.  directory_loads is 0 over a fine copy."""
     poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 5)
     st = np.zeros(4, np.uint64)
     self._check(self.lib.pcp_raycast_fan_stats(self.h, _ptr(poses), poses.shape[0], C.byref(fan),

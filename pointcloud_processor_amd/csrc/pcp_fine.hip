@@ -24,6 +24,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "pcp_fan_clear.hpp"
+#include "pcp_fan_pivot.hpp"
 #include "pcp_grid.hpp"
 #include "pcp_internal.hpp"
 
@@ -287,6 +288,38 @@ k_clear_code(const uint16_t *__restrict__ h, int fnx, int fny, uint32_t nw, uint
     fband[r] = (uint16_t)(0x00FFu | (fan_clear_code((uint32_t)D) << 8));
 }
 
+// The pivot table (pcp_fan_pivot.hpp, DESIGN.md §5 Skip 6), one thread per slot of the padded
+// 8 x 8 tile plane: the window's member nearest its cell's centre in xy, from the float4 entries
+// (their w still carries the original index), or the sentinel for an empty window or a padding
+// slot, as a 12-byte (x, y, z) record.
+__global__ void __launch_bounds__(kThreads)
+k_pivot(const float4 *__restrict__ wpts, const uint32_t *__restrict__ cstart, FineGeo f,
+        uint32_t tx, uint32_t nslot, float *__restrict__ piv) {
+    const uint32_t t = blockIdx.x * kThreads + threadIdx.x;
+    if (t >= nslot) return;
+    const uint32_t tile = t >> 6, sub = t & 63u;
+    const uint32_t wx = (tile % tx) * 8u + (sub & 7u), wy = (tile / tx) * 8u + (sub >> 3);
+    float3 best = make_float3(__int_as_float(0x7FC00000), __int_as_float(0x7FC00000), -INFINITY);
+    if (wx < (uint32_t)f.fnx && wy < (uint32_t)f.fny) {
+        const uint32_t w = wx + (uint32_t)f.fnx * wy;
+        const uint32_t s = cstart[w] + w, e = cstart[w + 1] + w;
+        PivotKey kb{};
+        for (uint32_t j = s; j < e; ++j) {
+            const float4 p = wpts[j];
+            const PivotKey k{pivot_d2(f.ox, f.oy, f.cf, wx, wy, p.x, p.y), p.z,
+                             __float_as_uint(p.w)};
+            if (j == s || pivot_better(k, kb)) {
+                kb = k;
+                best = make_float3(p.x, p.y, p.z);
+            }
+        }
+    }
+    float *o = piv + 3 * (size_t)t;   // (t = pivot_index(tx, wx, wy))
+    o[0] = best.x;
+    o[1] = best.y;
+    o[2] = best.z;
+}
+
 // the fine-window entries packed to 12 bytes (x, y, z): a quarter less working set for the walks
 __global__ void __launch_bounds__(kThreads)
 k_pack3(const float4 *__restrict__ src, uint32_t n, float *__restrict__ dst) {
@@ -306,6 +339,7 @@ struct FinePlan {
     ClearGeo cg;
     int F, tile;
     uint64_t fnx, fny, rz, nw, nrec;
+    uint64_t npiv;   // slots of the pivot table: the padded 8 x 8 tile plane (tile 2 only)
     size_t band_bytes, rec_bytes;
     uint32_t tsteps;
 };
@@ -323,6 +357,8 @@ FinePlan fine_plan(const GridIndex &g, int F, int tile) {
     p.nrec = tile ? ((p.fnx + T - 1) / T) * ((p.fny + T - 1) / T) * T * T * p.rz
                   : p.fnx * p.fny * p.rz;
     p.nw = p.fnx * p.fny;   // windows (the runs)
+    p.npiv = tile == 2 ? (uint64_t)pivot_tiles((uint32_t)p.fnx) * pivot_tiles((uint32_t)p.fny) * 64
+                       : 0;
     p.band_bytes = ((size_t)p.nrec * 2 + 255) & ~(size_t)255;
     p.rec_bytes = tile == 2 ? p.band_bytes + (size_t)p.nrec * 4 : (size_t)p.nrec * sizeof(uint2);
     p.f.ox = gv.ox;
@@ -416,13 +452,18 @@ int build_fine(pcp_ctx *ctx, GridIndex &g) {
     // the copy is an optional speed-up: an allocation failure keeps the other layouts
     const size_t nent = (size_t)np + nw;
     const bool pack = ctx->fine_pack != 0;
+    // the pivot table goes with the split records; its 12-byte records are addressed with
+    // 32-bit byte offsets (a plane past 2^28 cells keeps the copy and goes without)
+    const bool pivots = tile == 2 && plan.npiv < (1ull << 28);
     // packed: the float4 entries are built in scratch, then packed into wpts
     if ((pack && ctx->scratch[7].ensure(nent * sizeof(float4)) != hipSuccess) ||
         g.wpts.ensure(pack ? nent * 12 + 16 : nent * sizeof(float4)) != hipSuccess ||
-        g.frec.ensure(rec_bytes) != hipSuccess) {
+        g.frec.ensure(rec_bytes) != hipSuccess ||
+        (pivots && g.fpiv.ensure(plan.npiv * kPivotBytes + 16) != hipSuccess)) {
         (void)hipGetLastError();
         g.wpts.release();
         g.frec.release();
+        g.fpiv.release();
         g.fine_fail = true;
         return PCP_OK;
     }
@@ -443,6 +484,14 @@ int build_fine(pcp_ctx *ctx, GridIndex &g) {
                        g.frec.as<uint16_t>(),
                        reinterpret_cast<uint32_t *>(g.frec.as<char>() + band_bytes));
     PCP_CHECK_LAUNCH(ctx);
+    if (pivots) {
+        // the pivots, while the entries still carry their original index (the packing drops it)
+        hipLaunchKernelGGL(k_pivot, dim3((unsigned)((plan.npiv + kThreads - 1) / kThreads)),
+                           dim3(kThreads), 0, st, (const float4 *)went, (const uint32_t *)cstart,
+                           f, pivot_tiles((uint32_t)fnx), (uint32_t)plan.npiv,
+                           g.fpiv.as<float>());
+        PCP_CHECK_LAUNCH(ctx);
+    }
     if (tile == 2) {
         // clearance codes into the empty records (their high byte; the table does not grow)
         const size_t lev_bytes = ((size_t)nw * 4 + 255) & ~(size_t)255;
@@ -479,6 +528,7 @@ int build_fine(pcp_ctx *ctx, GridIndex &g) {
     g.fskip = skip2 ? 2 : 1;
     g.fstart_off = tile == 2 ? band_bytes : 0;
     g.fnent = nent;
+    g.fpiv_ok = pivots;
     g.fine_ok = true;
     return PCP_OK;
 }
@@ -538,5 +588,34 @@ extern "C" int pcp_debug_fine_copy(pcp_ctx *ctx, pcp_fine_geo *geo, void *frec,
     if (frec) PCP_HIP(ctx, hipMemcpy(frec, g.frec.p, geo->frec_bytes, hipMemcpyDeviceToHost));
     if (wpts) PCP_HIP(ctx, hipMemcpy(wpts, g.wpts.p, geo->wpts_bytes, hipMemcpyDeviceToHost));
     if (pts) PCP_HIP(ctx, hipMemcpy(pts, g.pts.p, geo->pts_bytes, hipMemcpyDeviceToHost));
+    return PCP_OK;
+}
+
+// Test infrastructure (tests/test_fan_pivot.py): the pivot table as it lies on the device.
+extern "C" int pcp_debug_fine_pivot(pcp_ctx *ctx, pcp_fine_pivot_geo *geo, void *piv,
+                                    uint64_t piv_cap) {
+    using namespace pcp;
+    if (!ctx || !geo) return PCP_E_INVALID;
+    const GridIndex &g = ctx->terrain;
+    *geo = pcp_fine_pivot_geo{};
+    if (!g.present || !g.fine_ok || !g.fpiv_ok) return PCP_OK;   // built = 0
+    const FinePlan p = fine_plan(g, (int)g.ffine, g.ftile);
+    geo->built = 1;
+    geo->enabled = g.fan_pivot ? 1 : 0;
+    geo->fnx = p.f.fnx;
+    geo->fny = p.f.fny;
+    geo->tx = (int32_t)pivot_tiles((uint32_t)p.fnx);
+    geo->ty = (int32_t)pivot_tiles((uint32_t)p.fny);
+    geo->n_slots = p.npiv;
+    geo->bytes = p.npiv * kPivotBytes;
+    geo->ox = p.f.ox;
+    geo->oy = p.f.oy;
+    geo->cf = p.f.cf;
+    if (!piv) return PCP_OK;   // the sizes only
+    if (piv_cap < geo->bytes)
+        return set_err(ctx, PCP_E_CAPACITY, "pcp_debug_fine_pivot: the buffer is too small");
+    PCP_HIP(ctx, hipSetDevice(ctx->device));
+    PCP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    PCP_HIP(ctx, hipMemcpy(piv, g.fpiv.p, geo->bytes, hipMemcpyDeviceToHost));
     return PCP_OK;
 }

@@ -79,6 +79,10 @@ GridView GridIndex::view() const {
     v.fclear = (fine_ok && ftile == 2 && fan_clear) ? 1 : 0;
     v.fclr_cf = fine_ok ? (float)(c / (double)ffine) : 0.0f;
     v.fclr_rb = std::nextafter((float)rb, INFINITY);
+    const bool piv = fine_ok && ftile == 2 && fpiv_ok;
+    v.fpiv = (piv && fan_pivot) ? fpiv.as<const float>() : nullptr;
+    v.fptx = piv ? (frx + 7u) >> 3 : 0u;
+    v.fpty = piv ? (fry + 7u) >> 3 : 0u;
     return v;
 }
 
@@ -703,6 +707,7 @@ int build_index(pcp_ctx *ctx, GridIndex &g, const pcp_cloud_view &v, double r_q,
     g.blk_ok = false;
     g.blk_fail = false;
     g.fine_ok = false;
+    g.fpiv_ok = false;
     g.fine_fail = false;
     // 1. the raw AoS bytes (the PointCloud2 data blob), device-readable: given by the caller,
     //    read in place from the pinned ring (message-sized), or DMA'd into ctx->stage
@@ -984,6 +989,7 @@ int pcp_terrain_info(pcp_ctx *ctx, pcp_index_info *info) {
     }
     info->scan_layout = g.fine_ok ? 2 : g.blk_ok ? 1 : 0;
     info->fine_tile = g.fine_ok ? g.ftile : 0;
+    info->fine_pivot = (g.fine_ok && g.fpiv_ok) ? 1 : 0;
     return PCP_OK;
 }
 

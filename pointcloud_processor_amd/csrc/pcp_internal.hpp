@@ -155,6 +155,12 @@ struct GridView {               // POD passed to kernels by value
     // fclr_cf = c / F, fclr_rb = r + m + 1e-6 max|coord| (rounded up)
     int32_t fclear;
     float fclr_cf, fclr_rb;
+    // ftile 2: the windows' pivots (pcp_fan_pivot.hpp, DESIGN.md §5 Skip 6), one 12-byte
+    // (x, y, z) record per fine cell in fptx x fpty 8 x 8 xy tiles (the band records' tiles
+    // without the iz term); null (PCP_FAN_PIVOT=0, or no split records) leaves the march as it
+    // was.  Read by the fan kernels only.
+    const float *fpiv;
+    uint32_t fptx, fpty;
 };
 constexpr float kZq = 2.0f / 250.0f;   // z band step, cells (2 cells = 250 steps)
 
@@ -165,7 +171,7 @@ struct GridIndex {
     double c = 0.0;
     int32_t nx = 0, ny = 0, nz = 0;
     double bmin[3] = {0, 0, 0}, bmax[3] = {0, 0, 0};
-    DevBuf pts, start, occ2, occz, bstart, bpts, frec, wpts;
+    DevBuf pts, start, occ2, occz, bstart, bpts, frec, wpts, fpiv;
     bool occz_ok = false;
     bool blk_ok = false;         // block-major copy built (bstart / bpts)
     bool blk_fail = false;       // copy unavailable for this index (size cap or allocation
@@ -179,6 +185,9 @@ struct GridIndex {
     int32_t fskip = 1;           // walk-start skip thresholds (PCP_FINE_SKIP)
     bool fan_clear = true;       // the march jumps by the empty records' clearance codes
                                  // (PCP_FAN_CLEAR, set once by pcp_create; release() keeps it)
+    bool fpiv_ok = false;        // pivot table built (fpiv; with the split records)
+    bool fan_pivot = true;       // the fan march tests a window's pivot before its walk
+                                 // (PCP_FAN_PIVOT, set once by pcp_create; release() keeps it)
     size_t fstart_off = 0;       // ftile 2: byte offset of the start array inside frec
     uint64_t fnent = 0;          // entries of wpts, sentinels included (pcp_debug_fine_copy)
     bool occ2_ok = false;        // occ2 built (only indices queried by stencil_any need it)
@@ -192,6 +201,8 @@ struct GridIndex {
         bpts.release();
         frec.release();
         wpts.release();
+        fpiv.release();
+        fpiv_ok = false;
         occz_ok = false;
         blk_ok = false;
         blk_fail = false;

@@ -245,7 +245,8 @@ __device__ __forceinline__ void clip_kf(const GridView &g, double px, double py,
 //  * A surviving sample computes q_k exactly (s_k is the step table entry: the table was built
 //    by the same repeated additions the reference performs) and scans the block of its exact
 //    corner, so every point test is the reference's test.
-// STATS counts probes, scanned stencils and point tests into cnt[0..2].
+// STATS counts probes, scanned stencils and point tests into cnt[0..2] (FN 8: probes, walk starts
+// loaded, exact point tests with the pivot tests among them: the gather lane-loads by kind).
 //  * FN (the fine-window copy, g.frec): the probe reads the record of the sample's fine corner
 //    -- its window's z band and run -- and a candidate walks that run with the exact q_k.  The
 //    approximate corner's window holds every point within r of q_k (the same margin argument as
@@ -257,7 +258,10 @@ __device__ __forceinline__ void clip_kf(const GridView &g, double px, double py,
 //  * CLR (the fan kernels): Skip 5, the jump over empty ground, below.  Cell scoring's march
 //    leaves it out: its rays end at their cell, few of them run on underground, and the jump's
 //    instructions cost it 1.7 %.
-template <bool STATS, bool ZB = true, int NB = 1, int FN = 0, bool CLR = false>
+//  * PIV (the fan kernels, FN 8): Skip 6, a candidate tests its window's pivot first, below.
+//    Cell scoring, the scan and the placement leave it out: their rays end at a visible cell, so
+//    few of their candidates are hits.
+template <bool STATS, bool ZB = true, int NB = 1, int FN = 0, bool CLR = false, bool PIV = false>
 __device__ __forceinline__ int march(const GridView &g, double px, double py, double pz,
                                      double dx, double dy, double dz,
                                      const double *__restrict__ steps, int K, double end,
@@ -265,16 +269,16 @@ __device__ __forceinline__ int march(const GridView &g, double px, double py, do
                                      int koff = 0, int kstr = 1) {
     if (FN == 2) {
         if (g.frec && g.ftile == 2)
-            return march<STATS, ZB, NB, 8, CLR>(g, px, py, pz, dx, dy, dz, steps, K, end, r2,
-                                                rexit, cnt, koff, kstr);
+            return march<STATS, ZB, NB, 8, CLR, PIV>(g, px, py, pz, dx, dy, dz, steps, K, end,
+                                                     r2, rexit, cnt, koff, kstr);
         if (g.frec && g.ftile)
-            return march<STATS, ZB, NB, 4, CLR>(g, px, py, pz, dx, dy, dz, steps, K, end, r2,
-                                                rexit, cnt, koff, kstr);
+            return march<STATS, ZB, NB, 4, CLR, PIV>(g, px, py, pz, dx, dy, dz, steps, K, end,
+                                                     r2, rexit, cnt, koff, kstr);
         if (g.frec)
-            return march<STATS, ZB, NB, 1, CLR>(g, px, py, pz, dx, dy, dz, steps, K, end, r2,
-                                                rexit, cnt, koff, kstr);
-        return march<STATS, ZB, NB, 0, CLR>(g, px, py, pz, dx, dy, dz, steps, K, end, r2, rexit,
-                                            cnt, koff, kstr);
+            return march<STATS, ZB, NB, 1, CLR, PIV>(g, px, py, pz, dx, dy, dz, steps, K, end,
+                                                     r2, rexit, cnt, koff, kstr);
+        return march<STATS, ZB, NB, 0, CLR, PIV>(g, px, py, pz, dx, dy, dz, steps, K, end, r2,
+                                                 rexit, cnt, koff, kstr);
     }
     int klo, khi;
     clip_kf(g, px, py, pz, dx, dy, dz, K, klo, khi);
@@ -349,10 +353,24 @@ __device__ __forceinline__ int march(const GridView &g, double px, double py, do
             if (cand) {
                 const double s = steps[k];
                 if (!(s < end)) return -1;
-                if (STATS) cnt[1] += 1;
                 const float qx = (float)(px + dx * s);
                 const float qy = (float)(py + dy * s);
                 const float qz = (float)(pz + dz * s);
+                // Skip 6 (FN 8 with PIV, pcp_fan_pivot.hpp): the window's point nearest its
+                // cell's centre, tested first with the walk's own predicate.  Within r: a
+                // terrain point within r of q_k, which is all radiusSearch(q, r) > 0 asks -- no
+                // walk start, no entry.  Otherwise nothing is concluded and the walk runs as it
+                // did.  The table's tiles are the band records' (rx = g.fptx; ri's low 6 bits
+                // are the cell's place in its tile); an empty window's sentinel is never within r.
+                if (FN == 8 && PIV && g.fpiv) {
+                    const uint32_t pi = (mad_u24(rx, iy >> 3, ix >> 3) << 6) | (ri & 63u);
+                    const float *pf = reinterpret_cast<const float *>(
+                        reinterpret_cast<const char *>(g.fpiv) + ((pi << 3) + (pi << 2)));
+                    const P3 pv = P3{pf[0], pf[1], pf[2]};
+                    if (STATS) cnt[2] += 1;
+                    if (flann_within(qx, qy, qz, pv, r2)) return k;
+                }
+                if (STATS) cnt[1] += 1;
                 uint32_t w0 = R.x;
                 if (FN == 8) {   // skip the run's entries > r above q (pcp_fine.hip, k_frec)
                     const uint32_t ws = ld_u32o(g.fstart, ri);
@@ -1463,8 +1481,8 @@ __device__ __forceinline__ void fan_body(const FanArgs &a, uint32_t p0, uint32_t
             asm volatile("" ::"v"(dx), "v"(dy));
             t1 = __builtin_amdgcn_s_memtime();
         }
-        hit = march<MODE == FAN_STATS, ZB, 1, FN, true>(a.g, P[0], P[1], P[2], dx, dy, dz, steps,
-                                                  a.K, 1e300, a.r2, a.rexit, cnt);
+        hit = march<MODE == FAN_STATS, ZB, 1, FN, true, true>(a.g, P[0], P[1], P[2], dx, dy, dz,
+                                                              steps, a.K, 1e300, a.r2, a.rexit, cnt);
     }
     if (MODE == FAN_STAMPS) {
         asm volatile("" ::"v"(hit));
