@@ -8,6 +8,7 @@
 #include <cstring>
 #include <new>
 
+#include "pcp_fan_clip.hpp"
 #include "pcp_internal.hpp"
 
 namespace pcp {
@@ -660,6 +661,8 @@ int pcp_create(int device, pcp_ctx **out) {
     if (const char *fc = std::getenv("PCP_FAN_CULL")) ctx->fan_cull = std::atoi(fc) != 0;
     if (const char *cl = std::getenv("PCP_FAN_CLEAR")) ctx->terrain.fan_clear = std::atoi(cl) != 0;
     if (const char *pv = std::getenv("PCP_FAN_PIVOT")) ctx->terrain.fan_pivot = std::atoi(pv) != 0;
+    if (const char *cp = std::getenv("PCP_FAN_CLIP"))
+        ctx->terrain.fan_clip_e = std::atoi(cp) != 0 ? pcp::kClipSlack : pcp::kClipSlackWhole;
     if (const char *fo = std::getenv("PCP_FAN_ORDER")) ctx->fan_horizon_first = std::atoi(fo) != 0;
     if (const char *ho = std::getenv("PCP_FAN_HOST_OUT")) ctx->fan_host_out = std::atoi(ho) != 0;
     if (const char *ne = std::getenv("PCP_NORMALS_EXACT")) ctx->normals_exact = std::atoi(ne) != 0;

@@ -83,6 +83,7 @@ GridView GridIndex::view() const {
     v.fpiv = (piv && fan_pivot) ? fpiv.as<const float>() : nullptr;
     v.fptx = piv ? (frx + 7u) >> 3 : 0u;
     v.fpty = piv ? (fry + 7u) >> 3 : 0u;
+    v.fclip_e = fan_clip_e;
     return v;
 }
 

@@ -161,6 +161,9 @@ struct GridView {               // POD passed to kernels by value
     // was.  Read by the fan kernels only.
     const float *fpiv;
     uint32_t fptx, fpty;
+    // the clip interval's slack each side, in samples (pcp_fan_clip.hpp, DESIGN.md §5 Skip 3):
+    // kClipSlack, or 1 (PCP_FAN_CLIP=0), the whole sample the rule kept before
+    float fclip_e;
 };
 constexpr float kZq = 2.0f / 250.0f;   // z band step, cells (2 cells = 250 steps)
 
@@ -188,6 +191,8 @@ struct GridIndex {
     bool fpiv_ok = false;        // pivot table built (fpiv; with the split records)
     bool fan_pivot = true;       // the fan march tests a window's pivot before its walk
                                  // (PCP_FAN_PIVOT, set once by pcp_create; release() keeps it)
+    float fan_clip_e = 1.0f / 64.0f;   // clip slack in samples, kClipSlack of pcp_fan_clip.hpp
+                                 // (PCP_FAN_CLIP=0: 1; set once by pcp_create; release() keeps it)
     size_t fstart_off = 0;       // ftile 2: byte offset of the start array inside frec
     uint64_t fnent = 0;          // entries of wpts, sentinels included (pcp_debug_fine_copy)
     bool occ2_ok = false;        // occ2 built (only indices queried by stencil_any need it)

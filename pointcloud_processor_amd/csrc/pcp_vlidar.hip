@@ -16,6 +16,7 @@
 
 #include "pcp_crmath.h"
 #include "pcp_fan_clear.hpp"
+#include "pcp_fan_clip.hpp"
 #include "pcp_fan_cull.hpp"
 #include "pcp_internal.hpp"
 #include "pcp_stencil.hpp"
@@ -197,37 +198,17 @@ __device__ __forceinline__ bool stencil_any(const GridView &g, float qx, float q
     return scan_stencil<false>(g, lin, qx, qy, qz, r2, nullptr);
 }
 
-// clip_k in float (approximate reciprocal): the interval is that of a box perturbed by ~1e-5 m;
-// samples it drops lie within that distance of the true clip box's outside, i.e. >= r + m -
-// 1e-5 from every point (the box is the point bbox inflated by r + m + 1e-6 |coord|): empty.
+// clip_k in float (approximate reciprocal), pcp_fan_clip.hpp: the samples it drops lie outside
+// the clip box shrunk by fan_clip_delta (< 1 mm of the margin beside the box's own 1e-6 |coord|),
+// i.e. further than r from every point (the box is the point bbox inflated by r + m +
+// 1e-6 |coord|): empty.  g.fclip_e samples of slack each side (2^-6; PCP_FAN_CLIP=0: 1).
 __device__ __forceinline__ void clip_kf(const GridView &g, double px, double py, double pz,
                                         double dx, double dy, double dz, int K, int &klo,
                                         int &khi) {
-    // branch-free slabs: a zero (or flushed denormal) direction component gives +-inf slab
-    // times, so a start strictly inside the slab leaves [t0, t1] as it is and one outside
-    // empties it; a start exactly on a slab face (0 * inf = NaN, dropped by fmin/fmax, the
-    // other time +-inf) also empties it -- exact, since the face lies r + m + 1e-6 |coord| from
-    // every point and a ray parallel to it never comes closer
-    float t0 = 0.0f, t1 = FLT_MAX;
-    const float p[3] = {(float)px, (float)py, (float)pz}, d[3] = {(float)dx, (float)dy, (float)dz};
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float inv = __builtin_amdgcn_rcpf(d[a]);
-        const float ta = (g.fb[2 * a] - p[a]) * inv, tb = (g.fb[2 * a + 1] - p[a]) * inv;
-        t0 = fmaxf(t0, fminf(ta, tb));
-        t1 = fminf(t1, fmaxf(ta, tb));
-    }
-    if (!(t0 <= t1)) {
-        klo = 0;
-        khi = -1;
-        return;
-    }
-    // one sample of slack each side (s_k = 0.5 + 0.3 k to ~1e-13, t0/t1 to float rounding)
-    const float inv_step = (float)(1.0 / kRayStep);
-    const float kl = ceilf((t0 - 0.5f) * inv_step) - 1.0f;
-    const float kh = floorf(fminf(t1, 1e30f) * inv_step - 0.5f * inv_step) + 1.0f;
-    klo = (int)fminf(fmaxf(kl, 0.0f), (float)K);
-    khi = (int)fminf(fmaxf(kh, -1.0f), (float)(K - 1));
+    const float p[3] = {(float)px, (float)py, (float)pz};
+    const float inv[3] = {__builtin_amdgcn_rcpf((float)dx), __builtin_amdgcn_rcpf((float)dy),
+                          __builtin_amdgcn_rcpf((float)dz)};
+    fan_clip(g.fb, p, inv, (float)(1.0 / kRayStep), g.fclip_e, K, klo, khi);
 }
 
 // checkVisibilityWithRaycasting's march (virtual_lidar.cpp:765-797) from pos along unit dir:
