@@ -404,6 +404,60 @@ int pcp_place_sensors(pcp_ctx *ctx, const double *poses5, uint64_t n,
                       double *zx120_total, int32_t *zx120_covered, /* nullable */
                       int32_t *n_selected);
 
+/* The exact best pair of mobile sensors: every pair of the poses evaluated, not greedy rounds (the
+ * best pair need not contain the best single pose, which is where pcp_place_sensors starts).
+ * S[p][c], Z[c], max(a, b) and osum(v) as above; fixed[0 .. n_fixed) are poses already placed.
+ *   1. base = Z; for i = 0 .. n_fixed - 1 in list order base = max(base, S[fixed[i]]);
+ *      owner[c] = Z[c] > 0 ? PCP_OWNER_ZX120 : PCP_OWNER_NONE, then fixed sensor i owns every
+ *      cell where base[c] < S[fixed[i]][c] held at its fold (ties keep the earlier owner);
+ *      *base_total = osum(base), *base_covered = #{base > 0} (n_fixed = 0: pcp_place_sensors'
+ *      zx120_total / zx120_covered).
+ *   2. Pose p is admissible iff it is not in fixed and, with min_separation > 0, for no fixed f
+ *      dx * dx + dy * dy < min_separation * min_separation (pcp_place_sensors' expression, each
+ *      operation rounded).
+ *   3. s[p] = osum(max(base, S[p])) for admissible p, -inf otherwise (single_totals [n]);
+ *      *best_single = the first maximum (strict '>' from -inf), -1 when no pose is admissible;
+ *      *single_total / *single_covered its total and #{.. > 0} (-inf / 0 without one).
+ *   4. For a < b, both admissible and (min_separation > 0) not closer to each other than it:
+ *      t[a][b] = osum(max(max(base, S[a]), S[b])); pair_totals [n][n] holds t[a][b], every other
+ *      entry -inf (the diagonal, the lower triangle, inadmissible pairs); best_pair = the first
+ *      maximum in row-major order (a ascending, then b; strict '>'), (-1, -1) when there is no
+ *      admissible pair; *pair_total / *pair_covered its values (-inf / 0 without one).
+ *   5. *n_selected = 2 when a pair exists and *pair_total > *single_total; otherwise 1 when a
+ *      single exists and *single_total > *base_total; otherwise 0 (under a separation the best
+ *      pair can lose to the best single).  cell_score / cell_owner describe that answer: the
+ *      base, then the chosen pose or poses folded in the order a, b with owners n_fixed and
+ *      n_fixed + 1, ties to the earlier owner.
+ * PCP_E_INVALID before any launch, nothing written: n_fixed outside 0 .. PCP_PLACE_MAX, reserved
+ * != 0, a fixed index >= n or listed twice, n > PCP_PAIR_MAX_POSES, a step table past
+ * PCP_MAX_STEPS, a null required pointer (everything not marked nullable), a null context.
+ * n == 0 or no cells: PCP_OK, *n_selected = 0, *best_single = -1, best_pair = (-1, -1), the base
+ * totals as defined (0 without cells).  One synchronisation; deterministic (two calls give
+ * identical bytes); the caller's GridCell flags are neither read nor written; the call's scratch
+ * is its own, so the other queries on the context are unchanged by it. */
+#define PCP_PAIR_MAX_POSES 2048
+typedef struct pcp_pair_params {
+    int32_t n_fixed;                 /* sensors already placed, 0 .. PCP_PLACE_MAX */
+    int32_t reserved;                /* 0 */
+    double  min_separation;          /* metres in XY; <= 0: no constraint */
+    int64_t fixed[PCP_PLACE_MAX];    /* indices into poses5, first n_fixed used */
+} pcp_pair_params;
+int pcp_place_pair(pcp_ctx *ctx, const double *poses5, uint64_t n, const double zx120_pose5[5],
+                   const pcp_vl_params *p, const pcp_pair_params *pp,
+                   int64_t best_pair[2], double *pair_total, int32_t *pair_covered,
+                   int64_t *best_single, double *single_total, int32_t *single_covered,
+                   double *base_total, int32_t *base_covered,
+                   double *pair_totals,    /* nullable [n][n]  */
+                   double *single_totals,  /* nullable [n]     */
+                   double *cell_score, int32_t *cell_owner,   /* nullable [n_cells] */
+                   int32_t *n_selected);
+
+/* Kernel timing of pcp_place_pair (the timing tool only): the query's setup (the scoring) once,
+ * then `reps` repetitions of its pair phase -- preparation, pair tiles, selection, no dense table
+ * -- between two stream events; *ms_per_rep = the interval / reps.  n >= 1, cells present. */
+int pcp_place_pair_burst(pcp_ctx *ctx, const double *poses5, uint64_t n, const double zx120_pose5[5],
+                         const pcp_vl_params *p, const pcp_pair_params *pp, int reps, double *ms_per_rep);
+
 /* Dense ray fan (BASELINE configs[1]): per pose, n_az x n_el rays, ray (i, j) with local
  * direction (cos e_j cos a_i, cos e_j sin a_i, sin e_j), a_i = 2*pi*i/n_az,
  * e_j = el_min + (el_max-el_min)*(j+0.5)/n_el, rotated by the pose yaw, marched with

@@ -86,6 +86,15 @@ class PlaceParams(C.Structure):
     _fields_ = [("k_max", C.c_int32), ("reserved", C.c_int32), ("min_separation", C.c_double)]
 
 
+PAIR_MAX_POSES = 2048   # PCP_PAIR_MAX_POSES: poses one pcp_place_pair call searches at most
+
+
+class PairParams(C.Structure):
+    """pcp_pair_params."""
+    _fields_ = [("n_fixed", C.c_int32), ("reserved", C.c_int32), ("min_separation", C.c_double),
+                ("fixed", C.c_int64 * PLACE_MAX)]
+
+
 SCAN_MAX_POSES = 64   # PCP_SCAN_MAX_POSES: poses one pcp_simulate_scan call casts (mask bits)
 
 
@@ -209,6 +218,11 @@ _SIGS = [
     ("pcp_score_matrix", C.c_int, [_P, _P, C.c_uint64, _P, C.POINTER(VlParams), _P, _P]),
     ("pcp_place_sensors", C.c_int, [_P, _P, C.c_uint64, _P, C.POINTER(VlParams),
                                     C.POINTER(PlaceParams), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("pcp_place_pair", C.c_int, [_P, _P, C.c_uint64, _P, C.POINTER(VlParams),
+                                 C.POINTER(PairParams), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                 _P, _P, _P]),
+    ("pcp_place_pair_burst", C.c_int, [_P, _P, C.c_uint64, _P, C.POINTER(VlParams),
+                                       C.POINTER(PairParams), C.c_int, C.POINTER(C.c_double)]),
     ("pcp_simulate_scan", C.c_int, [_P, _P, C.c_uint64, C.POINTER(FanParams), _P, C.c_uint64,
                                     C.POINTER(C.c_uint64), _P, _P, _P, _P, _P, C.c_uint64,
                                     C.POINTER(C.c_uint64), _P, C.POINTER(C.c_uint64)]),
@@ -976,6 +990,70 @@ class Context:
             out["cell_score"] = cs[:C_].copy()
             out["cell_owner"] = co[:C_].copy()
         return out
+
+    @staticmethod
+    def _pair_params(fixed, min_separation, reserved, n_fixed=None) -> PairParams:
+        fixed = [int(f) for f in fixed]
+        pp = PairParams(len(fixed) if n_fixed is None else int(n_fixed), int(reserved),
+                        float(min_separation))
+        for i, f in enumerate(fixed[:PLACE_MAX]):
+            pp.fixed[i] = f
+        return pp
+
+    def place_pair(self, poses5, zx120_pose5, params: VlParams, fixed=(),
+                   min_separation: float = 0.0, want_pair_totals: bool = False,
+                   want_single_totals: bool = False, want_cells: bool = False,
+                   reserved: int = 0) -> dict:
+        """pcp_place_pair: the exact best pair of the poses beside zx120 and the `fixed` poses
+        (every admissible pair a < b evaluated; the first maximum in row-major order), with the
+        best single pose and the base for comparison.  -> dict: n_selected (2: the pair beats the
+        single, 1: only the single adds, 0), best_pair (2,), pair_total, pair_covered,
+        best_single, single_total, single_covered, base_total, base_covered, and on request
+        pair_totals [P, P] (-inf off the admissible upper triangle), single_totals [P],
+        cell_score / cell_owner [n_cells] of the answer."""
+        poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 5)
+        zx = np.ascontiguousarray(zx120_pose5, np.float64)
+        P = poses.shape[0]
+        pp = self._pair_params(fixed, min_separation, reserved)
+        bp = np.full(2, -1, np.int64)
+        pt, st, bt = C.c_double(), C.c_double(), C.c_double()
+        pc, sc, bc, ns = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        bs = C.c_int64(-1)
+        dense = P <= PAIR_MAX_POSES   # (a refused call writes nothing: no table for it)
+        tab = np.zeros((max(P, 1), max(P, 1)), np.float64) if want_pair_totals and dense else None
+        sg = np.zeros(max(P, 1), np.float64) if want_single_totals else None
+        C_ = self.cells_count() if want_cells else 0
+        cs = np.zeros(max(C_, 1), np.float64) if want_cells else None
+        co = np.zeros(max(C_, 1), np.int32) if want_cells else None
+        self._check(self.lib.pcp_place_pair(
+            self.h, _ptr(poses) if P else None, P, _ptr(zx), C.byref(params), C.byref(pp),
+            _ptr(bp), C.byref(pt), C.byref(pc), C.byref(bs), C.byref(st), C.byref(sc),
+            C.byref(bt), C.byref(bc), _ptr(tab), _ptr(sg), _ptr(cs), _ptr(co), C.byref(ns)),
+            "pcp_place_pair")
+        out = {"n_selected": ns.value, "best_pair": bp, "pair_total": pt.value,
+               "pair_covered": pc.value, "best_single": bs.value, "single_total": st.value,
+               "single_covered": sc.value, "base_total": bt.value, "base_covered": bc.value}
+        if want_pair_totals:
+            out["pair_totals"] = tab[:P, :P].copy()
+        if want_single_totals:
+            out["single_totals"] = sg[:P].copy()
+        if want_cells:
+            out["cell_score"] = cs[:C_].copy()
+            out["cell_owner"] = co[:C_].copy()
+        return out
+
+    def place_pair_burst(self, poses5, zx120_pose5, params: VlParams, fixed=(),
+                         min_separation: float = 0.0, reps: int = 20) -> float:
+        """pcp_place_pair_burst -> ms per repetition of the pair phase (preparation, pair tiles,
+        selection; the scoring once before the interval)."""
+        poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 5)
+        zx = np.ascontiguousarray(zx120_pose5, np.float64)
+        pp = self._pair_params(fixed, min_separation, 0)
+        ms = C.c_double(0.0)
+        self._check(self.lib.pcp_place_pair_burst(self.h, _ptr(poses), poses.shape[0], _ptr(zx),
+                                                  C.byref(params), C.byref(pp), int(reps),
+                                                  C.byref(ms)), "pcp_place_pair_burst")
+        return ms.value
 
     def simulate_scan(self, poses5, fan: FanParams, want_dense: bool = False,
                       want_mask: bool = True, returns_cap: int | None = None,

@@ -7,6 +7,8 @@
 //                         MAXD OUT_TOTALS.f64 OUT_FLAGS.u8 OUT_REPORT.txt [TICKS]
 //   pcp_nodes_cli place   TERRAIN.f32 TN AUX.f32 AN CELLS.f64 NORMALS.f32 CN BBOX(6) ZXT(3) NUMC
 //                         MAXD KMAX MINSEP OUT_SELECTED.i64 OUT_TOTALS.f64 OUT_REPORT.txt
+//   pcp_nodes_cli place_pair  (place's arguments; KMAX: the greedy placement it is compared with)
+//                         OUT_SELECTED: the exact answer; OUT_TOTALS: base, single, pair
 //   pcp_nodes_cli scan    TERRAIN.f32 TN POSES(5 per sensor) NAZ NEL MAXD OUT_SCANS.bin
 //                         OUT_OFFSETS.u64 OUT_BLIND.f32 OUT_MASK.u64
 //   pcp_nodes_cli drivable IN.f32 N STEP TF(7) R1(2) R2(2) OUT.i8
@@ -189,7 +191,7 @@ static int cmd_vlidar(Device &dev, char **a, int argc) {
 
 // one tick of the virtual-LiDAR node (vlidar's inputs), then KMAX mobile sensors placed greedily
 // among its candidates: the selected candidates, the totals after each and the placement's table
-static int cmd_place(Device &dev, char **a) {
+static int cmd_place(Device &dev, char **a, bool exact_pair = false) {
     const auto t = read_file(a[0]), ax = read_file(a[2]), c = read_file(a[4]),
                nr = read_file(a[5]);
     const size_t tn = std::strtoull(a[1], nullptr, 10), an = std::strtoull(a[3], nullptr, 10),
@@ -219,6 +221,32 @@ static int cmd_place(Device &dev, char **a) {
         return 1;
     }
     MobileLidarPlacement placement(pp);
+    if (exact_pair) {
+        // place_pair: the exact best pair beside the greedy placement's first two (KMAX sensors
+        // placed greedily for the comparison); the chosen candidates, {base, single, pair}
+        // totals and the pair table
+        if (placement.place_pair(dev, SimplifiedDualLidarOptimizer::Result{}, p).ran) return 3;
+        const auto greedy = placement.place(dev, tick, p);
+        const auto r = placement.place_pair(dev, tick, p, {}, greedy.ran ? &greedy : nullptr);
+        if (!r.ran) {
+            std::fprintf(stderr, "place_pair: %s\n", placement.lastError().c_str());
+            return 1;
+        }
+        std::vector<int64_t> sel;
+        if (r.n_selected == 2) sel = {r.pair[0], r.pair[1]};
+        if (r.n_selected == 1) sel = {r.single};
+        const double tot[3] = {r.base_total, r.single_total, r.pair_total};
+        write_file(a[13], sel.data(), sel.size() * 8);
+        write_file(a[14], tot, sizeof(tot));
+        write_file(a[15], r.log.data(), r.log.size());
+        std::printf("{\"n_candidates\": %zu, \"n_selected\": %d, \"best_pair\": [%lld, %lld], "
+                    "\"pair_covered\": %d, \"best_single\": %lld, \"single_covered\": %d, "
+                    "\"base_covered\": %d, \"total_cells\": %d}\n",
+                    tick.candidates.size(), r.n_selected, (long long)r.pair[0],
+                    (long long)r.pair[1], r.pair_covered, (long long)r.single, r.single_covered,
+                    r.base_covered, r.total_cells);
+        return 0;
+    }
     if (placement.place(dev, SimplifiedDualLidarOptimizer::Result{}, p).ran) return 3;   // no tick
     const auto r = placement.place(dev, tick, p);
     if (!r.ran) {
@@ -659,7 +687,7 @@ int main(int argc, char **argv) {
         if (!hp || std::atoi(hp) != 0) setenv("HSA_ENABLE_INTERRUPT", "0", 0);
     }
     if (argc < 2) {
-        std::fprintf(stderr, "usage: pcp_nodes_cli filter|merge|vlidar|place|scan|area|drivable|replay ...\n");
+        std::fprintf(stderr, "usage: pcp_nodes_cli filter|merge|vlidar|place|place_pair|scan|area|drivable|replay ...\n");
         return 2;
     }
     const std::string cmd = argv[1];
@@ -667,6 +695,7 @@ int main(int argc, char **argv) {
                      : cmd == "merge"  ? 7
                      : cmd == "vlidar" ? 14
                      : cmd == "place"  ? 16
+                     : cmd == "place_pair" ? 16
                      : cmd == "scan"   ? 10
                      : cmd == "area"   ? 10
                      : cmd == "drivable" ? 7
@@ -682,6 +711,7 @@ int main(int argc, char **argv) {
         if (cmd == "merge") return cmd_merge(dev, argv + 2);
         if (cmd == "vlidar") return cmd_vlidar(dev, argv + 2, argc - 2);
         if (cmd == "place") return cmd_place(dev, argv + 2);
+        if (cmd == "place_pair") return cmd_place(dev, argv + 2, /*exact_pair=*/true);
         if (cmd == "scan") return cmd_scan(dev, argv + 2);
         if (cmd == "area") return cmd_area(dev, argv + 2);
         if (cmd == "drivable") return cmd_drivable(dev, argv + 2);

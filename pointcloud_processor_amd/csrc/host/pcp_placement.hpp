@@ -42,6 +42,32 @@ class MobileLidarPlacement {
     // are not touched
     Result place(Device &dev, const SimplifiedDualLidarOptimizer::Result &tick,
                  const SimplifiedDualLidarOptimizer::Params &vl);
+
+    // The exact best pair (pcp_place_pair): every pair of the tick's candidates evaluated beside
+    // zx120 and the `fixed` candidates (sensors already placed), not greedy rounds.
+    struct PairResult {
+        bool ran = false;              // false: the tick did not run, or the call failed
+        int32_t n_selected = 0;        // 2: the pair beats the best single; 1: only the single
+                                       // adds to the base; 0: nothing does
+        int64_t pair[2] = {-1, -1};    // candidate indices, a < b; -1: no admissible pair
+        double pair_total = 0;
+        int32_t pair_covered = 0;
+        int64_t single = -1;           // the best single candidate; -1: none admissible
+        double single_total = 0;
+        int32_t single_covered = 0;
+        double base_total = 0;         // zx120 and the fixed sensors alone
+        int32_t base_covered = 0;
+        int32_t n_fixed = 0;
+        int32_t total_cells = 0;
+        std::vector<SimplifiedDualLidarOptimizer::LidarPosition> placed;   // the n_selected chosen
+        SimplifiedDualLidarOptimizer::LidarPosition pair_pos[2], single_pos;   // where they exist
+        std::string log;
+    };
+    // min_separation is params()'s; num_mobile_lidars plays no part.  greedy (nullable): a
+    // place() result for the same tick, whose first two sensors the log compares the pair with
+    PairResult place_pair(Device &dev, const SimplifiedDualLidarOptimizer::Result &tick,
+                          const SimplifiedDualLidarOptimizer::Params &vl,
+                          const std::vector<int64_t> &fixed = {}, const Result *greedy = nullptr);
     const std::string &lastError() const { return err_; }
 
    private:
@@ -51,5 +77,9 @@ class MobileLidarPlacement {
 
 // the placement's table: host arithmetic only
 std::string placement_log(const MobileLidarPlacement::Result &r);
+// the pair search's table in the same format: the base, the best single, the best pair with its
+// gain over the single, and (greedy given, two sensors placed) its gain over greedy's two
+std::string placement_pair_log(const MobileLidarPlacement::PairResult &r,
+                               const MobileLidarPlacement::Result *greedy = nullptr);
 
 }  // namespace pcp

@@ -777,6 +777,9 @@ void pcp_destroy(pcp_ctx *ctx) {
     ctx->exc_land.release();
     ctx->place_d.release();
     ctx->place_host.release();
+    ctx->pair_d.release();
+    ctx->pair_m.release();
+    ctx->pair_host.release();
     ctx->vscan_d.release();
     ctx->vscan_host.release();
     if (ctx->area_stream) (void)hipStreamDestroy(ctx->area_stream);

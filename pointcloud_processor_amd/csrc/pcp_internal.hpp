@@ -350,6 +350,11 @@ struct pcp_ctx {
     // pcp_score_poses leaves and expects them)
     pcp::DevBuf place_d;
     pcp::PinnedBuf place_host;
+    // pcp_place_pair (pcp_pairs.hip): its state, base / owner, singles, per-block bests and the
+    // dense pair table (pair_d), the clamped transposed rows M [C][P16] (pair_m), and the pinned
+    // landing of its one download (its own, as the placement's)
+    pcp::DevBuf pair_d, pair_m;
+    pcp::PinnedBuf pair_host;
     // pcp_simulate_scan (pcp_scan.hip): wave bases, offsets, records, dense images, point mask and
     // counts, and the pinned landing of its downloads (its own: the fan's buffers stay as
     // pcp_raycast_fan leaves and expects them)

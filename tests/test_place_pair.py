@@ -1,0 +1,358 @@
+"""pcp_place_pair (the exact best pair of mobile sensors) on the 91-candidate tick.
+
+Every case asks for the dense outputs and is checked twice:
+  (a) bit for bit against tests/pair_ref.py run on ctx.score_matrix's own output for the same
+      arguments: the whole pair table with its -inf pattern, the singles, both selections, the
+      covered counts, the base values, cell_score's bits and cell_owner;
+  (b) against pair_ref on the oracle's matrix: selections, covered counts and owners equal, the
+      totals under parity.assert_totals (the base totals under the exact bar without fixed
+      sensors).  (b) applies where nothing on the oracle side is decided by less than GAP -- the
+      device matrix differs from glibc's by a few ulps in a few cells (tests/parity.py) -- and the
+      case asserts that; the smallest such gap of the full-tick cases is 0.199 (four fixed).
+The oracle's matrix is computed once for the whole tick; cell / pose subsets are slices of it."""
+import json
+import subprocess
+from pathlib import Path
+
+import numpy as np
+import pair_ref
+import parity
+import pytest
+
+from pointcloud_processor_amd import _abi
+
+pytestmark = pytest.mark.gpu
+
+ROOT = Path(__file__).resolve().parents[1]
+CLI = ROOT / "pointcloud_processor_amd" / "_lib" / "pcp_nodes_cli"
+GAP = 0.1
+T = 16        # the pair tile's edge in poses (kPairTile; tests/test_pair_tiles_host.py pins it)
+CHUNK = 64    # cells per staged chunk of a tile and per preparation block (kQC)
+CHAIN = 256   # cells per step of the base total's chain (kQT; runs with fixed sensors only)
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float64).view(np.uint64)
+
+
+@pytest.fixture(scope="module")
+def tick(oracle, scene, cells, aux):
+    """One context with the scene loaded, the tick's 91 candidates and the oracle's matrix."""
+    params = _abi.default_vl_params()
+    with _abi.Context(0) as ctx:
+        ctx.set_terrain(scene.terrain, point_step=32)
+        ctx.set_aux_cloud(aux, point_step=32)
+        ctx.set_cells(cells.xyz, cells.normals)
+        poses = np.ascontiguousarray(
+            ctx.generate_candidates(cells.grid_bbox, params, scene.zx120_pose5))
+        assert poses.shape == (91, 5) and cells.xyz.shape[0] == 3704
+        Tc, A = oracle.Cloud(scene.terrain), oracle.Cloud(aux)
+        o_S, o_Z = oracle.score_matrix(Tc, A, cells.xyz, cells.normals, poses, scene.zx120_pose5,
+                                       oracle.vl_params())
+        yield {"ctx": ctx, "poses": poses, "params": params, "S": o_S, "Z": o_Z,
+               "zx": scene.zx120_pose5, "cells": cells}
+        ctx.set_cells(cells.xyz, cells.normals)
+
+
+def _finite_totals(got, ref):
+    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
+    live = np.isfinite(ref)
+    np.testing.assert_array_equal(np.isfinite(got), live)
+    np.testing.assert_array_equal(got[~live], ref[~live])   # -inf where the definition says so
+    return got[live], ref[live]
+
+
+def _case(tick, pose_idx, Cn, fixed=(), sep=0.0, oracle_side=True):
+    """place_pair over poses[pose_idx] and cells[:Cn], checked (a) and, with oracle_side, (b);
+    returns (device result, device-side restatement)."""
+    ctx, cells = tick["ctx"], tick["cells"]
+    poses = np.ascontiguousarray(tick["poses"][pose_idx])
+    Pn = poses.shape[0]
+    ctx.set_cells(cells.xyz[:Cn], cells.normals[:Cn])
+    got = ctx.place_pair(poses, tick["zx"], tick["params"], fixed, sep, want_pair_totals=True,
+                         want_single_totals=True, want_cells=True)
+    d_S, d_Z = ctx.score_matrix(poses, tick["zx"], tick["params"])
+    assert d_S.shape == (Pn, Cn)
+    # (a) exact, on the device's own matrix
+    ref = pair_ref.place_pair(d_S, d_Z, poses[:, :2], fixed, sep)
+    assert got["pair_totals"].shape == (Pn, Pn) and got["single_totals"].shape == (Pn,)
+    np.testing.assert_array_equal(_bits(got["pair_totals"]), _bits(ref["pair_totals"]))
+    np.testing.assert_array_equal(_bits(got["single_totals"]), _bits(ref["single_totals"]))
+    np.testing.assert_array_equal(got["best_pair"], ref["best_pair"])
+    for k in ("best_single", "n_selected", "pair_covered", "single_covered", "base_covered"):
+        assert got[k] == ref[k], (k, got[k], ref[k])
+    for k in ("pair_total", "single_total", "base_total"):
+        assert _bits(got[k])[0] == _bits(ref[k])[0], (k, got[k], ref[k])
+    np.testing.assert_array_equal(_bits(got["cell_score"]), _bits(ref["cell_score"]))
+    np.testing.assert_array_equal(got["cell_owner"], ref["cell_owner"])
+    if not oracle_side:
+        return got, ref
+    # (b) the oracle's matrix
+    orc = pair_ref.place_pair(tick["S"][pose_idx][:, :Cn], tick["Z"][:Cn], poses[:, :2], fixed, sep)
+    assert pair_ref.runner_up_gap(orc) > GAP, pair_ref.runner_up_gap(orc)   # nothing hangs on ulps
+    np.testing.assert_array_equal(got["best_pair"], orc["best_pair"])
+    for k in ("best_single", "n_selected", "pair_covered", "single_covered", "base_covered"):
+        assert got[k] == orc[k], (k, got[k], orc[k])
+    np.testing.assert_array_equal(got["cell_owner"], orc["cell_owner"])
+    pt = _finite_totals(got["pair_totals"], orc["pair_totals"])
+    sg = _finite_totals(got["single_totals"], orc["single_totals"])
+    print(f"C={Cn} P={Pn} fixed={list(fixed)} sep={sep}: pairs", parity.totals_report(*pt),
+          "singles", parity.totals_report(*sg))
+    parity.assert_totals(*pt)
+    parity.assert_totals(*sg)
+    parity.assert_totals([got["pair_total"], got["single_total"]],
+                         [orc["pair_total"], orc["single_total"]])
+    if len(fixed) == 0:
+        parity.assert_totals_exact(got["base_total"], orc["base_total"])
+    else:
+        parity.assert_totals(got["base_total"], orc["base_total"])
+    return got, ref
+
+
+# fixed, sep -> admissible pairs, best pair, covered, best single, n_selected (the oracle-side
+# values of tests/test_pair_ref.py)
+FULL = [
+    ([], 0.0, 4095, (41, 48), 3260, 40, 2),
+    ([], 2.0, 3744, (41, 48), 3260, 40, 2),
+    ([], 5.0, 2301, (15, 48), 3015, 40, 2),
+    ([], 8.0, 697, (32, 90), None, 40, 1),     # the best pair loses to the best single
+    ([40], 0.0, 4005, (41, 48), 3447, 41, 2),
+    ([40], 2.0, 3175, (41, 56), 3414, None, 2),
+    ([41, 48], 2.0, None, (24, 32), 3504, 32, 2),
+    ([40, 41, 48, 3], 5.0, 11, (8, 87), 3487, 87, 2),
+]
+
+
+@pytest.mark.parametrize("fixed,sep,n_pairs,pair,pcov,single,nsel", FULL)
+def test_full_tick(tick, fixed, sep, n_pairs, pair, pcov, single, nsel):
+    got, ref = _case(tick, slice(None), 3704, fixed, sep)
+    assert tuple(got["best_pair"]) == pair and got["n_selected"] == nsel
+    if n_pairs is not None:
+        assert int(np.isfinite(got["pair_totals"]).sum()) == n_pairs
+    if pcov is not None:
+        assert got["pair_covered"] == pcov
+    if single is not None:
+        assert got["best_single"] == single
+    if nsel == 1:   # the answer is the single: its cells carry owner n_fixed, none n_fixed + 1
+        assert got["pair_total"] < got["single_total"]
+        assert (got["cell_owner"] == len(fixed)).any()
+        assert not (got["cell_owner"] == len(fixed) + 1).any()
+
+
+@pytest.mark.parametrize("Cn", [1, CHUNK - 1, CHUNK, CHUNK + 1, 191, 384, 385, 1153])
+def test_cell_prefixes(tick, Cn):
+    """Cell prefixes around the staged chunk and the placement's chunk / ring sizes.  Short
+    prefixes leave exact ties between poses, so these are held to (a)."""
+    _case(tick, slice(None), Cn, oracle_side=False)
+
+
+@pytest.mark.parametrize("Cn", [CHAIN - 1, CHAIN, CHAIN + 1])
+def test_cell_prefixes_fixed(tick, Cn):
+    """With fixed sensors the base total is the preparation's own chain, CHAIN cells a step."""
+    _case(tick, slice(None), Cn, fixed=[40, 3], sep=2.0, oracle_side=False)
+
+
+@pytest.mark.parametrize("Pn", [1, 2, 3, T - 1, T, T + 1, 2 * T + 1, 100])
+def test_pose_counts(tick, Pn):
+    """Pose counts around the tile edge; 100 > 91 wraps round: exact duplicate rows in different
+    tiles, ties decided by index."""
+    got, ref = _case(tick, np.arange(Pn) % 91, 3704, oracle_side=False)
+    if Pn == 1:
+        assert tuple(got["best_pair"]) == (-1, -1) and got["pair_total"] == -np.inf
+        assert got["pair_covered"] == 0 and got["best_single"] == 0
+    if Pn == 100:
+        assert tuple(got["best_pair"]) == (41, 48)
+        # poses 0 .. 8 and 91 .. 99 are the same rows: equal singles, the copies' pairs equal
+        np.testing.assert_array_equal(_bits(got["single_totals"][:9]),
+                                      _bits(got["single_totals"][91:]))
+        np.testing.assert_array_equal(_bits(got["pair_totals"][0, 1:9]),
+                                      _bits(got["pair_totals"][1:9, 91]))
+
+
+def test_pose_counts_fixed(tick):
+    """Fixed sensors in the last, partial tile."""
+    _case(tick, np.arange(2 * T + 1), 3704, fixed=[2 * T, 0], sep=1.0, oracle_side=False)
+
+
+def test_duplicates_and_ties(tick):
+    got, _ = _case(tick, [40, 40, 41, 48, 48], 3704, oracle_side=False)
+    assert got["best_single"] == 0 and tuple(got["best_pair"]) == (2, 3)
+    got, _ = _case(tick, [41, 48, 40], 3704, oracle_side=False)
+    assert tuple(got["best_pair"]) == (0, 1) and got["best_single"] == 2
+
+
+def test_agrees_with_the_greedy_kernels(tick):
+    ctx, cells = tick["ctx"], tick["cells"]
+    ctx.set_cells(cells.xyz, cells.normals)
+    poses, zx, params = tick["poses"], tick["zx"], tick["params"]
+    g = ctx.place_sensors(poses, zx, params, 2, want_round_totals=True)
+    e = ctx.place_pair(poses, zx, params, want_pair_totals=True, want_single_totals=True)
+    np.testing.assert_array_equal(_bits(e["single_totals"]), _bits(g["round_totals"][0]))
+    assert e["best_single"] == g["selected"][0]
+    assert _bits(e["base_total"])[0] == _bits(g["zx120_total"])[0]
+    assert e["base_covered"] == g["zx120_covered"]
+    first = int(g["selected"][0])
+    r1 = g["round_totals"][1]
+    live = np.isfinite(r1)
+    assert live.sum() == 90 and not live[first]
+    row = np.array([e["pair_totals"][min(first, p), max(first, p)] for p in np.flatnonzero(live)])
+    np.testing.assert_array_equal(_bits(row), _bits(r1[live]))
+    assert e["pair_total"] - g["total_after"][1] > 10   # what greedy leaves on the table
+
+
+def test_isolation(tick):
+    """pcp_score_poses before and after the search on one context: identical; the caller's flags
+    are not touched; the scratch allocations settle after the first call; two calls give equal
+    bytes, with a pcp_place_sensors call in between or not."""
+    ctx, cells = tick["ctx"], tick["cells"]
+    ctx.set_cells(cells.xyz, cells.normals)
+    poses, zx, params = tick["poses"], tick["zx"], tick["params"]
+    f0 = np.zeros(3704, np.uint8)
+    t0, c0, r0 = ctx.score_poses(poses, zx, params, f0)
+    held = f0.copy()
+    kw = dict(fixed=[40], min_separation=2.0, want_pair_totals=True, want_single_totals=True,
+              want_cells=True)
+    g0 = ctx.place_sensors(poses, zx, params, 8, 2.0, want_round_totals=True, want_cells=True)
+    first = ctx.place_pair(poses, zx, params, **kw)
+    np.testing.assert_array_equal(f0, held)
+    settled = _abi.alloc_stats()
+    again = ctx.place_pair(poses, zx, params, **kw)
+    assert _abi.alloc_stats() == settled
+    g1 = ctx.place_sensors(poses, zx, params, 8, 2.0, want_round_totals=True, want_cells=True)
+    third = ctx.place_pair(poses, zx, params, **kw)
+    for k in first:
+        for other in (again, third):
+            a, b = np.asarray(first[k]), np.asarray(other[k])
+            assert a.dtype == b.dtype and a.tobytes() == b.tobytes(), k
+    for k in g0:
+        np.testing.assert_array_equal(g0[k], g1[k])
+    f1 = np.zeros(3704, np.uint8)
+    t1, c1, r1 = ctx.score_poses(poses, zx, params, f1)
+    np.testing.assert_array_equal(_bits(t0), _bits(t1))
+    np.testing.assert_array_equal(c0, c1)
+    np.testing.assert_array_equal(f0, f1)
+    assert r0.as_dict() == r1.as_dict()
+    assert _abi.alloc_stats() == settled
+
+
+def test_refusals(tick):
+    ctx, cells = tick["ctx"], tick["cells"]
+    ctx.set_cells(cells.xyz, cells.normals)
+    poses, zx, params = tick["poses"], tick["zx"], tick["params"]
+    ctx.profile(True)
+    ctx.profile_reset()
+    try:
+        bad = [{"fixed": list(range(_abi.PLACE_MAX + 1))},   # n_fixed past PCP_PLACE_MAX
+               {"reserved": 1},
+               {"fixed": [91]}, {"fixed": [-1]},             # no pose of the call
+               {"fixed": [3, 40, 3]}]                        # listed twice
+        for kw in bad:
+            with pytest.raises(_abi.PcpError) as e:
+                ctx.place_pair(poses, zx, params, **kw)
+            assert e.value.code == _abi.PCP_E_INVALID, kw
+        many = np.ascontiguousarray(poses[np.arange(_abi.PAIR_MAX_POSES + 1) % 91])
+        with pytest.raises(_abi.PcpError) as e:
+            ctx.place_pair(many, zx, params)
+        assert e.value.code == _abi.PCP_E_INVALID
+        far = _abi.default_vl_params(max_distance=0.5 + 0.3 * (_abi.MAX_STEPS + 2))
+        with pytest.raises(_abi.PcpError) as e:
+            ctx.place_pair(poses, zx, far)
+        assert e.value.code == _abi.PCP_E_INVALID
+        # n_fixed below zero and a null required pointer: past the binding, at the C entry
+        pp = _abi.PairParams(-1, 0, 0.0)
+        out = [_abi.C.c_double() for _ in range(3)]
+        cnt = [_abi.C.c_int32() for _ in range(4)]
+        bp, bs = (_abi.C.c_int64 * 2)(), _abi.C.c_int64()
+        zxa = np.ascontiguousarray(zx, np.float64)
+        B = _abi.C.byref
+
+        def raw(pp, n_sel):
+            return ctx.lib.pcp_place_pair(
+                ctx.h, _abi._ptr(poses), 91, _abi._ptr(zxa), B(params), B(pp), bp, B(out[0]),
+                B(cnt[0]), B(bs), B(out[1]), B(cnt[1]), B(out[2]), B(cnt[2]), None, None, None,
+                None, n_sel)
+        assert raw(pp, B(cnt[3])) == _abi.PCP_E_INVALID
+        assert raw(_abi.PairParams(0, 0, 0.0), None) == _abi.PCP_E_INVALID
+        for k in ("score_cells", "pose_sum", "place_sensors"):   # nothing was launched
+            assert ctx.profile_get(k)[1] == 0
+        ctx.place_pair(poses, zx, params)
+        assert ctx.profile_get("score_cells")[1] >= 1   # the search scores
+        assert ctx.profile_get("place_sensors")[1] == 0  # and launches no placement round
+    finally:
+        ctx.profile(False)
+    # no cells: nothing to cover
+    ctx.set_cells(cells.xyz[:0], cells.normals[:0])
+    got = ctx.place_pair(poses, zx, params, want_pair_totals=True, want_single_totals=True,
+                         want_cells=True)
+    assert got["n_selected"] == 0 and got["best_single"] == -1
+    assert tuple(got["best_pair"]) == (-1, -1)
+    assert got["base_total"] == 0.0 and got["base_covered"] == 0
+    assert got["cell_score"].size == 0
+    # no poses: the zx120 sensor alone
+    ctx.set_cells(cells.xyz, cells.normals)
+    got = ctx.place_pair(poses[:0], zx, params, want_pair_totals=True, want_single_totals=True,
+                         want_cells=True)
+    assert got["n_selected"] == 0 and got["best_single"] == -1
+    assert tuple(got["best_pair"]) == (-1, -1) and got["pair_totals"].shape == (0, 0)
+    d_S, d_Z = ctx.score_matrix(poses[:1], zx, params)
+    ref = pair_ref.place_pair(d_S[:0], d_Z, poses[:0, :2])
+    np.testing.assert_array_equal(_bits(got["cell_score"]), _bits(d_Z))
+    np.testing.assert_array_equal(got["cell_owner"], ref["cell_owner"])
+    assert _bits(got["base_total"])[0] == _bits(ref["base_total"])[0]
+    assert got["base_covered"] == ref["base_covered"]
+
+
+def test_burst_times_the_pair_phase(tick):
+    ctx, cells = tick["ctx"], tick["cells"]
+    ctx.set_cells(cells.xyz, cells.normals)
+    ms = ctx.place_pair_burst(tick["poses"], tick["zx"], tick["params"], reps=3)
+    assert ms > 0.0
+    with pytest.raises(_abi.PcpError) as e:
+        ctx.place_pair_burst(tick["poses"], tick["zx"], tick["params"], reps=0)
+    assert e.value.code == _abi.PCP_E_INVALID
+
+
+def test_cli_place_pair(tick, tmp_path, scene, cells, aux):
+    """pcp_nodes_cli place_pair (MobileLidarPlacement::place_pair above the node's tick): the
+    binding's answer, and a log that names both poses and the gain over the single."""
+    assert CLI.exists(), "build first (__graft_entry__.build())"
+    np.ascontiguousarray(scene.terrain).tofile(tmp_path / "t.f32")
+    np.ascontiguousarray(aux).tofile(tmp_path / "a.f32")
+    np.ascontiguousarray(cells.xyz, np.float64).tofile(tmp_path / "c.f64")
+    np.ascontiguousarray(cells.normals, np.float32).tofile(tmp_path / "n.f32")
+    t = lambda v: ",".join(repr(float(x)) for x in v)   # noqa: E731
+    r = subprocess.run([str(CLI), "place_pair", str(tmp_path / "t.f32"),
+                        str(scene.terrain.shape[0]), str(tmp_path / "a.f32"), str(aux.shape[0]),
+                        str(tmp_path / "c.f64"), str(tmp_path / "n.f32"),
+                        str(cells.xyz.shape[0]), t(cells.grid_bbox), "0,0,0", "100", "15.0", "2",
+                        "2.0", str(tmp_path / "sel.i64"), str(tmp_path / "tot.f64"),
+                        str(tmp_path / "rep.txt")],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, (r.returncode, r.stderr)
+    res = json.loads(r.stdout.strip().splitlines()[-1])
+    ctx = tick["ctx"]
+    ctx.set_cells(cells.xyz, cells.normals)
+    got = ctx.place_pair(tick["poses"], tick["zx"], tick["params"], min_separation=2.0)
+    greedy = ctx.place_sensors(tick["poses"], tick["zx"], tick["params"], 2, 2.0)
+    assert res["n_candidates"] == 91 and res["n_selected"] == got["n_selected"] == 2
+    assert res["best_pair"] == got["best_pair"].tolist() == [41, 48]
+    assert res["best_single"] == got["best_single"] and res["total_cells"] == 3704
+    assert res["pair_covered"] == got["pair_covered"]
+    np.testing.assert_array_equal(np.fromfile(tmp_path / "sel.i64", np.int64), got["best_pair"])
+    np.testing.assert_array_equal(
+        _bits(np.fromfile(tmp_path / "tot.f64", np.float64)),
+        _bits([got["base_total"], got["single_total"], got["pair_total"]]))
+    log = (tmp_path / "rep.txt").read_text()
+    assert "Exact Pair Placement (ZX120 + 0 Fixed + 2 Mobile)" in log
+    assert f"Total Score (ZX120 only): {got['base_total']:.2f}" in log
+    p = tick["poses"][got["best_single"]]
+    assert (f"Best Single Position: ({p[0]:.2f}, {p[1]:.2f}, {p[2]:.2f})  "
+            f"[candidate {got['best_single']}]") in log
+    for i, s in enumerate(got["best_pair"]):
+        p = tick["poses"][s]
+        assert (f"Best Pair LiDAR {i + 1} Position: ({p[0]:.2f}, {p[1]:.2f}, {p[2]:.2f})  "
+                f"[candidate {s}]") in log
+    gain = got["pair_total"] - got["single_total"]
+    assert f"  Total Score: {got['pair_total']:.2f} (gain over single {gain:.2f})" in log
+    over = got["pair_total"] - greedy["total_after"][1]
+    assert f"(exact pair gains {over:.2f})" in log and over > 10
