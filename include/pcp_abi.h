@@ -729,6 +729,20 @@ typedef struct pcp_fine_pivot_geo {
 } pcp_fine_pivot_geo;
 int pcp_debug_fine_pivot(pcp_ctx *ctx, pcp_fine_pivot_geo *geo, void *piv, uint64_t piv_cap);
 
+/* Test infrastructure: the tight twin of the split records' probe thresholds (DESIGN.md section
+ * 5, Skip 7) read back as it lies on the device: one uint16 per record slot, lo | hi << 8, in the
+ * layout of the threshold array at the head of pcp_debug_fine_copy's frec (8 x 8 xy tiles, one
+ * plane per iz; that call's geometry describes both).  Empty records, with their clearance codes,
+ * and padding records equal the specified array's; every other record is never looser than it.
+ * *bytes is the array's size, 0 with PCP_OK when there is no twin (no fine copy, one without
+ * split records, or the twin's allocation failed); *enabled (may be NULL) reports whether the
+ * march reads the twin (PCP_FAN_BAND, default 1) -- the twin does not depend on the knob.  band
+ * NULL fills the two values only; with a buffer (cap in bytes, PCP_E_CAPACITY when short) it
+ * copies the array.  The call never builds, launches nothing, and synchronises the context's
+ * stream before its copy; pcp_debug_fine_copy's output is what it was. */
+int pcp_debug_fine_band(pcp_ctx *ctx, uint64_t *bytes, int32_t *enabled, void *band,
+                        uint64_t band_cap);
+
 /* diagnostics of the terrain index (cell edge, dims, points) */
 typedef struct pcp_index_info {
     uint64_t n_points;

@@ -232,6 +232,8 @@ _SIGS = [
     ("pcp_debug_fine_copy", C.c_int, [_P, C.POINTER(FineGeo), _P, C.c_uint64, _P, C.c_uint64, _P,
                                       C.c_uint64]),
     ("pcp_debug_fine_pivot", C.c_int, [_P, C.POINTER(FinePivotGeo), _P, C.c_uint64]),
+    ("pcp_debug_fine_band", C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_int32), _P,
+                                      C.c_uint64]),
     ("pcp_score_poses_burst", C.c_int, [_P, _P, C.c_uint64, _P, C.POINTER(VlParams), C.c_int,
                                         C.POINTER(C.c_double)]),
     ("pcp_stream_create", C.c_int, [_P, C.POINTER(_P)]),
@@ -940,6 +942,20 @@ class Context:
         self._check(self.lib.pcp_debug_fine_pivot(self.h, C.byref(geo), _ptr(piv), piv.nbytes),
                     "pcp_debug_fine_pivot")
         return d, piv
+
+    def debug_fine_band(self):
+        """pcp_debug_fine_band: the tight twin of the split records' thresholds as built ->
+        (enabled, uint16 array, one word lo | hi << 8 per record slot in the threshold array's
+        layout); (enabled, None) when there is no twin."""
+        nbytes, enabled = C.c_uint64(), C.c_int32()
+        self._check(self.lib.pcp_debug_fine_band(self.h, C.byref(nbytes), C.byref(enabled), None, 0),
+                    "pcp_debug_fine_band")
+        if not nbytes.value:
+            return int(enabled.value), None
+        band = np.zeros(nbytes.value // 2, np.uint16)
+        self._check(self.lib.pcp_debug_fine_band(self.h, C.byref(nbytes), C.byref(enabled),
+                                                 _ptr(band), band.nbytes), "pcp_debug_fine_band")
+        return int(enabled.value), band
 
     def score_matrix(self, poses5, zx120_pose5, params: VlParams):
         """pcp_score_matrix -> (score_mobile [P, C], score_zx120 [C]): evaluateCellScore per

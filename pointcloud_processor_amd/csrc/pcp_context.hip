@@ -661,6 +661,7 @@ int pcp_create(int device, pcp_ctx **out) {
     if (const char *fc = std::getenv("PCP_FAN_CULL")) ctx->fan_cull = std::atoi(fc) != 0;
     if (const char *cl = std::getenv("PCP_FAN_CLEAR")) ctx->terrain.fan_clear = std::atoi(cl) != 0;
     if (const char *pv = std::getenv("PCP_FAN_PIVOT")) ctx->terrain.fan_pivot = std::atoi(pv) != 0;
+    if (const char *bd = std::getenv("PCP_FAN_BAND")) ctx->terrain.fan_band = std::atoi(bd) != 0;
     if (const char *cp = std::getenv("PCP_FAN_CLIP"))
         ctx->terrain.fan_clip_e = std::atoi(cp) != 0 ? pcp::kClipSlack : pcp::kClipSlackWhole;
     if (const char *fo = std::getenv("PCP_FAN_ORDER")) ctx->fan_horizon_first = std::atoi(fo) != 0;

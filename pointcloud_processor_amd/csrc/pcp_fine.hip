@@ -23,6 +23,7 @@
 
 #include <rocprim/device/device_radix_sort.hpp>
 
+#include "pcp_fan_band.hpp"
 #include "pcp_fan_clear.hpp"
 #include "pcp_fan_pivot.hpp"
 #include "pcp_grid.hpp"
@@ -288,6 +289,50 @@ k_clear_code(const uint16_t *__restrict__ h, int fnx, int fny, uint32_t nw, uint
     fband[r] = (uint16_t)(0x00FFu | (fan_clear_code((uint32_t)D) << 8));
 }
 
+// The tight twin of the split records' thresholds (pcp_fan_band.hpp, DESIGN.md §5 Skip 7), one
+// thread per window after the clearance codes are in: `twin` starts as a copy of fband (empty
+// records with their codes and padding records stay as they are), and every other record of the
+// window is coded again from its entries -- k_frec's membership, the same two pointers down the
+// run -- each entry widening the band by its reach over the cell.
+__global__ void __launch_bounds__(kThreads)
+k_band_tight(const float4 *__restrict__ wpts, const uint32_t *__restrict__ cstart, CellMap m,
+             FineGeo f, double c, double qm, double rho, uint32_t rz, uint32_t tx, size_t plane,
+             const uint16_t *__restrict__ fband, uint16_t *__restrict__ twin) {
+    const uint32_t nw = (uint32_t)f.fnx * (uint32_t)f.fny, w = blockIdx.x * kThreads + threadIdx.x;
+    if (w >= nw) return;
+    const uint32_t wx = w % (uint32_t)f.fnx, wy = w / (uint32_t)f.fnx;
+    const size_t base = ((size_t)((wy >> 3) * tx + (wx >> 3)) << 6) | ((wy & 7u) << 3) | (wx & 7u);
+    const uint32_t s = cstart[w] + w, e = cstart[w + 1] + w;   // e: the sentinel
+    uint32_t jt = s, jb = s;
+    int ct = s < e ? cell_z(m, wpts[s].z) : -1, cb = ct;
+    const double step = (double)kZq * c;
+    for (int iz = (int)rz - 1; iz >= 0; --iz) {
+        while (jt < e && ct > iz + 1) {
+            ++jt;
+            ct = jt < e ? cell_z(m, wpts[jt].z) : -1;
+        }
+        if (jb < jt) {
+            jb = jt;
+            cb = ct;
+        }
+        while (jb < e && cb >= iz) {
+            ++jb;
+            cb = jb < e ? cell_z(m, wpts[jb].z) : -1;
+        }
+        const size_t r = (size_t)iz * plane + base;
+        const uint32_t spec = fband[r];
+        if (jb == jt || (spec & 255u) == 255u) continue;   // empty: the copy stands
+        BandAcc a = fan_band_begin();
+        for (uint32_t j = jt; j < jb; ++j) {
+            const float4 p = wpts[j];
+            fan_band_add(a, (double)p.z,
+                         fan_band_dist(f.ox, f.oy, f.cf, (int)wx, (int)wy, (double)p.x, (double)p.y),
+                         qm, rho);
+        }
+        twin[r] = (uint16_t)fan_band_word(a, m.oz + (double)iz * c, step, spec);
+    }
+}
+
 // The pivot table (pcp_fan_pivot.hpp, DESIGN.md §5 Skip 6), one thread per slot of the padded
 // 8 x 8 tile plane: the window's member nearest its cell's centre in xy, from the float4 entries
 // (their w still carries the original index), or the sentinel for an empty window or a padding
@@ -512,6 +557,23 @@ int build_fine(pcp_ctx *ctx, GridIndex &g) {
                            (int)fnx, (int)fny, (uint32_t)nw, (uint32_t)((fnx + 7) / 8), (size_t)(nrec / rz),
                            g.frec.as<uint16_t>());
         PCP_CHECK_LAUNCH(ctx);
+        // the tight twin of the thresholds (Skip 7); without its allocation the march reads the
+        // specified ones
+        g.fband_ok = false;
+        if (g.fband2.ensure(band_bytes) == hipSuccess) {
+            PCP_HIP(ctx, hipMemcpyAsync(g.fband2.p, g.frec.p, band_bytes, hipMemcpyDeviceToDevice,
+                                        st));
+            hipLaunchKernelGGL(k_band_tight, dim3(cgrid.x), dim3(kThreads), 0, st,
+                               (const float4 *)went, (const uint32_t *)cstart, m, f, g.c,
+                               kQueryMargin, g.r_q + kBandMu, (uint32_t)rz,
+                               (uint32_t)((fnx + 7) / 8), (size_t)(nrec / rz),
+                               g.frec.as<const uint16_t>(), g.fband2.as<uint16_t>());
+            PCP_CHECK_LAUNCH(ctx);
+            g.fband_ok = true;
+        } else {
+            (void)hipGetLastError();
+            g.fband2.release();
+        }
     }
     if (pack) {
         hipLaunchKernelGGL(k_pack3, dim3((unsigned)((nent + kThreads - 1) / kThreads)),
@@ -617,5 +679,28 @@ extern "C" int pcp_debug_fine_pivot(pcp_ctx *ctx, pcp_fine_pivot_geo *geo, void 
     PCP_HIP(ctx, hipSetDevice(ctx->device));
     PCP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     PCP_HIP(ctx, hipMemcpy(piv, g.fpiv.p, geo->bytes, hipMemcpyDeviceToHost));
+    return PCP_OK;
+}
+
+// Test infrastructure (tests/test_fan_band.py): the thresholds' tight twin as it lies on the
+// device, the bytes of the split records' threshold array (pcp_debug_fine_copy's geometry
+// describes both).  *bytes: the array's size, 0 when no twin is built; *enabled: the march reads
+// it (PCP_FAN_BAND).
+extern "C" int pcp_debug_fine_band(pcp_ctx *ctx, uint64_t *bytes, int32_t *enabled, void *band,
+                                   uint64_t band_cap) {
+    using namespace pcp;
+    if (!ctx || !bytes) return PCP_E_INVALID;
+    const GridIndex &g = ctx->terrain;
+    *bytes = 0;
+    if (enabled) *enabled = g.fan_band ? 1 : 0;
+    if (!g.present || !g.fine_ok || !g.fband_ok) return PCP_OK;
+    const FinePlan p = fine_plan(g, (int)g.ffine, g.ftile);
+    *bytes = (uint64_t)p.nrec * 2;
+    if (!band) return PCP_OK;   // the size only
+    if (band_cap < *bytes)
+        return set_err(ctx, PCP_E_CAPACITY, "pcp_debug_fine_band: the buffer is too small");
+    PCP_HIP(ctx, hipSetDevice(ctx->device));
+    PCP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    PCP_HIP(ctx, hipMemcpy(band, g.fband2.p, *bytes, hipMemcpyDeviceToHost));
     return PCP_OK;
 }

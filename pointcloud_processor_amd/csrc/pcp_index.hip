@@ -67,7 +67,9 @@ GridView GridIndex::view() const {
     v.frz = fine_ok ? frz : 0u;
     v.ffine = fine_ok ? ffine : 0.0f;
     v.ftile = fine_ok ? ftile : 0;
-    v.fband = (fine_ok && ftile == 2) ? frec.as<const uint16_t>() : nullptr;
+    v.fband = !(fine_ok && ftile == 2) ? nullptr
+              : (fband_ok && fan_band)   ? fband2.as<const uint16_t>()
+                                         : frec.as<const uint16_t>();
     v.fzc = (float)c;
     v.wpack = fine_ok ? wpack : 0;
     v.fzo = (float)v.oz;
@@ -709,6 +711,7 @@ int build_index(pcp_ctx *ctx, GridIndex &g, const pcp_cloud_view &v, double r_q,
     g.blk_fail = false;
     g.fine_ok = false;
     g.fpiv_ok = false;
+    g.fband_ok = false;
     g.fine_fail = false;
     // 1. the raw AoS bytes (the PointCloud2 data blob), device-readable: given by the caller,
     //    read in place from the pinned ring (message-sized), or DMA'd into ctx->stage

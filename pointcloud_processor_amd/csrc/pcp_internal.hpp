@@ -140,7 +140,9 @@ struct GridView {               // POD passed to kernels by value
     float fus_off, ffine;
     int32_t ftile;              // records in 4 x 4 xy tiles (1) or split (2), PCP_FINE_TILE
     // ftile 2: the record split in two arrays of 8 x 8 xy tiles -- the probe's 2-byte
-    // thresholds (one 128-byte line per tile) and the 4-byte walk start, read by candidates only
+    // thresholds (one 128-byte line per tile) and the 4-byte walk start, read by candidates only.
+    // fband is the thresholds' tight twin (pcp_fan_band.hpp, DESIGN.md §5 Skip 7: the same
+    // layout, never looser), or the specified array itself (PCP_FAN_BAND=0, or no twin built)
     const uint16_t *fband;
     const uint32_t *fstart;     // fskip 1: walk start (28 bits) | skip (4 bits, << 28): entries
                                 // of the run at or above oz + (iz + 1.5) c, skipped by a
@@ -174,7 +176,7 @@ struct GridIndex {
     double c = 0.0;
     int32_t nx = 0, ny = 0, nz = 0;
     double bmin[3] = {0, 0, 0}, bmax[3] = {0, 0, 0};
-    DevBuf pts, start, occ2, occz, bstart, bpts, frec, wpts, fpiv;
+    DevBuf pts, start, occ2, occz, bstart, bpts, frec, wpts, fpiv, fband2;
     bool occz_ok = false;
     bool blk_ok = false;         // block-major copy built (bstart / bpts)
     bool blk_fail = false;       // copy unavailable for this index (size cap or allocation
@@ -191,6 +193,9 @@ struct GridIndex {
     bool fpiv_ok = false;        // pivot table built (fpiv; with the split records)
     bool fan_pivot = true;       // the fan march tests a window's pivot before its walk
                                  // (PCP_FAN_PIVOT, set once by pcp_create; release() keeps it)
+    bool fband_ok = false;       // the thresholds' tight twin built (fband2; with the split records)
+    bool fan_band = true;        // the march's probe reads the twin (pcp_fan_band.hpp;
+                                 // PCP_FAN_BAND, set once by pcp_create; release() keeps it)
     float fan_clip_e = 1.0f / 64.0f;   // clip slack in samples, kClipSlack of pcp_fan_clip.hpp
                                  // (PCP_FAN_CLIP=0: 1; set once by pcp_create; release() keeps it)
     size_t fstart_off = 0;       // ftile 2: byte offset of the start array inside frec
@@ -207,7 +212,9 @@ struct GridIndex {
         frec.release();
         wpts.release();
         fpiv.release();
+        fband2.release();
         fpiv_ok = false;
+        fband_ok = false;
         occz_ok = false;
         blk_ok = false;
         blk_fail = false;
