@@ -458,6 +458,66 @@ int pcp_place_pair(pcp_ctx *ctx, const double *poses5, uint64_t n, const double 
 int pcp_place_pair_burst(pcp_ctx *ctx, const double *poses5, uint64_t n, const double zx120_pose5[5],
                          const pcp_vl_params *p, const pcp_pair_params *pp, int reps, double *ms_per_rep);
 
+/* 1-exchange refinement of a placement: a set of k sensors (greedy's answer, or a deployment as
+ * it stands) is improved by moving one sensor at a time to the pose that raises the total most,
+ * until no single move raises it.  S[p][c], Z[c], max(a, b), osum(v) and the separation expression
+ * as in pcp_place_sensors; fold(list) = Z with S[q] folded in, q in list order, by max.
+ *   1. s = start; T = osum(fold(s)) is *start_total, *start_covered = #{fold(s) > 0}.
+ *   2. One evaluation: for every slot i >= n_locked, L_i = fold(s without slot i) and
+ *      u[i][p] = osum(max(L_i, S[p])) with its count of positive elements; u[i][p] = -inf where
+ *      the move is inadmissible: slot i is locked (i < n_locked); p is in s (any slot, i included);
+ *      or, with min_separation > 0, p is closer than it to some s_j, j != i.  Only the incoming
+ *      pose is tested: the start set itself need not respect the separation, and a sensor that
+ *      stays is never moved or refused for it.  swap_totals[e] holds evaluation e's whole [k][n]
+ *      table.
+ *   3. The best entry is the first maximum in row-major order (slot ascending, then pose; strict
+ *      '>' from -inf).
+ *   4. If it is not > T (or there is none): *converged = 1, stop.  If max_moves moves are recorded
+ *      already: stop with *converged = 0.
+ *   5. Otherwise move m = (move_slot = i, move_from = s_i, move_to = p, move_total = u[i][p],
+ *      move_covered = its count); s_i = p, T = u[i][p]; evaluate again.
+ *   6. There are exactly *n_moves + 1 evaluations; T rises strictly with every move, so the
+ *      procedure ends.  Entries and tables from there on are not written.
+ *   7. selected = s, *total = T, *covered = its count; cell_score = fold(s); cell_owner = the slot
+ *      whose fold raised the cell, in slot order, or PCP_OWNER_ZX120 / PCP_OWNER_NONE (ties keep
+ *      the earlier owner).
+ * A set no single move improves is "1-exchange optimal"; it need not be the best set (two sensors
+ * may have to move together).  PCP_E_INVALID before any launch, nothing written: k outside 1 ..
+ * PCP_PLACE_MAX, n_locked outside 0 .. k, max_moves outside 0 .. PCP_REFINE_MAX_MOVES, reserved
+ * != 0, a start index >= n or listed twice, n > PCP_PAIR_MAX_POSES, a step table past
+ * PCP_MAX_STEPS, a null required pointer (everything not marked nullable; the move arrays may be
+ * null when max_moves == 0), a null context.  No cells: PCP_OK, selected = start, totals and
+ * counts 0, no moves, *converged = 1.  One synchronisation; deterministic (two calls give
+ * identical bytes); the caller's GridCell flags are neither read nor written; the call's scratch
+ * is its own, so the other queries on the context are unchanged by it. */
+#define PCP_REFINE_MAX_MOVES 64
+typedef struct pcp_refine_params {
+    int32_t k;                       /* sensors in the set, 1 .. PCP_PLACE_MAX */
+    int32_t n_locked;                /* slots 0 .. n_locked - 1 never move, 0 .. k */
+    int32_t max_moves;               /* 0 .. PCP_REFINE_MAX_MOVES */
+    int32_t reserved;                /* 0 */
+    double  min_separation;          /* metres in XY; <= 0: no constraint */
+    int64_t start[PCP_PLACE_MAX];    /* distinct indices into poses5, first k used */
+} pcp_refine_params;
+int pcp_place_refine(pcp_ctx *ctx, const double *poses5, uint64_t n, const double zx120_pose5[5],
+                     const pcp_vl_params *p, const pcp_refine_params *rp,
+                     int64_t *selected,        /* [k] the refined set                        */
+                     double *total, int32_t *covered,
+                     double *start_total, int32_t *start_covered,
+                     int32_t *move_slot, int64_t *move_from, int64_t *move_to, /* [max_moves] */
+                     double *move_total, int32_t *move_covered,                /* [max_moves] */
+                     double *swap_totals,      /* nullable [max_moves + 1][k][n]             */
+                     double *cell_score, int32_t *cell_owner,   /* nullable [n_cells] */
+                     int32_t *n_moves, int32_t *converged);
+
+/* Kernel timing of pcp_place_refine (the timing tool only): the query's setup (the scoring, the
+ * clamped rows, the start total) once, then `reps` repetitions of the start set's evaluation --
+ * preparation and evaluation launches, the last block's selection included, nothing committed --
+ * between two stream events; *ms_per_eval = the interval / reps.  n >= 1, cells present. */
+int pcp_place_refine_burst(pcp_ctx *ctx, const double *poses5, uint64_t n, const double zx120_pose5[5],
+                           const pcp_vl_params *p, const pcp_refine_params *rp, int reps,
+                           double *ms_per_eval);
+
 /* Dense ray fan (BASELINE configs[1]): per pose, n_az x n_el rays, ray (i, j) with local
  * direction (cos e_j cos a_i, cos e_j sin a_i, sin e_j), a_i = 2*pi*i/n_az,
  * e_j = el_min + (el_max-el_min)*(j+0.5)/n_el, rotated by the pose yaw, marched with

@@ -95,6 +95,16 @@ class PairParams(C.Structure):
                 ("fixed", C.c_int64 * PLACE_MAX)]
 
 
+REFINE_MAX_MOVES = 64   # PCP_REFINE_MAX_MOVES: moves one pcp_place_refine call records at most
+
+
+class RefineParams(C.Structure):
+    """pcp_refine_params."""
+    _fields_ = [("k", C.c_int32), ("n_locked", C.c_int32), ("max_moves", C.c_int32),
+                ("reserved", C.c_int32), ("min_separation", C.c_double),
+                ("start", C.c_int64 * PLACE_MAX)]
+
+
 SCAN_MAX_POSES = 64   # PCP_SCAN_MAX_POSES: poses one pcp_simulate_scan call casts (mask bits)
 
 
@@ -223,6 +233,12 @@ _SIGS = [
                                  _P, _P, _P]),
     ("pcp_place_pair_burst", C.c_int, [_P, _P, C.c_uint64, _P, C.POINTER(VlParams),
                                        C.POINTER(PairParams), C.c_int, C.POINTER(C.c_double)]),
+    ("pcp_place_refine", C.c_int, [_P, _P, C.c_uint64, _P, C.POINTER(VlParams),
+                                   C.POINTER(RefineParams), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                   _P, _P, _P, _P, _P]),
+    ("pcp_place_refine_burst", C.c_int, [_P, _P, C.c_uint64, _P, C.POINTER(VlParams),
+                                         C.POINTER(RefineParams), C.c_int,
+                                         C.POINTER(C.c_double)]),
     ("pcp_simulate_scan", C.c_int, [_P, _P, C.c_uint64, C.POINTER(FanParams), _P, C.c_uint64,
                                     C.POINTER(C.c_uint64), _P, _P, _P, _P, _P, C.c_uint64,
                                     C.POINTER(C.c_uint64), _P, C.POINTER(C.c_uint64)]),
@@ -1069,6 +1085,79 @@ class Context:
         self._check(self.lib.pcp_place_pair_burst(self.h, _ptr(poses), poses.shape[0], _ptr(zx),
                                                   C.byref(params), C.byref(pp), int(reps),
                                                   C.byref(ms)), "pcp_place_pair_burst")
+        return ms.value
+
+    @staticmethod
+    def _refine_params(start, n_locked, max_moves, min_separation, reserved,
+                       k=None) -> RefineParams:
+        start = [int(f) for f in start]
+        rp = RefineParams(len(start) if k is None else int(k), int(n_locked), int(max_moves),
+                          int(reserved), float(min_separation))
+        for i, f in enumerate(start[:PLACE_MAX]):
+            rp.start[i] = f
+        return rp
+
+    def place_refine(self, poses5, zx120_pose5, params: VlParams, start, n_locked: int = 0,
+                     max_moves: int = REFINE_MAX_MOVES, min_separation: float = 0.0,
+                     want_swap_totals: bool = False, want_cells: bool = False,
+                     reserved: int = 0) -> dict:
+        """pcp_place_refine: the set `start` of poses improved by single-sensor exchanges (every
+        unlocked sensor tried at every other pose with the rest held; the best exchange taken
+        while it raises the total).  -> dict: selected [k], total, covered, start_total,
+        start_covered, n_moves, converged (1: no single move raises the total; 0: max_moves ran
+        out first), move_slot / move_from / move_to / move_total / move_covered [n_moves], and on
+        request swap_totals [n_moves + 1, k, P] (-inf at inadmissible moves), cell_score /
+        cell_owner [n_cells] of the refined set."""
+        poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 5)
+        zx = np.ascontiguousarray(zx120_pose5, np.float64)
+        P = poses.shape[0]
+        rp = self._refine_params(start, n_locked, max_moves, min_separation, reserved)
+        k = max(min(rp.k, PLACE_MAX), 1)
+        mm = max(min(int(max_moves), REFINE_MAX_MOVES), 0)
+        sel = np.full(k, -1, np.int64)
+        tot, st = C.c_double(), C.c_double()
+        cov, sc, nm, cv = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        m_slot = np.zeros(max(mm, 1), np.int32)
+        m_from = np.zeros(max(mm, 1), np.int64)
+        m_to = np.zeros(max(mm, 1), np.int64)
+        m_tot = np.zeros(max(mm, 1), np.float64)
+        m_cov = np.zeros(max(mm, 1), np.int32)
+        dense = P <= PAIR_MAX_POSES   # (a refused call writes nothing: no table for it)
+        tab = (np.zeros((mm + 1, k, max(P, 1)), np.float64)
+               if want_swap_totals and dense else None)
+        C_ = self.cells_count() if want_cells else 0
+        cs = np.zeros(max(C_, 1), np.float64) if want_cells else None
+        co = np.zeros(max(C_, 1), np.int32) if want_cells else None
+        self._check(self.lib.pcp_place_refine(
+            self.h, _ptr(poses), P, _ptr(zx), C.byref(params), C.byref(rp), _ptr(sel),
+            C.byref(tot), C.byref(cov), C.byref(st), C.byref(sc), _ptr(m_slot), _ptr(m_from),
+            _ptr(m_to), _ptr(m_tot), _ptr(m_cov), _ptr(tab), _ptr(cs), _ptr(co), C.byref(nm),
+            C.byref(cv)), "pcp_place_refine")
+        n = nm.value
+        out = {"selected": sel, "total": tot.value, "covered": cov.value,
+               "start_total": st.value, "start_covered": sc.value, "n_moves": n,
+               "converged": cv.value, "move_slot": m_slot[:n].copy(),
+               "move_from": m_from[:n].copy(), "move_to": m_to[:n].copy(),
+               "move_total": m_tot[:n].copy(), "move_covered": m_cov[:n].copy()}
+        if want_swap_totals:
+            # (without cells nothing is evaluated: no table)
+            out["swap_totals"] = tab[:n + 1 if self.cells_count() else 0, :, :P].copy()
+        if want_cells:
+            out["cell_score"] = cs[:C_].copy()
+            out["cell_owner"] = co[:C_].copy()
+        return out
+
+    def place_refine_burst(self, poses5, zx120_pose5, params: VlParams, start, n_locked: int = 0,
+                           min_separation: float = 0.0, reps: int = 20) -> float:
+        """pcp_place_refine_burst -> ms per evaluation of the start set (preparation and
+        evaluation launches; the scoring and the setup once before the interval)."""
+        poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 5)
+        zx = np.ascontiguousarray(zx120_pose5, np.float64)
+        rp = self._refine_params(start, n_locked, 0, min_separation, 0)
+        ms = C.c_double(0.0)
+        self._check(self.lib.pcp_place_refine_burst(self.h, _ptr(poses), poses.shape[0], _ptr(zx),
+                                                    C.byref(params), C.byref(rp), int(reps),
+                                                    C.byref(ms)), "pcp_place_refine_burst")
         return ms.value
 
     def simulate_scan(self, poses5, fan: FanParams, want_dense: bool = False,

@@ -9,6 +9,9 @@
 //                         MAXD KMAX MINSEP OUT_SELECTED.i64 OUT_TOTALS.f64 OUT_REPORT.txt
 //   pcp_nodes_cli place_pair  (place's arguments; KMAX: the greedy placement it is compared with)
 //                         OUT_SELECTED: the exact answer; OUT_TOTALS: base, single, pair
+//   pcp_nodes_cli place_refine  (place's arguments) [N_LOCKED [MAX_MOVES]]: KMAX sensors placed
+//                         greedily, then refined by single-sensor exchanges; OUT_SELECTED: the
+//                         refined set; OUT_TOTALS: start, final, then the total after each move
 //   pcp_nodes_cli scan    TERRAIN.f32 TN POSES(5 per sensor) NAZ NEL MAXD OUT_SCANS.bin
 //                         OUT_OFFSETS.u64 OUT_BLIND.f32 OUT_MASK.u64
 //   pcp_nodes_cli drivable IN.f32 N STEP TF(7) R1(2) R2(2) OUT.i8
@@ -191,7 +194,8 @@ static int cmd_vlidar(Device &dev, char **a, int argc) {
 
 // one tick of the virtual-LiDAR node (vlidar's inputs), then KMAX mobile sensors placed greedily
 // among its candidates: the selected candidates, the totals after each and the placement's table
-static int cmd_place(Device &dev, char **a, bool exact_pair = false) {
+static int cmd_place(Device &dev, char **a, bool exact_pair = false, bool refine = false,
+                     int argc = 16) {
     const auto t = read_file(a[0]), ax = read_file(a[2]), c = read_file(a[4]),
                nr = read_file(a[5]);
     const size_t tn = std::strtoull(a[1], nullptr, 10), an = std::strtoull(a[3], nullptr, 10),
@@ -245,6 +249,48 @@ static int cmd_place(Device &dev, char **a, bool exact_pair = false) {
                     tick.candidates.size(), r.n_selected, (long long)r.pair[0],
                     (long long)r.pair[1], r.pair_covered, (long long)r.single, r.single_covered,
                     r.base_covered, r.total_cells);
+        return 0;
+    }
+    if (refine) {
+        // place_refine: the greedy placement, then single-sensor exchanges from it; the refined
+        // set, {start, final, after each move} totals and the refinement's table
+        if (placement.refine(dev, SimplifiedDualLidarOptimizer::Result{}, p, {0}).ran) return 3;
+        const auto greedy = placement.place(dev, tick, p);
+        if (!greedy.ran || greedy.rounds.empty()) {
+            std::fprintf(stderr, "place_refine: %s\n",
+                         greedy.ran ? "greedy placed nothing" : placement.lastError().c_str());
+            return 1;
+        }
+        std::vector<int64_t> start;
+        for (const auto &q : greedy.rounds) start.push_back(q.candidate);
+        const int n_locked = argc > 16 ? std::atoi(a[16]) : 0;
+        const int max_moves = argc > 17 ? std::atoi(a[17]) : PCP_REFINE_MAX_MOVES;
+        const auto r = placement.refine(dev, tick, p, start, n_locked, max_moves);
+        if (!r.ran) {
+            std::fprintf(stderr, "place_refine: %s\n", placement.lastError().c_str());
+            return 1;
+        }
+        std::vector<double> tot = {r.start_total, r.total};
+        std::string moves;
+        for (const auto &m : r.moves) {
+            tot.push_back(m.total);
+            char buf[96];
+            std::snprintf(buf, sizeof(buf), "%s[%d, %lld, %lld]", moves.empty() ? "" : ", ",
+                          m.slot, (long long)m.from, (long long)m.to);
+            moves += buf;
+        }
+        std::string sel;
+        for (size_t i = 0; i < r.selected.size(); ++i)
+            sel += (i ? ", " : "") + std::to_string((long long)r.selected[i]);
+        write_file(a[13], r.selected.data(), r.selected.size() * 8);
+        write_file(a[14], tot.data(), tot.size() * 8);
+        write_file(a[15], r.log.data(), r.log.size());
+        std::printf("{\"n_candidates\": %zu, \"k\": %zu, \"n_locked\": %d, \"n_moves\": %zu, "
+                    "\"converged\": %d, \"selected\": [%s], \"moves\": [%s], "
+                    "\"start_covered\": %d, \"covered\": %d, \"total_cells\": %d}\n",
+                    tick.candidates.size(), r.selected.size(), r.n_locked, r.moves.size(),
+                    r.converged ? 1 : 0, sel.c_str(), moves.c_str(), r.start_covered, r.covered,
+                    r.total_cells);
         return 0;
     }
     if (placement.place(dev, SimplifiedDualLidarOptimizer::Result{}, p).ran) return 3;   // no tick
@@ -687,7 +733,7 @@ int main(int argc, char **argv) {
         if (!hp || std::atoi(hp) != 0) setenv("HSA_ENABLE_INTERRUPT", "0", 0);
     }
     if (argc < 2) {
-        std::fprintf(stderr, "usage: pcp_nodes_cli filter|merge|vlidar|place|place_pair|scan|area|drivable|replay ...\n");
+        std::fprintf(stderr, "usage: pcp_nodes_cli filter|merge|vlidar|place|place_pair|place_refine|scan|area|drivable|replay ...\n");
         return 2;
     }
     const std::string cmd = argv[1];
@@ -696,6 +742,7 @@ int main(int argc, char **argv) {
                      : cmd == "vlidar" ? 14
                      : cmd == "place"  ? 16
                      : cmd == "place_pair" ? 16
+                     : cmd == "place_refine" ? 16
                      : cmd == "scan"   ? 10
                      : cmd == "area"   ? 10
                      : cmd == "drivable" ? 7
@@ -712,6 +759,8 @@ int main(int argc, char **argv) {
         if (cmd == "vlidar") return cmd_vlidar(dev, argv + 2, argc - 2);
         if (cmd == "place") return cmd_place(dev, argv + 2);
         if (cmd == "place_pair") return cmd_place(dev, argv + 2, /*exact_pair=*/true);
+        if (cmd == "place_refine")
+            return cmd_place(dev, argv + 2, /*exact_pair=*/false, /*refine=*/true, argc - 2);
         if (cmd == "scan") return cmd_scan(dev, argv + 2);
         if (cmd == "area") return cmd_area(dev, argv + 2);
         if (cmd == "drivable") return cmd_drivable(dev, argv + 2);

@@ -188,4 +188,111 @@ MobileLidarPlacement::PairResult MobileLidarPlacement::place_pair(
     return r;
 }
 
+std::string placement_refine_log(const MobileLidarPlacement::RefineResult &r) {
+    std::string log;
+    const int tc = r.total_cells;
+    auto pct = [tc](int v) { return tc > 0 ? (double)v / tc * 100.0 : 0.0; };
+    const char *rule = "========================================";
+    const char *thin = "----------------------------------------";
+    appendf(log, "%s", rule);
+    appendf(log, "Exchange Refinement (ZX120 + %zu Mobile, %d Locked)", r.selected.size(),
+            r.n_locked);
+    appendf(log, "%s", rule);
+    appendf(log, "Total Score (start set): %.2f", r.start_total);
+    appendf(log, "  Covered cells: %d of %d (%.1f%%)", r.start_covered, tc, pct(r.start_covered));
+    for (size_t i = 0; i < r.moves.size(); ++i) {
+        const auto &m = r.moves[i];
+        appendf(log, "%s", thin);
+        appendf(log, "Move %zu: LiDAR %d from (%.2f, %.2f, %.2f) [candidate %lld] to "
+                     "(%.2f, %.2f, %.2f) [candidate %lld]",
+                i + 1, m.slot + 1, m.from_pos.x, m.from_pos.y, m.from_pos.z, (long long)m.from,
+                m.to_pos.x, m.to_pos.y, m.to_pos.z, (long long)m.to);
+        appendf(log, "  Total Score: %.2f (gain %.2f)", m.total, m.gain);
+        appendf(log, "  Covered cells: %d of %d (%.1f%%)", m.covered, tc, pct(m.covered));
+    }
+    appendf(log, "%s", thin);
+    if (r.converged)
+        appendf(log, "1-exchange optimal after %zu moves: no single move raises the total",
+                r.moves.size());
+    else
+        appendf(log, "stopped after %zu moves: a better single move remains", r.moves.size());
+    appendf(log, "  Total Score: %.2f (gain over start %.2f)", r.total, r.total - r.start_total);
+    appendf(log, "  Covered cells: %d of %d (%.1f%%)", r.covered, tc, pct(r.covered));
+    for (size_t i = 0; i < r.placed.size(); ++i) {
+        const auto &p = r.placed[i];
+        appendf(log, "Mobile LiDAR %zu Position: (%.2f, %.2f, %.2f)  [candidate %lld]%s", i + 1,
+                p.x, p.y, p.z, (long long)r.selected[i], (int)i < r.n_locked ? "  (locked)" : "");
+    }
+    appendf(log, "%s", rule);
+    return log;
+}
+
+MobileLidarPlacement::RefineResult MobileLidarPlacement::refine(
+    Device &dev, const SimplifiedDualLidarOptimizer::Result &tick,
+    const SimplifiedDualLidarOptimizer::Params &vl, const std::vector<int64_t> &start,
+    int n_locked, int max_moves) {
+    RefineResult r;
+    err_.clear();
+    if (!tick.ran) return r;
+    if (start.empty() || start.size() > PCP_PLACE_MAX) {
+        err_ = "refine: the start set holds no sensor or more than PCP_PLACE_MAX";
+        return r;
+    }
+    const double zx[5] = {tick.zx120.x, tick.zx120.y, tick.zx120.z, tick.zx120.pitch,
+                          tick.zx120.yaw};
+    const pcp_vl_params p{vl.grid_resolution, vl.sensor_height, vl.search_radius, vl.max_distance,
+                          vl.num_candidates,  vl.vertical_layers};
+    pcp_refine_params rp{};
+    rp.k = (int32_t)start.size();
+    rp.n_locked = n_locked;
+    rp.max_moves = max_moves;
+    rp.min_separation = p_.min_separation;
+    for (size_t i = 0; i < start.size(); ++i) rp.start[i] = start[i];
+    const size_t n = tick.candidates.size();
+    std::vector<double> poses(5 * n);
+    for (size_t i = 0; i < n; ++i) {
+        const auto &c = tick.candidates[i];
+        poses[5 * i] = c.x;
+        poses[5 * i + 1] = c.y;
+        poses[5 * i + 2] = c.z;
+        poses[5 * i + 3] = c.pitch;
+        poses[5 * i + 4] = c.yaw;
+    }
+    int64_t sel[PCP_PLACE_MAX], from[PCP_REFINE_MAX_MOVES], to[PCP_REFINE_MAX_MOVES];
+    int32_t slot[PCP_REFINE_MAX_MOVES], cov[PCP_REFINE_MAX_MOVES], nm = 0, conv = 0;
+    double tot[PCP_REFINE_MAX_MOVES];
+    if (pcp_place_refine(dev.ctx(), poses.data(), n, zx, &p, &rp, sel, &r.total, &r.covered,
+                         &r.start_total, &r.start_covered, slot, from, to, tot, cov, nullptr,
+                         nullptr, nullptr, &nm, &conv) != PCP_OK) {
+        err_ = dev.error();
+        return r;
+    }
+    r.ran = true;
+    r.converged = conv != 0;
+    r.start = start;
+    r.n_locked = n_locked;
+    r.total_cells = tick.report.total_cells;
+    double before = r.start_total;
+    for (int32_t m = 0; m < nm; ++m) {
+        Move q;
+        q.slot = slot[m];
+        q.from = from[m];
+        q.to = to[m];
+        q.from_pos = tick.candidates[(size_t)from[m]];
+        q.to_pos = tick.candidates[(size_t)to[m]];
+        q.total = tot[m];
+        q.gain = tot[m] - before;
+        q.covered = cov[m];
+        before = tot[m];
+        r.moves.push_back(q);
+    }
+    for (size_t i = 0; i < start.size(); ++i) {
+        r.selected.push_back(sel[i]);
+        r.placed.push_back(tick.candidates[(size_t)sel[i]]);
+        r.placed.back().total_score = r.total;
+    }
+    r.log = placement_refine_log(r);
+    return r;
+}
+
 }  // namespace pcp

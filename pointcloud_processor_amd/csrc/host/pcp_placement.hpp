@@ -68,6 +68,38 @@ class MobileLidarPlacement {
     PairResult place_pair(Device &dev, const SimplifiedDualLidarOptimizer::Result &tick,
                           const SimplifiedDualLidarOptimizer::Params &vl,
                           const std::vector<int64_t> &fixed = {}, const Result *greedy = nullptr);
+
+    // 1-exchange refinement (pcp_place_refine): the set `start` of the tick's candidates -- a
+    // place() answer, or a deployment as it stands -- improved by moving one sensor at a time to
+    // the candidate that raises the total most, until no single move raises it.
+    struct Move {
+        int32_t slot = -1;             // which sensor of the set moved
+        int64_t from = -1, to = -1;    // candidate indices
+        SimplifiedDualLidarOptimizer::LidarPosition from_pos, to_pos;
+        double total = 0;              // the set's total after the move
+        double gain = 0;               // total - the total before it
+        int32_t covered = 0;
+    };
+    struct RefineResult {
+        bool ran = false;              // false: the tick did not run, or the call failed
+        bool converged = false;        // no single move raises the total (1-exchange optimal);
+                                       // false: max_moves ran out first
+        std::vector<int64_t> start, selected;   // candidate indices by slot
+        int32_t n_locked = 0;
+        double start_total = 0, total = 0;
+        int32_t start_covered = 0, covered = 0;
+        int32_t total_cells = 0;
+        std::vector<Move> moves;
+        std::vector<SimplifiedDualLidarOptimizer::LidarPosition> placed;   // the refined set by
+                                                                            // slot, total_score = total
+        std::string log;
+    };
+    // min_separation is params()'s and is tested for the incoming candidate of a move only;
+    // slots 0 .. n_locked - 1 never move; num_mobile_lidars plays no part
+    RefineResult refine(Device &dev, const SimplifiedDualLidarOptimizer::Result &tick,
+                        const SimplifiedDualLidarOptimizer::Params &vl,
+                        const std::vector<int64_t> &start, int n_locked = 0,
+                        int max_moves = PCP_REFINE_MAX_MOVES);
     const std::string &lastError() const { return err_; }
 
    private:
@@ -81,5 +113,8 @@ std::string placement_log(const MobileLidarPlacement::Result &r);
 // gain over the single, and (greedy given, two sensors placed) its gain over greedy's two
 std::string placement_pair_log(const MobileLidarPlacement::PairResult &r,
                                const MobileLidarPlacement::Result *greedy = nullptr);
+// the refinement's table in the same format: the start set, every move (slot, from and to with
+// their positions, the gain), and either "1-exchange optimal" or "stopped after N moves"
+std::string placement_refine_log(const MobileLidarPlacement::RefineResult &r);
 
 }  // namespace pcp

@@ -781,6 +781,9 @@ void pcp_destroy(pcp_ctx *ctx) {
     ctx->pair_d.release();
     ctx->pair_m.release();
     ctx->pair_host.release();
+    ctx->refine_d.release();
+    ctx->refine_m.release();
+    ctx->refine_host.release();
     ctx->vscan_d.release();
     ctx->vscan_host.release();
     if (ctx->area_stream) (void)hipStreamDestroy(ctx->area_stream);

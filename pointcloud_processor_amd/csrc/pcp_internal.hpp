@@ -362,6 +362,11 @@ struct pcp_ctx {
     // landing of its one download (its own, as the placement's)
     pcp::DevBuf pair_d, pair_m;
     pcp::PinnedBuf pair_host;
+    // pcp_place_refine (pcp_refine.hip): its state, cell_score / cell_owner and the evaluations'
+    // tables (refine_d), the clamped rows, the leave-one-out slot rows and the per-block bests
+    // (refine_m), and the pinned landing of its one download (its own, as the pair's)
+    pcp::DevBuf refine_d, refine_m;
+    pcp::PinnedBuf refine_host;
     // pcp_simulate_scan (pcp_scan.hip): wave bases, offsets, records, dense images, point mask and
     // counts, and the pinned landing of its downloads (its own: the fan's buffers stay as
     // pcp_raycast_fan leaves and expects them)

@@ -1,0 +1,423 @@
+"""pcp_place_refine (1-exchange refinement of a multi-sensor placement) on the 91-candidate tick.
+
+Every case asks for the evaluations' tables and the cells and is checked twice:
+  (a) bit for bit against tests/refine_ref.py run on ctx.score_matrix's own output for the same
+      arguments: every evaluation's [k, P] table with its -inf pattern, the move records, the
+      totals, the counts, cell_score's bits and cell_owner;
+  (b) against refine_ref on the oracle's matrix: moves, selections, counts and owners equal, the
+      totals under parity.assert_totals.  (b) applies where nothing on the oracle side is decided
+      by less than GAP -- the device matrix differs from glibc's by a few ulps in a few cells
+      (tests/parity.py) -- and the case asserts that (refine_ref's decision_gap); the smallest
+      such gap of the full-tick cases is 0.40 (greedy's sixteen sensors).
+The oracle's matrix is computed once for the whole tick; cell / pose subsets are slices of it."""
+import json
+import subprocess
+from pathlib import Path
+
+import numpy as np
+import parity
+import pytest
+import refine_ref
+
+from pointcloud_processor_amd import _abi
+
+pytestmark = pytest.mark.gpu
+
+ROOT = Path(__file__).resolve().parents[1]
+CLI = ROOT / "pointcloud_processor_amd" / "_lib" / "pcp_nodes_cli"
+GAP = 0.1
+TILE = 16     # poses per block of an evaluation (kRTile)
+CHUNK = 64    # cells per staged chunk of an evaluation (kRC)
+PREP = 256    # cells per preparation block and per step of the start total's chain (kRT)
+G6 = [40, 41, 48, 32, 49, 56]                  # greedy k = 6
+G6S = [40, 41, 56, 24, 57, 46]                 # greedy k = 6 at 2 m
+G8S = G6S + [30, 35]                           # greedy k = 8 at 2 m
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float64).view(np.uint64)
+
+
+@pytest.fixture(scope="module")
+def tick(oracle, scene, cells, aux):
+    """One context with the scene loaded, the tick's 91 candidates and the oracle's matrix."""
+    params = _abi.default_vl_params()
+    with _abi.Context(0) as ctx:
+        ctx.set_terrain(scene.terrain, point_step=32)
+        ctx.set_aux_cloud(aux, point_step=32)
+        ctx.set_cells(cells.xyz, cells.normals)
+        poses = np.ascontiguousarray(
+            ctx.generate_candidates(cells.grid_bbox, params, scene.zx120_pose5))
+        assert poses.shape == (91, 5) and cells.xyz.shape[0] == 3704
+        Tc, A = oracle.Cloud(scene.terrain), oracle.Cloud(aux)
+        o_S, o_Z = oracle.score_matrix(Tc, A, cells.xyz, cells.normals, poses, scene.zx120_pose5,
+                                       oracle.vl_params())
+        yield {"ctx": ctx, "poses": poses, "params": params, "S": o_S, "Z": o_Z,
+               "zx": scene.zx120_pose5, "cells": cells}
+        ctx.set_cells(cells.xyz, cells.normals)
+
+
+def _same(got, ref, exact):
+    """The decisions of got and ref are equal; with `exact` so is every bit."""
+    np.testing.assert_array_equal(got["selected"], ref["selected"])
+    for k in ("n_moves", "converged", "covered", "start_covered"):
+        assert got[k] == ref[k], (k, got[k], ref[k])
+    for k in ("move_slot", "move_from", "move_to", "move_covered", "cell_owner"):
+        assert got[k].dtype == ref[k].dtype, k
+        np.testing.assert_array_equal(got[k], ref[k], err_msg=k)
+    assert got["swap_totals"].shape == ref["swap_totals"].shape
+    np.testing.assert_array_equal(np.isfinite(got["swap_totals"]), np.isfinite(ref["swap_totals"]))
+    dead = ~np.isfinite(ref["swap_totals"])
+    np.testing.assert_array_equal(got["swap_totals"][dead], ref["swap_totals"][dead])   # -inf
+    if exact:
+        for k in ("swap_totals", "move_total", "cell_score", "total", "start_total"):
+            np.testing.assert_array_equal(_bits(got[k]), _bits(ref[k]), err_msg=k)
+
+
+def _case(tick, pose_idx, Cn, start, n_locked=0, max_moves=64, sep=0.0, oracle_side=True):
+    """place_refine over poses[pose_idx] and cells[:Cn], checked (a) and, with oracle_side, (b);
+    returns (device result, device-side restatement)."""
+    ctx, cells = tick["ctx"], tick["cells"]
+    poses = np.ascontiguousarray(tick["poses"][pose_idx])
+    Pn = poses.shape[0]
+    ctx.set_cells(cells.xyz[:Cn], cells.normals[:Cn])
+    got = ctx.place_refine(poses, tick["zx"], tick["params"], start, n_locked, max_moves, sep,
+                           want_swap_totals=True, want_cells=True)
+    d_S, d_Z = ctx.score_matrix(poses, tick["zx"], tick["params"])
+    assert d_S.shape == (Pn, Cn)
+    # (a) exact, on the device's own matrix
+    ref = refine_ref.place_refine(d_S, d_Z, poses[:, :2], start, n_locked, max_moves, sep)
+    assert got["swap_totals"].shape == (got["n_moves"] + 1, len(start), Pn)
+    _same(got, ref, exact=True)
+    if not oracle_side:
+        return got, ref
+    # (b) the oracle's matrix
+    orc = refine_ref.place_refine(tick["S"][pose_idx][:, :Cn], tick["Z"][:Cn], poses[:, :2], start,
+                                  n_locked, max_moves, sep)
+    assert orc["decision_gap"] > GAP, orc["decision_gap"]   # nothing hangs on ulps
+    _same(got, orc, exact=False)
+    live = np.isfinite(orc["swap_totals"])
+    print(f"C={Cn} P={Pn} start={list(start)} locked={n_locked} sep={sep}: tables",
+          parity.totals_report(got["swap_totals"][live], orc["swap_totals"][live])
+          if live.any() else "empty")
+    if live.any():
+        parity.assert_totals(got["swap_totals"][live], orc["swap_totals"][live])
+    parity.assert_totals(np.concatenate([[got["start_total"], got["total"]], got["move_total"]]),
+                         np.concatenate([[orc["start_total"], orc["total"]], orc["move_total"]]))
+    return got, ref
+
+
+@pytest.fixture(scope="module")
+def g16(tick):
+    ctx, cells = tick["ctx"], tick["cells"]
+    ctx.set_cells(cells.xyz, cells.normals)
+    g = ctx.place_sensors(tick["poses"], tick["zx"], tick["params"], 16)
+    assert g["n_selected"] == 16
+    return g["selected"].tolist()
+
+
+# start, n_locked, sep -> selected, moves (None: only their number, the last entry)
+FULL = [
+    ([40, 41], 0, 0.0, [48, 41], [(0, 40, 48)], 1),
+    (G6, 0, 0.0, [40, 41, 48, 33, 49, 56], [(3, 32, 33)], 1),
+    (G6S, 0, 2.0, [40, 41, 56, 23, 57, 46], [(3, 24, 23)], 1),
+    ([0, 1, 2, 3], 0, 0.0, [40, 41, 48, 32], None, 4),
+    (list(range(8)), 0, 3.0, [40, 49, 77, 3, 4, 26, 45, 64], None, 6),
+    ([90, 89, 88, 87], 0, 0.0, [40, 41, 48, 32], None, 4),
+    ([0, 1, 2, 3], 2, 0.0, [0, 1, 48, 41], [(2, 2, 40), (3, 3, 41), (2, 40, 48)], 3),
+    ([0], 0, 0.0, [40], [(0, 0, 40)], 1),
+    ([40, 41], 1, 0.0, [40, 41], [], 0),
+]
+
+
+@pytest.mark.parametrize("start,n_locked,sep,selected,moves,n_moves", FULL)
+def test_full_tick(tick, start, n_locked, sep, selected, moves, n_moves):
+    got, _ = _case(tick, slice(None), 3704, start, n_locked, 64, sep)
+    assert got["selected"].tolist() == selected and got["converged"] == 1
+    assert got["n_moves"] == n_moves
+    if moves is not None:
+        assert list(zip(got["move_slot"].tolist(), got["move_from"].tolist(),
+                        got["move_to"].tolist())) == moves
+    assert np.all(np.diff(np.concatenate([[got["start_total"]], got["move_total"]])) > 0)
+    if n_moves:
+        assert got["total"] == got["move_total"][-1]
+    else:
+        assert got["total"] == got["start_total"] and got["covered"] == got["start_covered"]
+
+
+def test_full_tick_greedy_sixteen(tick, g16):
+    """Greedy's sixteen sensors are 1-exchange optimal on this tick (by 0.40 on the oracle's
+    matrix): one evaluation of 16 x 91 rows, no move."""
+    got, _ = _case(tick, slice(None), 3704, g16, 0, 64, 0.0)
+    assert got["n_moves"] == 0 and got["converged"] == 1 and got["selected"].tolist() == g16
+    assert int(np.isfinite(got["swap_totals"]).sum()) == 16 * (91 - 16)
+
+
+def test_full_tick_narrow_decision(tick):
+    """Greedy's eight sensors at 2 m: slot 3 moves 24 -> 23, decided by 0.022 on the oracle's
+    matrix -- too little for (b), so (a) alone, and the oracle's answer printed."""
+    got, _ = _case(tick, slice(None), 3704, G8S, 0, 64, 2.0, oracle_side=False)
+    orc = refine_ref.place_refine(tick["S"], tick["Z"], tick["poses"][:, :2], G8S, 0, 64, 2.0)
+    assert orc["decision_gap"] < GAP
+    print("device", got["selected"].tolist(), "oracle", orc["selected"].tolist())
+
+
+@pytest.mark.parametrize("Cn", [1, CHUNK - 1, CHUNK, CHUNK + 1, PREP - 1, PREP, PREP + 1, 1153])
+def test_cell_prefixes(tick, Cn):
+    """Cell prefixes around the staged chunk and the preparation's block (the start total's chain
+    step).  Short prefixes leave exact ties between poses, so these are held to (a)."""
+    _case(tick, slice(None), Cn, [0, 40, 3], oracle_side=False)
+
+
+@pytest.mark.parametrize("Pn", [2, TILE - 1, TILE, TILE + 1, 2 * TILE + 1, 100])
+def test_pose_counts(tick, Pn):
+    """Pose counts around the block's poses; 100 > 91 wraps round: exact duplicate rows in
+    different blocks, ties decided by index."""
+    start = [0, Pn - 1] if Pn > 2 else [1]
+    got, _ = _case(tick, np.arange(Pn) % 91, 3704, start, oracle_side=False)
+    if Pn == 100:
+        # poses 0 .. 8 and 91 .. 99 are the same rows: a set never gains by holding both copies
+        assert sorted(got["selected"].tolist()) == [41, 48]
+        assert (got["move_to"] < 91).all()
+
+
+@pytest.mark.parametrize("k,n_locked", [(1, 0), (1, 1), (2, 0), (2, 1), (2, 2), (15, 0), (15, 1),
+                                        (16, 0), (16, 1), (16, 16)])
+def test_k_and_locking(tick, k, n_locked):
+    start = [(7 * i + 3) % 91 for i in range(k)]   # distinct: 7 and 91 share the factor 7 only
+    start = list(dict.fromkeys(start + list(range(91))))[:k]
+    got, _ = _case(tick, slice(None), 3704, start, n_locked, 64, oracle_side=False)
+    assert got["selected"].tolist()[:n_locked] == start[:n_locked]
+    assert not np.isfinite(got["swap_totals"][:, :n_locked]).any()
+    if n_locked == k:
+        assert got["n_moves"] == 0 and got["converged"] == 1
+
+
+def test_max_moves(tick):
+    # 0: one evaluation; converged iff the start set is optimal already
+    got, _ = _case(tick, slice(None), 3704, [0, 1, 2, 3], 0, 0)
+    assert got["n_moves"] == 0 and got["converged"] == 0 and got["swap_totals"].shape[0] == 1
+    assert got["selected"].tolist() == [0, 1, 2, 3] and got["total"] == got["start_total"]
+    got, _ = _case(tick, slice(None), 3704, [48, 41], 0, 0)
+    assert got["n_moves"] == 0 and got["converged"] == 1
+    # 1: the first move of four, then the evaluation that finds a second
+    got, _ = _case(tick, slice(None), 3704, [0, 1, 2, 3], 0, 1)
+    assert got["n_moves"] == 1 and got["converged"] == 0 and got["swap_totals"].shape[0] == 2
+    # exactly as many as needed: the last evaluation still runs and finds nothing
+    got, _ = _case(tick, slice(None), 3704, [0, 1, 2, 3], 0, 4)
+    assert got["n_moves"] == 4 and got["converged"] == 1 and got["swap_totals"].shape[0] == 5
+
+
+def test_separations(tick):
+    xy = tick["poses"][:, :2]
+    d = np.hypot(xy[40, 0] - xy[41, 0], xy[40, 1] - xy[41, 1])
+    assert d < 3.0   # greedy's first two are 2.90 m apart
+    # a start set that violates the separation itself: accepted, only incoming poses are tested,
+    # and the two that are too close stay where they are
+    got, _ = _case(tick, slice(None), 3704, [40, 41, 0], 0, 64, 3.0)
+    assert got["n_moves"] >= 1 and got["selected"].tolist()[:2] == [40, 41]
+    # locked sensors that block candidates: everything within 5 m of poses 40 and 48 is -inf
+    got, _ = _case(tick, slice(None), 3704, [40, 48, 0], 2, 64, 5.0)
+    near = np.zeros(91, bool)
+    for q in (40, 48):
+        dx, dy = xy[:, 0] - xy[q, 0], xy[:, 1] - xy[q, 1]
+        near |= dx * dx + dy * dy < 25.0
+    assert near.sum() > 10
+    assert not np.isfinite(got["swap_totals"][:, 2, near]).any()
+    assert np.isfinite(got["swap_totals"][0, 2, ~near]).sum() == (~near).sum() - 1   # pose 0
+
+
+def test_agrees_with_the_existing_kernels(tick):
+    ctx, cells = tick["ctx"], tick["cells"]
+    ctx.set_cells(cells.xyz, cells.normals)
+    poses, zx, params = tick["poses"], tick["zx"], tick["params"]
+    g = ctx.place_sensors(poses, zx, params, 2, want_round_totals=True)
+    assert g["selected"].tolist() == [40, 41]
+    r = ctx.place_refine(poses, zx, params, [40, 41], want_swap_totals=True)
+    assert _bits(r["start_total"])[0] == _bits(g["total_after"][1])[0]
+    assert r["start_covered"] == g["covered_after"][1]
+    # slot 1 exchanged with pose 40 held: greedy's second round
+    live = np.isfinite(g["round_totals"][1])
+    assert live.sum() == 90
+    live[41] = False   # (in the set: no move)
+    np.testing.assert_array_equal(_bits(r["swap_totals"][0, 1, live]),
+                                  _bits(g["round_totals"][1][live]))
+    # slot 0 exchanged with pose 41 held: the singles of the pair search beside a fixed 41
+    e = ctx.place_pair(poses, zx, params, fixed=[41], want_single_totals=True)
+    adm = np.isfinite(e["single_totals"])
+    adm[40] = False
+    assert adm.sum() == 89
+    np.testing.assert_array_equal(_bits(r["swap_totals"][0, 0, adm]),
+                                  _bits(e["single_totals"][adm]))
+    # the refined pair is the exact pair
+    x = ctx.place_pair(poses, zx, params)
+    assert sorted(r["selected"].tolist()) == x["best_pair"].tolist()
+    assert _bits(r["total"])[0] == _bits(x["pair_total"])[0]
+    assert r["covered"] == x["pair_covered"]
+
+
+def test_isolation(tick):
+    """pcp_score_poses before and after the refinement on one context: identical; the caller's
+    flags are not touched; the scratch allocations settle after the first call; two calls give
+    equal bytes, with the other placement calls in between or not."""
+    ctx, cells = tick["ctx"], tick["cells"]
+    ctx.set_cells(cells.xyz, cells.normals)
+    poses, zx, params = tick["poses"], tick["zx"], tick["params"]
+    f0 = np.zeros(3704, np.uint8)
+    t0, c0, r0 = ctx.score_poses(poses, zx, params, f0)
+    held = f0.copy()
+    kw = dict(start=[0, 1, 2, 3], n_locked=1, min_separation=2.0, want_swap_totals=True,
+              want_cells=True)
+    g0 = ctx.place_sensors(poses, zx, params, 8, 2.0, want_round_totals=True, want_cells=True)
+    p0 = ctx.place_pair(poses, zx, params, fixed=[40], want_single_totals=True, want_cells=True)
+    first = ctx.place_refine(poses, zx, params, **kw)
+    assert first["n_moves"] >= 2
+    np.testing.assert_array_equal(f0, held)
+    settled = _abi.alloc_stats()
+    again = ctx.place_refine(poses, zx, params, **kw)
+    assert _abi.alloc_stats() == settled
+    g1 = ctx.place_sensors(poses, zx, params, 8, 2.0, want_round_totals=True, want_cells=True)
+    p1 = ctx.place_pair(poses, zx, params, fixed=[40], want_single_totals=True, want_cells=True)
+    third = ctx.place_refine(poses, zx, params, **kw)
+    for k in first:
+        for other in (again, third):
+            a, b = np.asarray(first[k]), np.asarray(other[k])
+            assert a.dtype == b.dtype and a.tobytes() == b.tobytes(), k
+    for a, b in ((g0, g1), (p0, p1)):
+        for k in a:
+            np.testing.assert_array_equal(a[k], b[k])
+    f1 = np.zeros(3704, np.uint8)
+    t1, c1, r1 = ctx.score_poses(poses, zx, params, f1)
+    np.testing.assert_array_equal(_bits(t0), _bits(t1))
+    np.testing.assert_array_equal(c0, c1)
+    np.testing.assert_array_equal(f0, f1)
+    assert r0.as_dict() == r1.as_dict()
+    assert _abi.alloc_stats() == settled
+
+
+def test_refusals(tick):
+    ctx, cells = tick["ctx"], tick["cells"]
+    ctx.set_cells(cells.xyz, cells.normals)
+    poses, zx, params = tick["poses"], tick["zx"], tick["params"]
+    ctx.profile(True)
+    ctx.profile_reset()
+    try:
+        bad = [{"start": list(range(_abi.PLACE_MAX + 1))},   # k past PCP_PLACE_MAX
+               {"start": []},                                # k = 0
+               {"start": [1], "reserved": 1},
+               {"start": [1, 2], "n_locked": 3}, {"start": [1, 2], "n_locked": -1},
+               {"start": [1], "max_moves": _abi.REFINE_MAX_MOVES + 1},
+               {"start": [1], "max_moves": -1},
+               {"start": [91]}, {"start": [-1]},             # no pose of the call
+               {"start": [3, 40, 3]}]                        # listed twice
+        for kw in bad:
+            with pytest.raises(_abi.PcpError) as e:
+                ctx.place_refine(poses, zx, params, **kw)
+            assert e.value.code == _abi.PCP_E_INVALID, kw
+        many = np.ascontiguousarray(poses[np.arange(_abi.PAIR_MAX_POSES + 1) % 91])
+        with pytest.raises(_abi.PcpError) as e:
+            ctx.place_refine(many, zx, params, [0])
+        assert e.value.code == _abi.PCP_E_INVALID
+        with pytest.raises(_abi.PcpError) as e:   # no poses: no start index is one of them
+            ctx.place_refine(poses[:0], zx, params, [0])
+        assert e.value.code == _abi.PCP_E_INVALID
+        far = _abi.default_vl_params(max_distance=0.5 + 0.3 * (_abi.MAX_STEPS + 2))
+        with pytest.raises(_abi.PcpError) as e:
+            ctx.place_refine(poses, zx, far, [0])
+        assert e.value.code == _abi.PCP_E_INVALID
+        # a null required pointer: past the binding, at the C entry; nothing is written
+        rp = _abi.RefineParams(1, 0, 2, 0, 0.0)
+        d = [_abi.C.c_double(-7.0) for _ in range(2)]
+        i = [_abi.C.c_int32(-7) for _ in range(4)]
+        sel = (_abi.C.c_int64 * 1)(-7)
+        m32 = [(_abi.C.c_int32 * 2)(-7, -7) for _ in range(2)]
+        m64 = [(_abi.C.c_int64 * 2)(-7, -7) for _ in range(2)]
+        mt = (_abi.C.c_double * 2)(-7.0, -7.0)
+        zxa = np.ascontiguousarray(zx, np.float64)
+        B = _abi.C.byref
+
+        def raw(conv, slot):
+            return ctx.lib.pcp_place_refine(
+                ctx.h, _abi._ptr(poses), 91, _abi._ptr(zxa), B(params), B(rp), sel, B(d[0]),
+                B(i[0]), B(d[1]), B(i[1]), slot, m64[0], m64[1], mt, m32[1], None, None, None,
+                B(i[2]), conv)
+        assert raw(None, m32[0]) == _abi.PCP_E_INVALID
+        assert raw(B(i[3]), None) == _abi.PCP_E_INVALID   # max_moves > 0 needs the move arrays
+        assert list(sel) == [-7] and all(x.value == -7.0 for x in d)
+        assert all(x.value == -7 for x in i)
+        for k in ("score_cells", "pose_sum", "place_sensors"):   # nothing was launched
+            assert ctx.profile_get(k)[1] == 0
+        ctx.place_refine(poses, zx, params, [0, 1])
+        assert ctx.profile_get("score_cells")[1] >= 1   # the refinement scores
+        assert ctx.profile_get("place_sensors")[1] == 0  # and launches no placement round
+    finally:
+        ctx.profile(False)
+    # no cells: nothing to cover, nothing to gain
+    ctx.set_cells(cells.xyz[:0], cells.normals[:0])
+    got = ctx.place_refine(poses, zx, params, [5, 3], want_swap_totals=True, want_cells=True)
+    assert got["n_moves"] == 0 and got["converged"] == 1 and got["selected"].tolist() == [5, 3]
+    assert got["total"] == 0.0 and got["start_total"] == 0.0
+    assert got["covered"] == 0 and got["start_covered"] == 0
+    assert got["cell_score"].size == 0 and got["swap_totals"].shape == (0, 2, 91)
+    ctx.set_cells(cells.xyz, cells.normals)
+
+
+def test_burst_times_an_evaluation(tick):
+    ctx, cells = tick["ctx"], tick["cells"]
+    ctx.set_cells(cells.xyz, cells.normals)
+    poses, zx, params = tick["poses"], tick["zx"], tick["params"]
+    ms = ctx.place_refine_burst(poses, zx, params, [40, 41], reps=3)
+    assert ms > 0.0
+    # the repetitions commit nothing: the call after it starts from its own state
+    got = ctx.place_refine(poses, zx, params, [40, 41])
+    assert got["selected"].tolist() == [48, 41] and got["n_moves"] == 1
+    with pytest.raises(_abi.PcpError) as e:
+        ctx.place_refine_burst(poses, zx, params, [40, 41], reps=0)
+    assert e.value.code == _abi.PCP_E_INVALID
+
+
+def test_cli_place_refine(tick, tmp_path, scene, cells, aux):
+    """pcp_nodes_cli place_refine (MobileLidarPlacement::refine above the node's tick, from the
+    greedy placement): the binding's answer, and a log that names the move and the verdict."""
+    assert CLI.exists(), "build first (__graft_entry__.build())"
+    np.ascontiguousarray(scene.terrain).tofile(tmp_path / "t.f32")
+    np.ascontiguousarray(aux).tofile(tmp_path / "a.f32")
+    np.ascontiguousarray(cells.xyz, np.float64).tofile(tmp_path / "c.f64")
+    np.ascontiguousarray(cells.normals, np.float32).tofile(tmp_path / "n.f32")
+    t = lambda v: ",".join(repr(float(x)) for x in v)   # noqa: E731
+    r = subprocess.run([str(CLI), "place_refine", str(tmp_path / "t.f32"),
+                        str(scene.terrain.shape[0]), str(tmp_path / "a.f32"), str(aux.shape[0]),
+                        str(tmp_path / "c.f64"), str(tmp_path / "n.f32"),
+                        str(cells.xyz.shape[0]), t(cells.grid_bbox), "0,0,0", "100", "15.0", "6",
+                        "2.0", str(tmp_path / "sel.i64"), str(tmp_path / "tot.f64"),
+                        str(tmp_path / "rep.txt")],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, (r.returncode, r.stderr)
+    res = json.loads(r.stdout.strip().splitlines()[-1])
+    ctx, poses = tick["ctx"], tick["poses"]
+    ctx.set_cells(cells.xyz, cells.normals)
+    greedy = ctx.place_sensors(poses, tick["zx"], tick["params"], 6, 2.0)
+    assert greedy["selected"].tolist() == G6S
+    got = ctx.place_refine(poses, tick["zx"], tick["params"], G6S, min_separation=2.0)
+    assert res["n_candidates"] == 91 and res["k"] == 6 and res["n_locked"] == 0
+    assert res["n_moves"] == got["n_moves"] == 1 and res["converged"] == got["converged"] == 1
+    assert res["selected"] == got["selected"].tolist() == [40, 41, 56, 23, 57, 46]
+    assert res["moves"] == [[3, 24, 23]]
+    assert res["covered"] == got["covered"] and res["start_covered"] == got["start_covered"]
+    assert res["total_cells"] == 3704
+    np.testing.assert_array_equal(np.fromfile(tmp_path / "sel.i64", np.int64), got["selected"])
+    np.testing.assert_array_equal(
+        _bits(np.fromfile(tmp_path / "tot.f64", np.float64)),
+        _bits([got["start_total"], got["total"], got["move_total"][0]]))
+    log = (tmp_path / "rep.txt").read_text()
+    assert "Exchange Refinement (ZX120 + 6 Mobile, 0 Locked)" in log
+    assert f"Total Score (start set): {got['start_total']:.2f}" in log
+    a, b = poses[24], poses[23]
+    assert (f"Move 1: LiDAR 4 from ({a[0]:.2f}, {a[1]:.2f}, {a[2]:.2f}) [candidate 24] to "
+            f"({b[0]:.2f}, {b[1]:.2f}, {b[2]:.2f}) [candidate 23]") in log
+    gain = got["move_total"][0] - got["start_total"]
+    assert f"  Total Score: {got['move_total'][0]:.2f} (gain {gain:.2f})" in log
+    assert "1-exchange optimal after 1 moves" in log and "stopped after" not in log
+    assert f"  Total Score: {got['total']:.2f} (gain over start {gain:.2f})" in log
+    p = poses[23]
+    assert f"Mobile LiDAR 4 Position: ({p[0]:.2f}, {p[1]:.2f}, {p[2]:.2f})  [candidate 23]" in log
