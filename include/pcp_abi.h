@@ -258,7 +258,13 @@ typedef struct pcp_excavation_params {   /* excavated_surface_generator.cpp:29-5
  *                input order) then generateExcavatedSurface's bottom and wall points (:487-584)
  *   area_out:    /excavation_area = generateExcavationArea (:350-455)
  * Every getTerrainHeight (:183-226) runs on the GPU against one index of the input (the
- * reference rebuilds a KD-tree per call, once per input point).  pose_out (nullable): the
+ * reference rebuilds a KD-tree per call, once per input point).  A height that is a mean is
+ * the exactly rounded sum of its m neighbours' z over m (to one ulp: the double-double's final
+ * rounding); it is the reference's bits whenever the reference's own sequential double sum is
+ * exact -- sufficient: every z within the radius a multiple of one quantum u with
+ * m * max|z| < 2^53 * u (e.g. u = 2^-42: every such float z zero or |z| >= 2^-19, which the
+ * default radius keeps below 0.5, and m <= 1024).  Past that the reference's sum depends on its
+ * neighbour order and the two can differ in the mean's last bits.  pose_out (nullable): the
  * excavation centre x, y, its terrain height, yaw (publishExcavationMarkers).  *_cap in
  * records; PCP_E_CAPACITY with *n_* set when short.  A missing TF is the caller's branch
  * (:276-279: the input is republished unchanged). */

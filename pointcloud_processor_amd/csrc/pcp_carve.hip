@@ -6,9 +6,10 @@
 // KdTreeFLANN over the whole cloud, once per input point -- is a GPU query against ONE uniform
 // grid of the input (r = terrain_search_radius):
 //   3-D radius search from (x, y, 0) with FLANN's float predicate, the 2-D distance filter in
-//   double, the mean z (double-double sum: the reference's sequential double sum, exact for
-//   these magnitudes), else the nearest point's z (brute force, smallest float distance, lowest
-//   index on a tie), else 0.
+//   double, the mean z (double-double sum: the exactly rounded sum in any order, which is the
+//   reference's sequential double sum whenever that sum is itself exact -- see pcp_abi.h for
+//   the sufficient condition), else the nearest point's z (brute force, smallest float distance,
+//   lowest index on a tie), else 0.
 // Per input point, the pit test needs a height only where the point can be inside a box
 // widened by the largest slope offset; all other points are kept without a query (exact).
 // The pose / lattice / wall geometry is O(lattice) double arithmetic on the host (glibc), the
@@ -118,8 +119,8 @@ k_heights(GridView g, float r2, double radius, const double2 *__restrict__ qxy,
           const uint32_t *__restrict__ nq_dev, uint32_t nq_fixed, double *__restrict__ h,
           uint32_t *__restrict__ fb_list, uint32_t *__restrict__ fb_count) {
     // one wave per query: the lanes split the stencil's candidate points (a query used to walk
-    // hundreds of them on one lane).  The z sum is double-double, exact at these magnitudes, so
-    // the lanes' partial sums merge to the same value in any order.
+    // hundreds of them on one lane).  The z sum is double-double (exact for float z of any
+    // realistic spread), so the lanes' partial sums merge to the same value in any order.
     const uint32_t nq = nq_fixed + (nq_dev ? *nq_dev : 0u);
     const uint32_t q = blockIdx.x * (kCT / 64) + (threadIdx.x >> 6);
     const uint32_t lane = threadIdx.x & 63;
