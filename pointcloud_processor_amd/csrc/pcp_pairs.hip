@@ -1,7 +1,9 @@
 // pcp_pairs.hip -- the exact best pair of mobile sensors (pcp_place_pair): every pair a < b of
 // the admissible poses gets t[a][b] = osum(max(max(base, S[a]), S[b])), the ordered sum of the
 // positive combined scores over zx120, the fixed sensors and the two poses, and the first maximum
-// wins (include/pcp_abi.h has the definition; DESIGN.md §6h the kernels and their timing).
+// wins (include/pcp_abi.h has the definition; DESIGN.md §6h the kernels and their timing).  The
+// first-maximum reductions, the ordered total, the fold and the separation test are
+// pcp_place_shared.hpp's; k_pair_tiles holds its walk_chunk's text in place.
 //
 // The scoring (k_score_cells) leaves comb [P][C] and score_z [C] on the device.  Three launches
 // follow, ordered by the stream alone (no block ever waits for another):
@@ -16,20 +18,17 @@
 
 #include "pcp_internal.hpp"
 #include "pcp_pair_tiles.hpp"
+#include "pcp_place_shared.hpp"
 
 namespace pcp {
 namespace {
 
 constexpr int kQT = 256;        // threads per block of the preparation
 constexpr int kQS = 1024;       // threads of the selection's one block
-constexpr int kQC = 64;         // cells per preparation block / per staged chunk of a tile
-constexpr int kQLd = kQC + 2;   // a staged row: 16 rows of b128 reads fall on 16 x 4 distinct banks
-constexpr int kQG = 4;          // b128 reads per row per register group of the tile walk
-static_assert((kQC / 2) % (2 * kQG) == 0, "whole group pairs per chunk");
 constexpr int kQRows = 2 * kPairTile;                      // a tile pair's A rows and B rows
-constexpr int kQLoads = kQRows * (kQC / 2) / kPairLanes;    // b128 loads per thread per chunk
+constexpr int kQLoads = kQRows * (kWalkC / 2) / kPairLanes;    // b128 loads per thread per chunk
 static_assert(kPairSub == 1 && kPairLanes == 256, "k_pair_tiles: one pair per lane, four waves");
-static_assert(kQRows * (kQC / 2) % kPairLanes == 0 && kQLd % 2 == 0, "whole b128 loads per thread");
+static_assert(kQRows * (kWalkC / 2) % kPairLanes == 0, "whole b128 loads per thread");
 
 // the call's result record (downloaded)
 struct PairState {
@@ -47,18 +46,7 @@ struct PairFixed {
     int32_t idx[PCP_PLACE_MAX];
 };
 
-// a tile pair's best: the first maximum in row-major order among its admissible pairs
-struct PairBest {
-    double t;
-    int32_t a, b;
-};
-
-// (t2, a2, b2) ahead of (t1, a1, b1): a larger total, or the same and lexicographically smaller
-__device__ __forceinline__ bool pair_ahead(double t2, int a2, int b2, double t1, int a1, int b1) {
-    return a2 >= 0 && (a1 < 0 || t2 > t1 || (t2 == t1 && (a2 < a1 || (a2 == a1 && b2 < b1))));
-}
-
-// Preparation.  Block (cc, g) of the first ncc * npg: cells cc kQC .., poses g kPairTile ..: the
+// Preparation.  Block (cc, g) of the first ncc * npg: cells cc kWalkC .., poses g kPairTile ..: the
 // base of its cells from Z and the fixed rows (every block its own: no block waits for
 // another), then its poses' clamped rows into M [Pp][Cs] (+0.0 in the rows past P and the cells
 // past C).  The blocks with g == 0 store base / owner, those with cc == 0 the admissible mask.
@@ -76,14 +64,8 @@ k_pair_prep(const double *__restrict__ S, const double *__restrict__ Z, int C, i
     const int tid = threadIdx.x;
     auto base_of = [&](int c, int32_t &own) {
         double b = Z[c];
-        own = b > 0 ? PCP_OWNER_ZX120 : PCP_OWNER_NONE;
-        for (int i = 0; i < fx.n; ++i) {
-            const double v = S[(size_t)fx.idx[i] * C + c];
-            if (b < v) {   // std::max(base, S); ties keep the earlier owner
-                b = v;
-                own = i;
-            }
-        }
+        own = owner_of_zx(b);
+        for (int i = 0; i < fx.n; ++i) fold_owner(b, own, S[(size_t)fx.idx[i] * C + c], i);
         return b;
     };
     if ((int)blockIdx.x == ncc * npg) {   // ---- the base total
@@ -94,25 +76,12 @@ k_pair_prep(const double *__restrict__ S, const double *__restrict__ Z, int C, i
             }
             return;
         }
-        if (tid == 0) s_cnt = 0;
-        double acc = 0.0;
-        int32_t cnt = 0;
-        for (int c0 = 0; c0 < C; c0 += kQT) {
-            __syncthreads();
-            int32_t own;
-            const double b = c0 + tid < C ? base_of(c0 + tid, own) : 0.0;
-            const bool pos = b > 0;
-            cnt += pos ? 1 : 0;
-            s_b[tid] = pos ? b : 0.0;
-            __syncthreads();
-            if (tid == 0) {
-#pragma unroll 16
-                for (int i = 0; i < kQT; ++i) acc += s_b[i];   // (+0.0 is bit-neutral)
-            }
-        }
-        __syncthreads();
-        atomicAdd(&s_cnt, cnt);
-        __syncthreads();
+        const double acc = ordered_total<kQT>(
+            [&](int c) {
+                int32_t own;
+                return base_of(c, own);
+            },
+            C, s_b, s_cnt);
         if (tid == 0) {
             st->base_total = acc;
             st->base_cov = s_cnt;
@@ -120,8 +89,8 @@ k_pair_prep(const double *__restrict__ S, const double *__restrict__ Z, int C, i
         return;
     }
     const int cc = blockIdx.x % ncc, g = blockIdx.x / ncc;
-    if (tid < kQC) {
-        const int c = cc * kQC + tid;
+    if (tid < kWalkC) {
+        const int c = cc * kWalkC + tid;
         if (c < C) {
             int32_t own;
             const double b = base_of(c, own);
@@ -140,20 +109,17 @@ k_pair_prep(const double *__restrict__ S, const double *__restrict__ Z, int C, i
             for (int i = 0; i < fx.n; ++i) {
                 const int f = fx.idx[i];
                 ok &= f != p;
-                if (sep2 > 0) {
-                    const double dx = px - poses5[5 * (size_t)f], dy = py - poses5[5 * (size_t)f + 1];
-                    ok &= !(dx * dx + dy * dy < sep2);
-                }
+                if (sep2 > 0) ok &= !closer_than(px, py, poses5, f, sep2);
             }
         }
         adm[p] = ok ? 1u : 0u;
     }
     if (!Pp) return;   // (uniform) no poses: the base alone
     __syncthreads();
-    const int cl = tid & (kQC - 1), c = cc * kQC + cl;   // (c < Cs: Cs is whole chunks)
+    const int cl = tid & (kWalkC - 1), c = cc * kWalkC + cl;   // (c < Cs: Cs is whole chunks)
 #pragma unroll
-    for (int k = 0; k < kPairTile * kQC / kQT; ++k) {
-        const int p = g * kPairTile + (tid >> 6) + (kQT / kQC) * k;
+    for (int k = 0; k < kPairTile * kWalkC / kQT; ++k) {
+        const int p = g * kPairTile + (tid >> 6) + (kQT / kWalkC) * k;
         double x = 0.0;   // rows past P and cells past C: +0.0
         if (p < P && c < C) {
             const double v = S[(size_t)p * C + c], b = s_b[cl];
@@ -164,30 +130,22 @@ k_pair_prep(const double *__restrict__ S, const double *__restrict__ Z, int C, i
     }
 }
 
-// the larger of two values that are finite, not NaN and never -0.0 (M's): one instruction, and
-// for equal values their common bits -- the reference's std::max on these inputs
-__device__ __forceinline__ double max_pos(double a, double b) {
-    double r;
-    asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-
 // One tile pair (ta <= tb) per block of four waves; lane (ia, jb) owns the pair of A row ia and
 // B row jb: one f64 chain, adding its cells in ascending order from +0.0, one rounded add per
 // cell (+0.0 for the cells that are not positive and for the padding past C: bit-neutral).  The
-// block stages chunks of kQC cells of its 16 A rows and 16 B rows -- coalesced b128 loads of M,
-// one chunk ahead in registers, stored to LDS as they lie, rows kQLd apart -- and every lane
+// block stages chunks of kWalkC cells of its 16 A rows and 16 B rows -- coalesced b128 loads of M,
+// one chunk ahead in registers, stored to LDS as they lie, rows kWalkLd apart -- and every lane
 // reads two cells of its A row and of its B row per ds_read_b128: a group of 16 lanes reads at
 // most 16 B rows, 4 banks apart each, and its A rows by broadcast.  A tile with no admissible A
 // row or B row loads nothing.
 __global__ void __launch_bounds__(kPairLanes)
 k_pair_tiles(const double *__restrict__ M, int Cs, int n, int nt,
              const uint32_t *__restrict__ adm, const double *__restrict__ poses5, double sep2,
-             double *__restrict__ singles, PairBest *__restrict__ slots,
+             double *__restrict__ singles, RowBest *__restrict__ slots,
              double *__restrict__ table) {
-    __shared__ double2 s_m[2][kQRows * kQLd / 2];
+    __shared__ double2 s_m[2][kQRows * kWalkLd / 2];
     __shared__ int s_live[2];
-    __shared__ PairBest s_best[kPairLanes / 64];
+    __shared__ RowBest s_best[kPairLanes / 64];
     const int tid = threadIdx.x;
     const PairTile tile = pair_tile_of(nt, (int)blockIdx.x);
     const int ta = tile.ta, tb = tile.tb;
@@ -199,22 +157,23 @@ k_pair_tiles(const double *__restrict__ M, int Cs, int n, int nt,
     const bool live = s_live[0] != 0 && s_live[1] != 0;
     double acc = 0.0;
     if (live) {   // (uniform)
-        const int nch = Cs / kQC;
+        const int nch = Cs / kWalkC;
         const int ia = tid / kPairSide, jb = kPairTile + tid % kPairSide;
         // a thread's four b128 loads per chunk: double2 `col` of the rows r0 and r0 + 8 of A and
         // of B (32 threads per row: 512 contiguous bytes)
-        static_assert(kQLoads == 4 && kPairLanes / (kQC / 2) == kPairTile / 2, "two rows of each");
-        const int r0 = tid / (kQC / 2), col = tid % (kQC / 2);
+        static_assert(kQLoads == 4 && kPairLanes / (kWalkC / 2) == kPairTile / 2,
+                      "two rows of each");
+        const int r0 = tid / (kWalkC / 2), col = tid % (kWalkC / 2);
         const size_t half = (size_t)(kPairTile / 2) * Cs / 2;   // 8 rows of M in double2
         const double2 *srcA =
             reinterpret_cast<const double2 *>(M + (size_t)(ta * kPairTile + r0) * Cs) + col;
         const double2 *srcB =
             reinterpret_cast<const double2 *>(M + (size_t)(tb * kPairTile + r0) * Cs) + col;
-        const int dst = r0 * (kQLd / 2) + col;
-        constexpr int kHalf = (kPairTile / 2) * (kQLd / 2);     // 8 staged rows in double2
+        const int dst = r0 * (kWalkLd / 2) + col;
+        constexpr int kHalf = (kPairTile / 2) * (kWalkLd / 2);     // 8 staged rows in double2
         double2 rA0, rA1, rB0, rB1;
         auto load = [&](int k) {
-            const size_t o = (size_t)k * (kQC / 2);
+            const size_t o = (size_t)k * (kWalkC / 2);
             rA0 = srcA[o];
             rA1 = srcA[o + half];
             rB0 = srcB[o];
@@ -234,33 +193,34 @@ k_pair_tiles(const double *__restrict__ M, int Cs, int n, int nt,
             // (unconditional: the last chunk is loaded and stored once more, into the buffer no
             // one reads again -- straight-line code keeps the prefetch in registers)
             load(min(k + 1, nch - 1));
-            // two register groups of kQG b128 reads per row: the adds of one group run while the
-            // other's reads are in flight (one wave per SIMD: nothing else hides the LDS latency;
-            // the scheduling barriers keep each group's reads ahead of the adds before it)
-            const double2 *va = s_m[k & 1] + ia * (kQLd / 2), *vb = s_m[k & 1] + jb * (kQLd / 2);
-            double2 a0[kQG], b0[kQG], a1[kQG], b1[kQG];
+            // walk_chunk's text in place: called from here, the compiler keeps the last two
+            // groups' adds behind their maxima one by one where it otherwise gathers the maxima
+            // first, and the pair phase takes 0.3 us longer (profiles/place_shared_timing.json)
+            const double2 *va = s_m[k & 1] + ia * (kWalkLd / 2),
+                          *vb = s_m[k & 1] + jb * (kWalkLd / 2);
+            double2 a0[kWalkG], b0[kWalkG], a1[kWalkG], b1[kWalkG];
             auto rd = [&](double2 *a, double2 *b, int j) {
 #pragma unroll
-                for (int i = 0; i < kQG; ++i) {
+                for (int i = 0; i < kWalkG; ++i) {
                     a[i] = va[j + i];
                     b[i] = vb[j + i];
                 }
             };
             auto add = [&](const double2 *a, const double2 *b) {
 #pragma unroll
-                for (int i = 0; i < kQG; ++i) {
+                for (int i = 0; i < kWalkG; ++i) {
                     acc += max_pos(a[i].x, b[i].x);
                     acc += max_pos(a[i].y, b[i].y);
                 }
             };
             rd(a0, b0, 0);
 #pragma unroll
-            for (int j = 0; j < kQC / 2; j += 2 * kQG) {
-                rd(a1, b1, j + kQG);
+            for (int j = 0; j < kWalkC / 2; j += 2 * kWalkG) {
+                rd(a1, b1, j + kWalkG);
                 __builtin_amdgcn_sched_barrier(0);
                 add(a0, b0);
                 __builtin_amdgcn_sched_barrier(0);
-                if (j + 2 * kQG < kQC / 2) rd(a0, b0, j + 2 * kQG);
+                if (j + 2 * kWalkG < kWalkC / 2) rd(a0, b0, j + 2 * kWalkG);
                 __builtin_amdgcn_sched_barrier(0);
                 add(a1, b1);
                 __builtin_amdgcn_sched_barrier(0);
@@ -271,11 +231,7 @@ k_pair_tiles(const double *__restrict__ M, int Cs, int n, int nt,
     }
     const PairSlot ps = pair_slot(ta, tb, tid, 0);
     bool ok = pair_is_pair(ps, n) && adm[ps.a] != 0u && adm[ps.b] != 0u;
-    if (ok && sep2 > 0) {
-        const double dx = poses5[5 * (size_t)ps.a] - poses5[5 * (size_t)ps.b];
-        const double dy = poses5[5 * (size_t)ps.a + 1] - poses5[5 * (size_t)ps.b + 1];
-        ok = !(dx * dx + dy * dy < sep2);
-    }
+    if (ok && sep2 > 0) ok = !closer_than(poses5, ps.a, ps.b, sep2);
     double bt = ok ? acc : -INFINITY;
     if (table && ps.a < n && ps.b < n) {
         table[(size_t)ps.a * n + ps.b] = bt;
@@ -284,22 +240,8 @@ k_pair_tiles(const double *__restrict__ M, int Cs, int n, int nt,
     if (pair_is_single(ps, n)) singles[ps.a] = adm[ps.a] != 0u ? acc : -INFINITY;
     // the block's first maximum in row-major order
     int ba = ok ? ps.a : -1, bb = ok ? ps.b : -1;
-    auto take = [&](double t2, int a2, int b2) {
-        if (pair_ahead(t2, a2, b2, bt, ba, bb)) {
-            bt = t2;
-            ba = a2;
-            bb = b2;
-        }
-    };
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1)
-        take(__shfl_xor(bt, o, 64), __shfl_xor(ba, o, 64), __shfl_xor(bb, o, 64));
-    if ((tid & 63) == 0) s_best[tid >> 6] = PairBest{bt, ba, bb};
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < kPairLanes / 64; ++w) take(s_best[w].t, s_best[w].a, s_best[w].b);
-        slots[blockIdx.x] = PairBest{bt, ba, bb};
-    }
+    block_first_max<kPairLanes / 64>(s_best, bt, ba, bb);
+    if (tid == 0) slots[blockIdx.x] = RowBest{bt, ba, bb};
 }
 
 // Selection, one block: the first maximum of the tile bests (ties to the lexicographically
@@ -307,54 +249,20 @@ k_pair_tiles(const double *__restrict__ M, int Cs, int n, int nt,
 // the covered counts of both from M's rows, and the answer folded into cell_score / cell_owner
 // (base and the owners of the fixed sensors are there from the preparation).
 __global__ void __launch_bounds__(kQS)
-k_pair_select(const PairBest *__restrict__ slots, int nblk, const double *__restrict__ singles,
+k_pair_select(const RowBest *__restrict__ slots, int nblk, const double *__restrict__ singles,
               int P, int Cs, const double *__restrict__ M, const double *__restrict__ S, int C,
               int n_fixed, double *__restrict__ cs, int32_t *__restrict__ owner,
               PairState *__restrict__ st) {
-    __shared__ double s_t[kQS / 64];
-    __shared__ int s_a[kQS / 64], s_b[kQS / 64];
+    __shared__ RowBest s_best[kQS / 64];
     __shared__ int32_t s_pc, s_sc;
     const int tid = threadIdx.x;
-    // a wave's candidates by shuffles, the waves' through LDS; every thread gets the result
-    auto reduce = [&](double &t, int &a, int &b) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const double t2 = __shfl_xor(t, o, 64);
-            const int a2 = __shfl_xor(a, o, 64), b2 = __shfl_xor(b, o, 64);
-            if (pair_ahead(t2, a2, b2, t, a, b)) {
-                t = t2;
-                a = a2;
-                b = b2;
-            }
-        }
-        __syncthreads();   // (the arrays' previous readers are done)
-        if ((tid & 63) == 0) {
-            s_t[tid >> 6] = t;
-            s_a[tid >> 6] = a;
-            s_b[tid >> 6] = b;
-        }
-        __syncthreads();
-        t = s_t[0];
-        a = s_a[0];
-        b = s_b[0];
-        for (int w = 1; w < kQS / 64; ++w)
-            if (pair_ahead(s_t[w], s_a[w], s_b[w], t, a, b)) {
-                t = s_t[w];
-                a = s_a[w];
-                b = s_b[w];
-            }
-    };
     double bt = -INFINITY;
     int ba = -1, bb = -1;
     for (int i = tid; i < nblk; i += kQS) {
-        const PairBest v = slots[i];
-        if (pair_ahead(v.t, v.a, v.b, bt, ba, bb)) {
-            bt = v.t;
-            ba = v.a;
-            bb = v.b;
-        }
+        const RowBest v = slots[i];
+        take_ahead(bt, ba, bb, v.t, v.a, v.b);
     }
-    reduce(bt, ba, bb);
+    block_first_max_all<kQS / 64>(s_best, bt, ba, bb);
     // the singles: inadmissible poses hold -inf and are never taken (strict '>' from -inf)
     double sv = -INFINITY;
     int si = -1, sz = 0;
@@ -365,7 +273,7 @@ k_pair_select(const PairBest *__restrict__ slots, int nblk, const double *__rest
             si = p;
         }
     }
-    reduce(sv, si, sz);
+    block_first_max_all<kQS / 64>(s_best, sv, si, sz);
     if (tid == 0) {
         s_pc = 0;
         s_sc = 0;
@@ -381,18 +289,8 @@ k_pair_select(const PairBest *__restrict__ slots, int nblk, const double *__rest
         if (n_sel) {
             double x = cs[c];
             int32_t own = owner[c];
-            const double v0 = S[(size_t)(n_sel == 2 ? ba : si) * C + c];
-            if (x < v0) {
-                x = v0;
-                own = n_fixed;
-            }
-            if (n_sel == 2) {
-                const double v1 = S[(size_t)bb * C + c];
-                if (x < v1) {
-                    x = v1;
-                    own = n_fixed + 1;
-                }
-            }
+            fold_owner(x, own, S[(size_t)(n_sel == 2 ? ba : si) * C + c], n_fixed);
+            if (n_sel == 2) fold_owner(x, own, S[(size_t)bb * C + c], n_fixed + 1);
             cs[c] = x;
             owner[c] = own;
         }
@@ -424,28 +322,27 @@ k_pair_select(const PairBest *__restrict__ slots, int nblk, const double *__rest
 //  pair table f64 P x P (only when asked for)]
 struct PairPlan {
     int C, P, Pp, Cs, nt, nblk, ncc, npg;
-    size_t cs_off, own_off, sg_off, adm_off, slot_off, tab_off, bytes, m_bytes;
+    CellBlock cb;   // sg_off = cb.rest_off
+    size_t sg_off, adm_off, slot_off, tab_off, bytes, m_bytes;
     bool dense;
 };
 
 PairPlan make_plan(int C, int P, bool dense) {
-    auto a16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
     PairPlan s{};
     s.C = C;
     s.P = P;
     s.nt = pair_tiles(P);
     s.Pp = s.nt * kPairTile;
     s.nblk = pair_blocks(s.nt);
-    s.ncc = (C + kQC - 1) / kQC;
-    s.Cs = s.ncc * kQC;
+    s.ncc = (C + kWalkC - 1) / kWalkC;
+    s.Cs = s.ncc * kWalkC;
     s.npg = std::max(1, s.nt);
     s.dense = dense;
-    s.cs_off = sizeof(PairState);
-    s.own_off = a16(s.cs_off + (size_t)C * sizeof(double));
-    s.sg_off = a16(s.own_off + (size_t)C * sizeof(int32_t));
+    s.cb = cell_block(sizeof(PairState), C);
+    s.sg_off = s.cb.rest_off;
     s.adm_off = a16(s.sg_off + (size_t)P * sizeof(double));
     s.slot_off = a16(s.adm_off + (size_t)s.Pp * sizeof(uint32_t));
-    s.tab_off = a16(s.slot_off + (size_t)s.nblk * sizeof(PairBest));
+    s.tab_off = a16(s.slot_off + (size_t)s.nblk * sizeof(RowBest));
     s.bytes = s.tab_off + (dense ? (size_t)P * P * sizeof(double) : 0);
     s.m_bytes = (size_t)s.Cs * s.Pp * sizeof(double);
     return s;
@@ -457,11 +354,11 @@ int pair_enqueue(pcp_ctx *ctx, const PairPlan &s, const ScoreEnq &o, const PairF
     hipStream_t st = ctx->stream;
     char *blk = ctx->pair_d.as<char>();
     PairState *state = reinterpret_cast<PairState *>(blk);
-    double *cs = reinterpret_cast<double *>(blk + s.cs_off);
-    int32_t *owner = reinterpret_cast<int32_t *>(blk + s.own_off);
+    double *cs = reinterpret_cast<double *>(blk + s.cb.score_off);
+    int32_t *owner = reinterpret_cast<int32_t *>(blk + s.cb.owner_off);
     double *singles = reinterpret_cast<double *>(blk + s.sg_off);
     uint32_t *adm = reinterpret_cast<uint32_t *>(blk + s.adm_off);
-    PairBest *slots = reinterpret_cast<PairBest *>(blk + s.slot_off);
+    RowBest *slots = reinterpret_cast<RowBest *>(blk + s.slot_off);
     double *table = s.dense ? reinterpret_cast<double *>(blk + s.tab_off) : nullptr;
     double *M = ctx->pair_m.as<double>();
     hipLaunchKernelGGL(k_pair_prep, dim3((unsigned)(s.ncc * s.npg + 1)), dim3(kQT), 0, st,
@@ -475,7 +372,7 @@ int pair_enqueue(pcp_ctx *ctx, const PairPlan &s, const ScoreEnq &o, const PairF
                            sep2, singles, slots, table);
         PCP_CHECK_LAUNCH(ctx);
     }
-    hipLaunchKernelGGL(k_pair_select, dim3(1), dim3(kQS), 0, st, (const PairBest *)slots, s.nblk,
+    hipLaunchKernelGGL(k_pair_select, dim3(1), dim3(kQS), 0, st, (const RowBest *)slots, s.nblk,
                        (const double *)singles, s.P, s.Cs, (const double *)M,
                        (const double *)o.comb, s.C, (int)fx.n, cs, owner, state);
     PCP_CHECK_LAUNCH(ctx);
@@ -488,22 +385,8 @@ int check_args(pcp_ctx *ctx, const char *what, uint64_t n, const pcp_pair_params
     if (pp->n_fixed < 0 || pp->n_fixed > PCP_PLACE_MAX || pp->reserved != 0)
         return set_err(ctx, PCP_E_INVALID, "%s: n_fixed %d outside 0..%d or reserved %d != 0", what,
                        (int)pp->n_fixed, PCP_PLACE_MAX, (int)pp->reserved);
-    if (n > PCP_PAIR_MAX_POSES)
-        return set_err(ctx, PCP_E_INVALID, "%s: %llu poses, at most %d per call", what,
-                       (unsigned long long)n, PCP_PAIR_MAX_POSES);
     fx.n = pp->n_fixed;
-    for (int i = 0; i < pp->n_fixed; ++i) {
-        const int64_t f = pp->fixed[i];
-        if (f < 0 || (uint64_t)f >= n)
-            return set_err(ctx, PCP_E_INVALID, "%s: fixed[%d] = %lld is no pose of %llu", what, i,
-                           (long long)f, (unsigned long long)n);
-        for (int j = 0; j < i; ++j)
-            if (pp->fixed[j] == f)
-                return set_err(ctx, PCP_E_INVALID, "%s: pose %lld is fixed twice", what,
-                               (long long)f);
-        fx.idx[i] = (int32_t)f;
-    }
-    return PCP_OK;
+    return check_pose_list(ctx, what, "fixed", "fixed", pp->fixed, pp->n_fixed, n, fx.idx);
 }
 
 }  // namespace
@@ -543,8 +426,7 @@ extern "C" int pcp_place_pair(pcp_ctx *ctx, const double *poses5, uint64_t n, co
         *n_selected = 0;
     };
     if (!C) {   // no cells: nothing to cover
-        PCP_HIP(ctx, hipStreamSynchronize(st));
-        prof_resolve(ctx);
+        if (int rc = stream_done(ctx)) return rc;
         nothing();
         *base_total = 0.0;
         *base_covered = 0;
@@ -555,16 +437,14 @@ extern "C" int pcp_place_pair(pcp_ctx *ctx, const double *poses5, uint64_t n, co
     const size_t down = s.dense ? s.bytes
                         : single_totals ? s.adm_off
                         : cells_out ? s.sg_off
-                                    : s.cs_off;
+                                    : s.cb.score_off;
     PCP_HIP(ctx, ctx->pair_d.ensure(s.bytes + 64));
     PCP_HIP(ctx, ctx->pair_m.ensure(s.m_bytes + 64));
     PCP_HIP(ctx, ctx->pair_host.ensure(down + 64));
-    const double sep = pp->min_separation;
-    if (int rc = pair_enqueue(ctx, s, o, fx, sep > 0 ? sep * sep : 0.0)) return rc;
+    if (int rc = pair_enqueue(ctx, s, o, fx, sep2_of(pp->min_separation))) return rc;
     char *pin = ctx->pair_host.as<char>();
     PCP_HIP(ctx, hipMemcpyAsync(pin, ctx->pair_d.as<char>(), down, hipMemcpyDeviceToHost, st));
-    PCP_HIP(ctx, hipStreamSynchronize(st));
-    prof_resolve(ctx);
+    if (int rc = stream_done(ctx)) return rc;
     const PairState *h = reinterpret_cast<const PairState *>(pin);
     nothing();
     best_pair[0] = h->pair[0];
@@ -584,8 +464,7 @@ extern "C" int pcp_place_pair(pcp_ctx *ctx, const double *poses5, uint64_t n, co
     if (pair_totals && P)
         host_copy(ctx, pair_totals, pin + s.tab_off, (size_t)P * P * sizeof(double));
     if (single_totals && P) std::memcpy(single_totals, pin + s.sg_off, (size_t)P * sizeof(double));
-    if (cell_score) std::memcpy(cell_score, pin + s.cs_off, (size_t)C * sizeof(double));
-    if (cell_owner) std::memcpy(cell_owner, pin + s.own_off, (size_t)C * sizeof(int32_t));
+    copy_cells(pin, s.cb, C, cell_score, cell_owner);
     return PCP_OK;
 }
 
@@ -601,31 +480,14 @@ extern "C" int pcp_place_pair_burst(pcp_ctx *ctx, const double *poses5, uint64_t
     *ms_per_rep = 0.0;
     ScoreEnq o;
     if (int rc = score_enqueue(ctx, poses5, n, zx, p, o)) return rc;
-    hipStream_t st = ctx->stream;
     if (!o.C) {
-        PCP_HIP(ctx, hipStreamSynchronize(st));
-        prof_resolve(ctx);
+        if (int rc = stream_done(ctx)) return rc;
         return set_err(ctx, PCP_E_INVALID, "pcp_place_pair_burst: no cells, nothing to time");
     }
     const PairPlan s = make_plan(o.C, o.P, false);
     PCP_HIP(ctx, ctx->pair_d.ensure(s.bytes + 64));
     PCP_HIP(ctx, ctx->pair_m.ensure(s.m_bytes + 64));
-    const double sep = pp->min_separation, sep2 = sep > 0 ? sep * sep : 0.0;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    PCP_HIP(ctx, hipEventCreate(&e0));
-    PCP_HIP(ctx, hipEventCreate(&e1));
-    int rc = pair_enqueue(ctx, s, o, fx, sep2);   // once untimed: the phase's first touches
-    hipError_t e = rc ? hipSuccess : hipEventRecord(e0, st);
-    for (int r = 0; r < reps && !rc && e == hipSuccess; ++r) rc = pair_enqueue(ctx, s, o, fx, sep2);
-    if (!rc && e == hipSuccess) e = hipEventRecord(e1, st);
-    if (!rc && e == hipSuccess) e = hipEventSynchronize(e1);
-    float t = 0.0f;
-    if (!rc && e == hipSuccess) e = hipEventElapsedTime(&t, e0, e1);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (rc) return rc;
-    if (e != hipSuccess) return hip_fail(ctx, e, "pcp_place_pair_burst", __FILE__, __LINE__);
-    *ms_per_rep = (double)t / reps;
-    prof_resolve(ctx);
-    return PCP_OK;
+    const double sep2 = sep2_of(pp->min_separation);
+    auto once = [&] { return pair_enqueue(ctx, s, o, fx, sep2); };
+    return time_reps(ctx, "pcp_place_pair_burst", ctx->stream, reps, once, once, ms_per_rep);
 }

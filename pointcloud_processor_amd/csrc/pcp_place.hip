@@ -8,11 +8,13 @@
 // round then sums every alive pose's row against `base` (the combined score of what is placed
 // so far) in the reference's order, and the LAST block of the round to finish selects the pose
 // and folds its row into `base` for the next launch.  Rounds are ordered by the stream alone:
-// no block ever waits for another.
+// no block ever waits for another.  The ticket, the first-maximum reduction, the fold and the
+// separation test are pcp_place_shared.hpp's.
 #include <cmath>
 #include <cstring>
 
 #include "pcp_internal.hpp"
+#include "pcp_place_shared.hpp"
 
 namespace pcp {
 namespace {
@@ -49,7 +51,7 @@ k_place_init(const double *__restrict__ score_z, int C, int P, const double *__r
     if (i < C) {
         const double z = score_z[i];
         base[i] = z;
-        owner[i] = z > 0 ? PCP_OWNER_ZX120 : PCP_OWNER_NONE;
+        owner[i] = owner_of_zx(z);
     }
     if (i < P) alive[i] = 1u;
     if (i == 0) {
@@ -205,56 +207,23 @@ k_place_round(const double *__restrict__ S, double *base, int C, int P, uint32_t
         rc[r0 + tid] = a ? s_cov[tid] : 0;
     }
     // the round's ticket: this block's totals written back before the draw
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const uint32_t t =
-            __hip_atomic_fetch_add(&s->ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_flag = t == gridDim.x - 1;
-        if (s_flag) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-    }
-    __syncthreads();
-    if (!s_flag) return;
+    if (!last_block(&s->ticket, s_flag)) return;
 
     // ---- the last block of the round ------------------------------------------------------
     // first maximum over the alive poses (strict '>' from -inf, :471-474): each thread scans
     // its poses in ascending order, the threads' bests are combined with ties to the lower index
-    double *s_t = &s_v[0][0][0];                            // [kPT] the threads' best totals
-    int *s_i = reinterpret_cast<int *>(&s_v[1][0][0]);      // [kPT] and their poses
-    double bt = -INFINITY;
-    int bi = -1;
+    RowBest *s_best = reinterpret_cast<RowBest *>(&s_v[0][0][0]);   // [kPT / 64]
+    double tb = -INFINITY;
+    int b = -1, none = 0;   // (a row is a pose here: RowBest's second index stays 0)
     for (int p = tid; p < P; p += kPT) {
         if (alive[p] == 0u) continue;
         const double t = __hip_atomic_load(&rt[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (t > bt) {
-            bt = t;
-            bi = p;
+        if (t > tb) {
+            tb = t;
+            b = p;
         }
     }
-    s_t[tid] = bt;
-    s_i[tid] = bi;
-    __syncthreads();
-    for (int o = kPT / 2; o > 0; o >>= 1) {
-        if (tid < o) {
-            const double t2 = s_t[tid + o];
-            const int i2 = s_i[tid + o];
-            const double t1 = s_t[tid];
-            const int i1 = s_i[tid];
-            if (i2 >= 0 && (i1 < 0 || t2 > t1 || (t2 == t1 && i2 < i1))) {
-                s_t[tid] = t2;
-                s_i[tid] = i2;
-            }
-        }
-        __syncthreads();
-    }
-    const int b = s_i[0];
-    const double tb = s_t[0];
-    __syncthreads();
+    block_first_max_all<kPT / 64>(s_best, tb, b, none);
     // no pose alive, or the best adds nothing (fl-addition is monotone: t >= T always)
     if (tid == 0) {
         s->ticket = 0u;   // (the next launch draws from zero)
@@ -274,22 +243,16 @@ k_place_round(const double *__restrict__ S, double *base, int C, int P, uint32_t
     // the placed pose's row into base; ties keep the earlier owner
     const double *row = S + (size_t)b * C;
     for (int c = tid; c < C; c += kPT) {
-        const double v = row[c];
-        if (base[c] < v) {
-            base[c] = v;
-            owner[c] = r;
+        double x = base[c];
+        int32_t own;
+        if (fold_owner(x, own, row[c], r)) {
+            base[c] = x;
+            owner[c] = own;
         }
     }
     // the placed pose and, with a separation, every pose closer than it in XY leave the search
-    const double bx = poses5[5 * (size_t)b], by = poses5[5 * (size_t)b + 1];
-    for (int p = tid; p < P; p += kPT) {
-        bool dead = p == b;
-        if (sep2 > 0) {
-            const double dx = poses5[5 * (size_t)p] - bx, dy = poses5[5 * (size_t)p + 1] - by;
-            dead |= dx * dx + dy * dy < sep2;
-        }
-        if (dead) alive[p] = 0u;
-    }
+    for (int p = tid; p < P; p += kPT)
+        if (p == b || (sep2 > 0 && closer_than(poses5, p, b, sep2))) alive[p] = 0u;
 }
 
 }  // namespace
@@ -323,8 +286,7 @@ extern "C" int pcp_place_sensors(pcp_ctx *ctx, const double *poses5, uint64_t n,
     const int C = o.C, P = o.P, K = pp->k_max;
     *n_selected = 0;
     if (!C) {   // no cells: nothing to cover
-        PCP_HIP(ctx, hipStreamSynchronize(st));
-        prof_resolve(ctx);
+        if (int rc = stream_done(ctx)) return rc;
         if (zx120_total) *zx120_total = 0.0;
         if (zx120_covered) *zx120_covered = 0;
         return PCP_OK;
@@ -332,26 +294,23 @@ extern "C" int pcp_place_sensors(pcp_ctx *ctx, const double *poses5, uint64_t n,
     // the call's block, device and pinned alike: [state | base f64 C | owner i32 C | round
     // totals f64 K x P | round covered i32 K x P | alive u32 P]; the download is the span the
     // caller asked for, in one copy
-    auto a16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    const size_t base_off = sizeof(PlaceState);
-    const size_t own_off = a16(base_off + (size_t)C * sizeof(double));
-    const size_t rt_off = a16(own_off + (size_t)C * sizeof(int32_t));
+    const CellBlock cb = cell_block(sizeof(PlaceState), C);
+    const size_t rt_off = cb.rest_off;
     const size_t rc_off = a16(rt_off + (size_t)K * P * sizeof(double));
     const size_t al_off = a16(rc_off + (size_t)K * P * sizeof(int32_t));
     const size_t bytes = al_off + (size_t)P * sizeof(uint32_t);
     const bool cells_out = cell_score || cell_owner;
-    const size_t down = round_totals ? rc_off : cells_out ? rt_off : base_off;
+    const size_t down = round_totals ? rc_off : cells_out ? rt_off : cb.score_off;
     PCP_HIP(ctx, ctx->place_d.ensure(bytes + 64));
     PCP_HIP(ctx, ctx->place_host.ensure(down + 64));
     char *blk = ctx->place_d.as<char>();
     PlaceState *s = reinterpret_cast<PlaceState *>(blk);
-    double *base = reinterpret_cast<double *>(blk + base_off);
-    int32_t *owner = reinterpret_cast<int32_t *>(blk + own_off);
+    double *base = reinterpret_cast<double *>(blk + cb.score_off);
+    int32_t *owner = reinterpret_cast<int32_t *>(blk + cb.owner_off);
     double *rt = reinterpret_cast<double *>(blk + rt_off);
     int32_t *rcov = reinterpret_cast<int32_t *>(blk + rc_off);
     uint32_t *alive = reinterpret_cast<uint32_t *>(blk + al_off);
-    const double sep = pp->min_separation;
-    const double sep2 = sep > 0 ? sep * sep : 0.0;
+    const double sep2 = sep2_of(pp->min_separation);
     hipLaunchKernelGGL(k_place_init, dim3((unsigned)((std::max(C, P) + kPT - 1) / kPT)), dim3(kPT),
                        0, st, (const double *)o.score_z, C, P, (const double *)o.tot_d,
                        (const int32_t *)o.cov_d, base, owner, alive, s);
@@ -365,8 +324,7 @@ extern "C" int pcp_place_sensors(pcp_ctx *ctx, const double *poses5, uint64_t n,
     }
     char *pin = ctx->place_host.as<char>();
     PCP_HIP(ctx, hipMemcpyAsync(pin, blk, down, hipMemcpyDeviceToHost, st));
-    PCP_HIP(ctx, hipStreamSynchronize(st));
-    prof_resolve(ctx);
+    if (int rc = stream_done(ctx)) return rc;
     const PlaceState *h = reinterpret_cast<const PlaceState *>(pin);
     const int ns = h->n_sel;
     for (int r = 0; r < ns; ++r) {
@@ -376,8 +334,7 @@ extern "C" int pcp_place_sensors(pcp_ctx *ctx, const double *poses5, uint64_t n,
     }
     if (round_totals && ns)
         std::memcpy(round_totals, pin + rt_off, (size_t)ns * P * sizeof(double));
-    if (cell_score) std::memcpy(cell_score, pin + base_off, (size_t)C * sizeof(double));
-    if (cell_owner) std::memcpy(cell_owner, pin + own_off, (size_t)C * sizeof(int32_t));
+    copy_cells(pin, cb, C, cell_score, cell_owner);
     if (zx120_total) *zx120_total = h->zx_total;
     if (zx120_covered) *zx120_covered = h->zx_cov;
     *n_selected = ns;

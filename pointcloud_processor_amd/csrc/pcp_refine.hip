@@ -16,11 +16,14 @@
 //                  slots; the LAST block of the launch picks the first maximum, tests it against
 //                  T, records the move and updates the set; the evaluations enqueued behind a stop
 //                  return at once
-// and k_refine_final folds the final set into cell_score / cell_owner.
+// and k_refine_final folds the final set into cell_score / cell_owner.  The walk, the ticket, the
+// first-maximum reduction, the ordered total, the fold and the separation test are
+// pcp_place_shared.hpp's.
 #include <cmath>
 #include <cstring>
 
 #include "pcp_internal.hpp"
+#include "pcp_place_shared.hpp"
 
 namespace pcp {
 namespace {
@@ -28,14 +31,10 @@ namespace {
 constexpr int kRT = 256;          // threads per block of the preparation, cells per block
 constexpr int kRTile = 16;        // poses per block of an evaluation
 constexpr int kRSl = 64 / kRTile; // slots per wave: lane (j, q) is slot row j against pose q
-constexpr int kRC = 64;           // cells per staged chunk
-constexpr int kRLd = kRC + 2;     // a staged row: 16 rows of b128 reads fall on 16 x 4 distinct banks
-constexpr int kRG = 4;            // b128 reads per row per register group of the walk
 constexpr int kRD = 4;            // chunks a thread's loads run ahead of the walk
 static_assert(kRD == 4, "k_refine_eval names its four register sets");
 static_assert(kRTile == PCP_PLACE_MAX, "four waves of kRSl slot rows are the whole set");
-static_assert((kRC / 2) % (2 * kRG) == 0, "whole group pairs per chunk");
-static_assert(kRT % kRC == 0 && kRLd % 2 == 0, "whole chunks per preparation block");
+static_assert(kRT % kWalkC == 0, "whole chunks per preparation block");
 
 // the call's state: control words of the evaluations and the result record (downloaded)
 struct RefineState {
@@ -58,28 +57,8 @@ struct RefineSet {
     int32_t idx[PCP_PLACE_MAX];
 };
 
-// a block's best: the first maximum in row-major order (slot, then pose) among its admissible rows
-struct RefineBest {
-    double t;
-    int32_t a, b;
-};
-static_assert(sizeof(RefineBest) == 16, "two 8-byte words");
-
-// (t2, a2, b2) ahead of (t1, a1, b1): a larger total, or the same and earlier in row-major order
-__device__ __forceinline__ bool row_ahead(double t2, int a2, int b2, double t1, int a1, int b1) {
-    return a2 >= 0 && (a1 < 0 || t2 > t1 || (t2 == t1 && (a2 < a1 || (a2 == a1 && b2 < b1))));
-}
-
-// the larger of two values that are finite, not NaN and never -0.0 (the clamped rows'): one
-// instruction, and for equal values their common bits -- the reference's std::max on these inputs
 // a staged pair of cells in registers (a native vector: the register sets stay in VGPRs)
 typedef double v2d __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ double max_pos(double a, double b) {
-    double r;
-    asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
 
 // Once per call: the clamped rows Sc [Pp][Cs] (+0.0 in the rows past P and the cells past C), the
 // slot rows Lc [kRTile][Cs] zeroed (the preparation stores the unlocked slots' cells below C
@@ -145,26 +124,13 @@ k_refine_prep(const double *__restrict__ S, const double *__restrict__ Z, int C,
         return first;
     };
     if ((int)blockIdx.x == ncb) {   // ---- the start total (the first evaluation only)
-        if (tid == 0) s_cnt = 0;
-        double acc = 0.0;
-        int32_t cnt = 0;
-        for (int c0 = 0; c0 < C; c0 += kRT) {
-            __syncthreads();
-            double second;
-            int arg;
-            const double b = c0 + tid < C ? top2(c0 + tid, second, arg) : 0.0;
-            const bool pos = b > 0;
-            cnt += pos ? 1 : 0;
-            s_b[tid] = pos ? b : 0.0;
-            __syncthreads();
-            if (tid == 0) {
-#pragma unroll 16
-                for (int i = 0; i < kRT; ++i) acc += s_b[i];   // (+0.0 is bit-neutral)
-            }
-        }
-        __syncthreads();
-        atomicAdd(&s_cnt, cnt);
-        __syncthreads();
+        const double acc = ordered_total<kRT>(
+            [&](int c) {
+                double second;
+                int arg;
+                return top2(c, second, arg);
+            },
+            C, s_b, s_cnt);
         if (tid == 0) {
             s->start_total = acc;
             s->T = acc;
@@ -188,10 +154,10 @@ k_refine_prep(const double *__restrict__ S, const double *__restrict__ Z, int C,
 // +0.0, one rounded add per cell (+0.0 for the cells that are not positive and for the padding
 // past C: bit-neutral).  W = 1, 2 or 4 waves for up to 4, 8 or 16 unlocked slots: a small set
 // neither stages nor walks sixteen slot rows (four waves take 18 % longer than one or two).  The
-// block stages chunks of kRC cells of its kRSl W slot rows and its kRTile pose rows -- coalesced
-// b128 loads, kRD chunks ahead in registers, stored to LDS as they lie, rows kRLd apart -- and
-// every lane reads two cells of its slot row and of its pose row per ds_read_b128 (k_pair_tiles'
-// walk: a pose's loads are shared by every slot).
+// block stages chunks of kWalkC cells of its kRSl W slot rows and its kRTile pose rows -- coalesced
+// b128 loads, kRD chunks ahead in registers, stored to LDS as they lie, rows kWalkLd apart -- and
+// every lane reads two cells of its slot row and of its pose row per ds_read_b128 (walk_chunk, as
+// k_pair_tiles: a pose's loads are shared by every slot).
 //
 // The last block to draw the evaluation's ticket (its best released to the device before the
 // draw, the others' acquired after it) takes the first maximum of the blocks' bests in row-major
@@ -203,16 +169,16 @@ template <int W>
 __global__ void __launch_bounds__(64 * W)
 k_refine_eval(const double *__restrict__ Lc, const double *__restrict__ Sc, int Cs, int C, int P,
               int K, int n_locked, const double *__restrict__ poses5, double sep2,
-              RefineBest *slots, double *__restrict__ table, RefineState *s, int max_moves,
+              RowBest *slots, double *__restrict__ table, RefineState *s, int max_moves,
               int commit) {
     constexpr int kT = 64 * W;                    // threads
     constexpr int kA = kRSl * W;                  // staged slot rows
     constexpr int kRows = kA + kRTile;            // and the pose rows behind them
-    constexpr int kStep = kT / (kRC / 2);         // rows one b128 load of every thread covers
+    constexpr int kStep = kT / (kWalkC / 2);         // rows one b128 load of every thread covers
     constexpr int kNL = kRows / kStep;            // b128 loads per thread per chunk
     static_assert(kRows % kStep == 0 && kA % kStep == 0, "whole loads; a load is of one kind");
-    __shared__ double2 s_m[2][kRows * kRLd / 2];
-    __shared__ RefineBest s_best[W];
+    __shared__ double2 s_m[2][kRows * kWalkLd / 2];
+    __shared__ RowBest s_best[W];
     __shared__ int s_set[PCP_PLACE_MAX];
     __shared__ int s_flag;
     __shared__ int32_t s_cnt;
@@ -224,19 +190,19 @@ k_refine_eval(const double *__restrict__ Lc, const double *__restrict__ Sc, int 
     const int tb = blockIdx.x;
     double acc = 0.0;
     {
-        const int nch = Cs / kRC;
+        const int nch = Cs / kWalkC;
         const int ia = tid / kRTile, jb = kA + tid % kRTile;
         // a thread's b128 loads per chunk: double2 `col` of the rows r0 + kStep i, slot rows
         // first (32 threads per row: 512 contiguous bytes)
-        const int r0 = tid / (kRC / 2), col = tid % (kRC / 2);
+        const int r0 = tid / (kWalkC / 2), col = tid % (kWalkC / 2);
         const v2d *srcA = reinterpret_cast<const v2d *>(Lc + (size_t)r0 * Cs) + col;
         const v2d *srcB = reinterpret_cast<const v2d *>(Sc + (size_t)(tb * kRTile + r0) * Cs) + col;
         const size_t step = (size_t)kStep * Cs / 2;          // kStep rows in double2
-        const int dst = r0 * (kRLd / 2) + col;
+        const int dst = r0 * (kWalkLd / 2) + col;
         v2d g0[kNL], g1[kNL], g2[kNL], g3[kNL];
         auto load = [&](int k, v2d (&r)[kNL]) __attribute__((always_inline)) {
             // (past the end: the last chunk once more)
-            const size_t o = (size_t)min(k, nch - 1) * (kRC / 2);
+            const size_t o = (size_t)min(k, nch - 1) * (kWalkC / 2);
 #pragma unroll
             for (int i = 0; i < kNL; ++i)
                 r[i] = i < kA / kStep ? srcA[o + i * step] : srcB[o + (i - kA / kStep) * step];
@@ -244,40 +210,7 @@ k_refine_eval(const double *__restrict__ Lc, const double *__restrict__ Sc, int 
         auto store = [&](int buf, const v2d (&r)[kNL]) __attribute__((always_inline)) {
             v2d *d = reinterpret_cast<v2d *>(s_m[buf]) + dst;
 #pragma unroll
-            for (int i = 0; i < kNL; ++i) d[i * kStep * (kRLd / 2)] = r[i];
-        };
-        auto walk = [&](int buf) __attribute__((always_inline)) {
-            // two register groups of kRG b128 reads per row: the adds of one group run while the
-            // other's reads are in flight; the scheduling barriers keep each group's reads ahead
-            // of the adds before it
-            const double2 *va = s_m[buf] + ia * (kRLd / 2), *vb = s_m[buf] + jb * (kRLd / 2);
-            double2 a0[kRG], b0[kRG], a1[kRG], b1[kRG];
-            auto rd = [&](double2 *a, double2 *b, int j) {
-#pragma unroll
-                for (int i = 0; i < kRG; ++i) {
-                    a[i] = va[j + i];
-                    b[i] = vb[j + i];
-                }
-            };
-            auto add = [&](const double2 *a, const double2 *b) {
-#pragma unroll
-                for (int i = 0; i < kRG; ++i) {
-                    acc += max_pos(a[i].x, b[i].x);
-                    acc += max_pos(a[i].y, b[i].y);
-                }
-            };
-            rd(a0, b0, 0);
-#pragma unroll
-            for (int j = 0; j < kRC / 2; j += 2 * kRG) {
-                rd(a1, b1, j + kRG);
-                __builtin_amdgcn_sched_barrier(0);
-                add(a0, b0);
-                __builtin_amdgcn_sched_barrier(0);
-                if (j + 2 * kRG < kRC / 2) rd(a0, b0, j + 2 * kRG);
-                __builtin_amdgcn_sched_barrier(0);
-                add(a1, b1);
-                __builtin_amdgcn_sched_barrier(0);
-            }
+            for (int i = 0; i < kNL; ++i) d[i * kStep * (kWalkLd / 2)] = r[i];
         };
         // kRD chunks in flight in registers: a chunk's walk is a fraction of a load's latency, so
         // the loads run that many chunks ahead of the walk.  While chunk k is walked, g[(k + 1)
@@ -287,7 +220,7 @@ k_refine_eval(const double *__restrict__ Lc, const double *__restrict__ Sc, int 
         // prefetch in registers)
         auto chunk = [&](int k, int buf, v2d (&next)[kNL]) __attribute__((always_inline)) {
             if (k < nch) {   // (uniform)
-                walk(buf);
+                walk_chunk(s_m[buf] + ia * (kWalkLd / 2), s_m[buf] + jb * (kWalkLd / 2), acc);
                 store(buf ^ 1, next);
                 load(k + 1 + kRD, next);
                 __syncthreads();
@@ -316,10 +249,7 @@ k_refine_eval(const double *__restrict__ Lc, const double *__restrict__ Sc, int 
         for (int j = 0; j < K; ++j) {
             const int q = s_set[j];
             ok &= q != p;
-            if (sep2 > 0 && j != slot) {
-                const double dx = px - poses5[5 * (size_t)q], dy = py - poses5[5 * (size_t)q + 1];
-                ok &= !(dx * dx + dy * dy < sep2);
-            }
+            if (sep2 > 0 && j != slot) ok &= !closer_than(px, py, poses5, q, sep2);
         }
     }
     double bt = ok ? acc : -INFINITY;
@@ -330,44 +260,14 @@ k_refine_eval(const double *__restrict__ Lc, const double *__restrict__ Sc, int 
     }
     // the block's first maximum in row-major order
     int ba = ok ? slot : -1, bb = ok ? p : -1;
-    auto take = [&](double t2, int a2, int b2) {
-        if (row_ahead(t2, a2, b2, bt, ba, bb)) {
-            bt = t2;
-            ba = a2;
-            bb = b2;
-        }
-    };
-    auto reduce = [&] {   // the block's best into thread 0
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1)
-            take(__shfl_xor(bt, o, 64), __shfl_xor(ba, o, 64), __shfl_xor(bb, o, 64));
-        if ((tid & 63) == 0) s_best[tid >> 6] = RefineBest{bt, ba, bb};
-        __syncthreads();
-        if (tid == 0)
-            for (int w = 1; w < W; ++w) take(s_best[w].t, s_best[w].a, s_best[w].b);
-    };
-    reduce();
+    block_first_max<W>(s_best, bt, ba, bb);
     if (tid == 0) {
         unsigned long long *w = reinterpret_cast<unsigned long long *>(&slots[blockIdx.x]);
         w[0] = (unsigned long long)__double_as_longlong(bt);
         w[1] = (unsigned long long)(uint32_t)ba | ((unsigned long long)(uint32_t)bb << 32);
     }
     // the evaluation's ticket: this block's best written back before the draw
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const uint32_t t =
-            __hip_atomic_fetch_add(&s->ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_flag = t == gridDim.x - 1;
-        if (s_flag) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-    }
-    __syncthreads();
-    if (!s_flag) return;
+    if (!last_block(&s->ticket, s_flag)) return;
 
     // ---- the last block of the evaluation ---------------------------------------------------
     bt = -INFINITY;
@@ -378,12 +278,13 @@ k_refine_eval(const double *__restrict__ Lc, const double *__restrict__ Sc, int 
             __hip_atomic_load(&w[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const unsigned long long w1 =
             __hip_atomic_load(&w[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        take(__longlong_as_double((long long)w0), (int)(uint32_t)w1, (int)(uint32_t)(w1 >> 32));
+        take_ahead(bt, ba, bb, __longlong_as_double((long long)w0), (int)(uint32_t)w1,
+                   (int)(uint32_t)(w1 >> 32));
     }
     __syncthreads();   // (s_best's readers of the block's own reduction are done)
-    reduce();
+    block_first_max<W>(s_best, bt, ba, bb);
     if (tid == 0) {
-        s_best[0] = RefineBest{bt, ba, bb};
+        s_best[0] = RowBest{bt, ba, bb};
         s_cnt = 0;
         s->ticket = 0u;   // (the next launch draws from zero)
         // no admissible row, or the best exchange adds nothing; or it does and no move is left
@@ -432,14 +333,8 @@ k_refine_final(const double *__restrict__ S, const double *__restrict__ Z, int C
     const int c = blockIdx.x * kRT + threadIdx.x;
     if (c >= C) return;
     double b = Z[c];
-    int32_t own = b > 0 ? PCP_OWNER_ZX120 : PCP_OWNER_NONE;
-    for (int i = 0; i < K; ++i) {
-        const double v = S[(size_t)s->set[i] * C + c];
-        if (b < v) {   // std::max(base, S); ties keep the earlier owner
-            b = v;
-            own = i;
-        }
-    }
+    int32_t own = owner_of_zx(b);
+    for (int i = 0; i < K; ++i) fold_owner(b, own, S[(size_t)s->set[i] * C + c], i);
     cs[c] = b;
     owner[c] = own;
 }
@@ -449,12 +344,12 @@ k_refine_final(const double *__restrict__ S, const double *__restrict__ Z, int C
 // the scratch (refine_m): [Sc f64 Pp x Cs | Lc f64 kRTile x Cs | block bests]
 struct RefinePlan {
     int C, P, Pp, Cs, nblk, ncb, K, n_locked, max_moves;
-    size_t cs_off, own_off, tab_off, bytes, lc_off, slot_off, m_bytes;
+    CellBlock cb;   // tab_off = cb.rest_off
+    size_t tab_off, bytes, lc_off, slot_off, m_bytes;
     bool dense;
 };
 
 RefinePlan make_plan(int C, int P, const pcp_refine_params *rp, bool dense) {
-    auto a16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
     RefinePlan s{};
     s.C = C;
     s.P = P;
@@ -463,17 +358,16 @@ RefinePlan make_plan(int C, int P, const pcp_refine_params *rp, bool dense) {
     s.max_moves = rp->max_moves;
     s.nblk = (P + kRTile - 1) / kRTile;
     s.Pp = s.nblk * kRTile;
-    s.Cs = (C + kRC - 1) / kRC * kRC;
+    s.Cs = (C + kWalkC - 1) / kWalkC * kWalkC;
     s.ncb = (C + kRT - 1) / kRT;
     s.dense = dense;
-    s.cs_off = sizeof(RefineState);
-    s.own_off = a16(s.cs_off + (size_t)C * sizeof(double));
-    s.tab_off = a16(s.own_off + (size_t)C * sizeof(int32_t));
+    s.cb = cell_block(sizeof(RefineState), C);
+    s.tab_off = s.cb.rest_off;
     s.bytes = s.tab_off +
               (dense ? (size_t)(s.max_moves + 1) * s.K * P * sizeof(double) : 0);
     s.lc_off = (size_t)s.Pp * s.Cs * sizeof(double);
     s.slot_off = s.lc_off + (size_t)kRTile * s.Cs * sizeof(double);
-    s.m_bytes = s.slot_off + (size_t)s.nblk * sizeof(RefineBest);
+    s.m_bytes = s.slot_off + (size_t)s.nblk * sizeof(RowBest);
     return s;
 }
 
@@ -481,19 +375,19 @@ struct RefinePtrs {
     RefineState *state;
     double *cs, *table, *Sc, *Lc;
     int32_t *owner;
-    RefineBest *slots;
+    RowBest *slots;
 };
 
 RefinePtrs pointers(pcp_ctx *ctx, const RefinePlan &s) {
     char *blk = ctx->refine_d.as<char>(), *m = ctx->refine_m.as<char>();
     RefinePtrs q;
     q.state = reinterpret_cast<RefineState *>(blk);
-    q.cs = reinterpret_cast<double *>(blk + s.cs_off);
-    q.owner = reinterpret_cast<int32_t *>(blk + s.own_off);
+    q.cs = reinterpret_cast<double *>(blk + s.cb.score_off);
+    q.owner = reinterpret_cast<int32_t *>(blk + s.cb.owner_off);
     q.table = s.dense ? reinterpret_cast<double *>(blk + s.tab_off) : nullptr;
     q.Sc = reinterpret_cast<double *>(m);
     q.Lc = reinterpret_cast<double *>(m + s.lc_off);
-    q.slots = reinterpret_cast<RefineBest *>(m + s.slot_off);
+    q.slots = reinterpret_cast<RowBest *>(m + s.slot_off);
     return q;
 }
 
@@ -544,21 +438,7 @@ int check_args(pcp_ctx *ctx, const char *what, uint64_t n, const pcp_refine_para
                        "0..%d or reserved %d != 0",
                        what, (int)rp->k, PCP_PLACE_MAX, (int)rp->n_locked, (int)rp->max_moves,
                        PCP_REFINE_MAX_MOVES, (int)rp->reserved);
-    if (n > PCP_PAIR_MAX_POSES)
-        return set_err(ctx, PCP_E_INVALID, "%s: %llu poses, at most %d per call", what,
-                       (unsigned long long)n, PCP_PAIR_MAX_POSES);
-    for (int i = 0; i < rp->k; ++i) {
-        const int64_t f = rp->start[i];
-        if (f < 0 || (uint64_t)f >= n)
-            return set_err(ctx, PCP_E_INVALID, "%s: start[%d] = %lld is no pose of %llu", what, i,
-                           (long long)f, (unsigned long long)n);
-        for (int j = 0; j < i; ++j)
-            if (rp->start[j] == f)
-                return set_err(ctx, PCP_E_INVALID, "%s: pose %lld is in the set twice", what,
-                               (long long)f);
-        start.idx[i] = (int32_t)f;
-    }
-    return PCP_OK;
+    return check_pose_list(ctx, what, "start", "in the set", rp->start, rp->k, n, start.idx);
 }
 
 }  // namespace
@@ -589,8 +469,7 @@ extern "C" int pcp_place_refine(pcp_ctx *ctx, const double *poses5, uint64_t n, 
     hipStream_t st = ctx->stream;
     const int C = o.C, P = o.P, K = rp->k;
     if (!C) {   // no cells: nothing to cover, nothing to gain
-        PCP_HIP(ctx, hipStreamSynchronize(st));
-        prof_resolve(ctx);
+        if (int rc = stream_done(ctx)) return rc;
         for (int i = 0; i < K; ++i) selected[i] = rp->start[i];
         *total = *start_total = 0.0;
         *covered = *start_covered = 0;
@@ -600,11 +479,11 @@ extern "C" int pcp_place_refine(pcp_ctx *ctx, const double *poses5, uint64_t n, 
     }
     const RefinePlan s = make_plan(C, P, rp, swap_totals != nullptr);
     const bool cells_out = cell_score || cell_owner;
-    const size_t down = s.dense ? s.bytes : cells_out ? s.tab_off : s.cs_off;
+    const size_t down = s.dense ? s.bytes : cells_out ? s.tab_off : s.cb.score_off;
     PCP_HIP(ctx, ctx->refine_d.ensure(s.bytes + 64));
     PCP_HIP(ctx, ctx->refine_m.ensure(s.m_bytes + 64));
     PCP_HIP(ctx, ctx->refine_host.ensure(down + 64));
-    const double sep = rp->min_separation, sep2 = sep > 0 ? sep * sep : 0.0;
+    const double sep2 = sep2_of(rp->min_separation);
     if (int rc = init_enqueue(ctx, s, o, start)) return rc;
     // every evaluation the moves allow, back to back: those behind the stop return at once
     for (int e = 0; e <= s.max_moves; ++e)
@@ -618,8 +497,7 @@ extern "C" int pcp_place_refine(pcp_ctx *ctx, const double *poses5, uint64_t n, 
     }
     char *pin = ctx->refine_host.as<char>();
     PCP_HIP(ctx, hipMemcpyAsync(pin, ctx->refine_d.as<char>(), down, hipMemcpyDeviceToHost, st));
-    PCP_HIP(ctx, hipStreamSynchronize(st));
-    prof_resolve(ctx);
+    if (int rc = stream_done(ctx)) return rc;
     const RefineState *h = reinterpret_cast<const RefineState *>(pin);
     const int nm = h->n_moves;
     for (int i = 0; i < K; ++i) selected[i] = h->set[i];
@@ -638,8 +516,7 @@ extern "C" int pcp_place_refine(pcp_ctx *ctx, const double *poses5, uint64_t n, 
     *converged = h->converged;
     if (swap_totals)
         host_copy(ctx, swap_totals, pin + s.tab_off, (size_t)(nm + 1) * K * P * sizeof(double));
-    if (cell_score) std::memcpy(cell_score, pin + s.cs_off, (size_t)C * sizeof(double));
-    if (cell_owner) std::memcpy(cell_owner, pin + s.own_off, (size_t)C * sizeof(int32_t));
+    copy_cells(pin, s.cb, C, cell_score, cell_owner);
     return PCP_OK;
 }
 
@@ -656,35 +533,20 @@ extern "C" int pcp_place_refine_burst(pcp_ctx *ctx, const double *poses5, uint64
     *ms_per_eval = 0.0;
     ScoreEnq o;
     if (int rc = score_enqueue(ctx, poses5, n, zx, p, o)) return rc;
-    hipStream_t st = ctx->stream;
     if (!o.C) {
-        PCP_HIP(ctx, hipStreamSynchronize(st));
-        prof_resolve(ctx);
+        if (int rc = stream_done(ctx)) return rc;
         return set_err(ctx, PCP_E_INVALID, "pcp_place_refine_burst: no cells, nothing to time");
     }
     const RefinePlan s = make_plan(o.C, o.P, rp, false);
     PCP_HIP(ctx, ctx->refine_d.ensure(s.bytes + 64));
     PCP_HIP(ctx, ctx->refine_m.ensure(s.m_bytes + 64));
-    const double sep = rp->min_separation, sep2 = sep > 0 ? sep * sep : 0.0;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    PCP_HIP(ctx, hipEventCreate(&e0));
-    PCP_HIP(ctx, hipEventCreate(&e1));
+    const double sep2 = sep2_of(rp->min_separation);
     // the start set's evaluation, over and over: nothing is committed, so every repetition does
     // the whole work of a live evaluation.  Once untimed: the start total and the first touches
-    int rc = init_enqueue(ctx, s, o, start);
-    if (!rc) rc = eval_enqueue(ctx, s, o, sep2, 0, true, false);
-    hipError_t e = rc ? hipSuccess : hipEventRecord(e0, st);
-    for (int r = 0; r < reps && !rc && e == hipSuccess; ++r)
-        rc = eval_enqueue(ctx, s, o, sep2, 0, false, false);
-    if (!rc && e == hipSuccess) e = hipEventRecord(e1, st);
-    if (!rc && e == hipSuccess) e = hipEventSynchronize(e1);
-    float t = 0.0f;
-    if (!rc && e == hipSuccess) e = hipEventElapsedTime(&t, e0, e1);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (rc) return rc;
-    if (e != hipSuccess) return hip_fail(ctx, e, "pcp_place_refine_burst", __FILE__, __LINE__);
-    *ms_per_eval = (double)t / reps;
-    prof_resolve(ctx);
-    return PCP_OK;
+    auto warm = [&] {
+        const int rc = init_enqueue(ctx, s, o, start);
+        return rc ? rc : eval_enqueue(ctx, s, o, sep2, 0, true, false);
+    };
+    auto body = [&] { return eval_enqueue(ctx, s, o, sep2, 0, false, false); };
+    return time_reps(ctx, "pcp_place_refine_burst", ctx->stream, reps, warm, body, ms_per_eval);
 }

@@ -27,7 +27,8 @@ ROOT = Path(__file__).resolve().parents[1]
 CLI = ROOT / "pointcloud_processor_amd" / "_lib" / "pcp_nodes_cli"
 GAP = 0.1
 T = 16        # the pair tile's edge in poses (kPairTile; tests/test_pair_tiles_host.py pins it)
-CHUNK = 64    # cells per staged chunk of a tile and per preparation block (kQC)
+CHUNK = 64    # cells per staged chunk of a tile and per preparation block (kWalkC of
+              # pcp_place_shared.hpp; tests/test_place_shared_host.py pins it)
 CHAIN = 256   # cells per step of the base total's chain (kQT; runs with fixed sensors only)
 
 

@@ -27,7 +27,7 @@ ROOT = Path(__file__).resolve().parents[1]
 CLI = ROOT / "pointcloud_processor_amd" / "_lib" / "pcp_nodes_cli"
 GAP = 0.1
 TILE = 16     # poses per block of an evaluation (kRTile)
-CHUNK = 64    # cells per staged chunk of an evaluation (kRC)
+CHUNK = 64    # cells per staged chunk of an evaluation (kWalkC of pcp_place_shared.hpp)
 PREP = 256    # cells per preparation block and per step of the start total's chain (kRT)
 G6 = [40, 41, 48, 32, 49, 56]                  # greedy k = 6
 G6S = [40, 41, 56, 24, 57, 46]                 # greedy k = 6 at 2 m

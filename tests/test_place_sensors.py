@@ -214,6 +214,22 @@ def test_duplicates_and_ties(tick):
     assert got["n_selected"] == 2
 
 
+def test_ties_across_threads_and_waves(tick):
+    """P = 2 x 256 + 3 poses, the tick's 91 candidates repeated: every pose has exact copies 91,
+    182, .. later.  A thread of the round's last block then scans up to three poses, and the tied
+    maxima sit in different threads and waves of its first-maximum reduction: every round picks
+    the lowest index among the tied rows."""
+    idx = np.arange(2 * 256 + 3) % 91
+    got, orc = _case(tick, idx, 385, 4, margins=False)   # (exact ties: same rows)
+    assert orc["n_selected"] == 4 and got["n_selected"] == 4
+    assert np.all(got["selected"] < 91)
+    for r in range(4):
+        t = got["round_totals"][r]
+        tied = np.flatnonzero(t == t.max())
+        assert tied.size >= 5 and np.all(tied % 91 == tied[0])
+        assert got["selected"][r] == tied[0]
+
+
 def test_isolation(tick):
     """pcp_score_poses before and after a placement on one context: identical; the caller's
     flags are not touched; the scratch allocations settle after the first call."""
