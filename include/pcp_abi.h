@@ -609,6 +609,47 @@ int pcp_simulate_scan(pcp_ctx *ctx, const double *poses5, uint64_t n, const pcp_
 int pcp_simulate_scan_burst(pcp_ctx *ctx, const double *poses5, uint64_t n,
                             const pcp_fan_params *fan, int reps, double ms[2]);
 
+/* The fan and the simulated scan of tilted mounts, with an optional beam table.
+ * poses6: x, y, z, roll, pitch, yaw per sensor (radians).  pitch has the sign of poses5's pitch:
+ * the elevation of the boresight, so negative looks down.  A tf static transform
+ * "x y z yaw pitch_tf roll" is pitch = -pitch_tf (the zx120 Velodyne: pitch = -0.4363).
+ * For ray (i, j) the local direction is l = (ce_j ca_i, ce_j sa_i, se_j): ca, sa as
+ * pcp_raycast_fan's; with el_table (nullable, [fan->n_el] radians, any order) ce_j =
+ * cos(el_table[j]), se_j = sin(el_table[j]) and fan->el_min / el_max are not read, without it
+ * the fan's uniform table.  Every cos / sin -- the tables', roll's, pitch's, yaw's -- is the host
+ * C library's double function.  Then three plane rotations in double, every product and sum
+ * rounded on its own (no contraction):
+ *   x1 = lx               y1 = ly*cr - lz*sr    z1 = ly*sr + lz*cr    (roll about the boresight)
+ *   x2 = x1*cp - z1*sp    y2 = y1               z2 = x1*sp + z1*cp    (pitch: (1,0,0) -> (cp,0,sp))
+ *   dx = cy*x2 - sy*y2    dy = sy*x2 + cy*y2    dz = z2               (yaw, as pcp_raycast_fan)
+ * Everything after the direction is pcp_raycast_fan's / pcp_simulate_scan's definition word for
+ * word: the step table, q = float(p + d s_k), the strict float r2 predicate, first_hit, blocked,
+ * units, best_idx, and for the scan the hit point, range, records, offsets, dense images, mask
+ * and counts.  With roll = pitch = 0 the direction equals the level fan's as a value (a component
+ * can differ in the sign of a zero only), so every output equals the level call's.
+ * Limits and errors are the level calls'; in addition a non-finite el_table entry is
+ * PCP_E_INVALID before any launch, nothing written.  One host synchronisation per call,
+ * deterministic; the caller's GridCell flags and the other queries' buffers are not touched.
+ * The launch is timed under PCP_K_RAYCAST_FAN.  Not offered: the multi-GPU and all-reduce forms,
+ * the diagnostic modes, an azimuth sector, several beam models in one call. */
+int pcp_raycast_fan_mounted(pcp_ctx *ctx, const double *poses6, uint64_t n,
+                            const pcp_fan_params *fan, const double *el_table, uint32_t *blocked,
+                            uint64_t *units, int16_t *first_hit, int64_t *best_idx);
+int pcp_simulate_scan_mounted(pcp_ctx *ctx, const double *poses6, uint64_t n,
+                              const pcp_fan_params *fan, const double *el_table,
+                              pcp_scan_return *returns, uint64_t returns_cap, uint64_t *n_returns,
+                              uint64_t *offsets, int32_t *hit_point, float *range_img,
+                              int16_t *first_hit, uint64_t *point_mask, uint64_t mask_cap,
+                              uint64_t *n_points, uint32_t *seen_points, uint64_t *n_seen_any);
+/* Kernel timing (the timing tool only): as pcp_raycast_fan_burst / pcp_simulate_scan_burst, of
+ * the mounted query's production launch and resolve phase. */
+int pcp_raycast_fan_mounted_burst(pcp_ctx *ctx, const double *poses6, uint64_t n,
+                                  const pcp_fan_params *fan, const double *el_table, int reps,
+                                  double *ms_per_launch);
+int pcp_simulate_scan_mounted_burst(pcp_ctx *ctx, const double *poses6, uint64_t n,
+                                    const pcp_fan_params *fan, const double *el_table, int reps,
+                                    double ms[2]);
+
 /* Diagnostic build with s_memtime stamps (shader clock) per wave: stamps[(p*W + w)*4 + i],
  * W = ceil(n_az*n_el/64), i = 0 start, 1 after direction setup, 2 after the march, 3 end.
  * For locating where wave lifetime goes; never used for timing. */

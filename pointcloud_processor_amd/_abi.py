@@ -244,6 +244,16 @@ _SIGS = [
                                     C.POINTER(C.c_uint64), _P, C.POINTER(C.c_uint64)]),
     ("pcp_simulate_scan_burst", C.c_int, [_P, _P, C.c_uint64, C.POINTER(FanParams), C.c_int,
                                           _P]),
+    ("pcp_raycast_fan_mounted", C.c_int, [_P, _P, C.c_uint64, C.POINTER(FanParams), _P, _P, _P, _P,
+                                          C.POINTER(C.c_int64)]),
+    ("pcp_raycast_fan_mounted_burst", C.c_int, [_P, _P, C.c_uint64, C.POINTER(FanParams), _P,
+                                                C.c_int, C.POINTER(C.c_double)]),
+    ("pcp_simulate_scan_mounted", C.c_int, [_P, _P, C.c_uint64, C.POINTER(FanParams), _P, _P,
+                                            C.c_uint64, C.POINTER(C.c_uint64), _P, _P, _P, _P, _P,
+                                            C.c_uint64, C.POINTER(C.c_uint64), _P,
+                                            C.POINTER(C.c_uint64)]),
+    ("pcp_simulate_scan_mounted_burst", C.c_int, [_P, _P, C.c_uint64, C.POINTER(FanParams), _P,
+                                                  C.c_int, _P]),
     ("pcp_debug_exclusive_scan", C.c_int, [_P, _P, C.c_uint64, _P]),
     ("pcp_debug_fine_copy", C.c_int, [_P, C.POINTER(FineGeo), _P, C.c_uint64, _P, C.c_uint64, _P,
                                       C.c_uint64]),
@@ -1162,7 +1172,7 @@ class Context:
 
     def simulate_scan(self, poses5, fan: FanParams, want_dense: bool = False,
                       want_mask: bool = True, returns_cap: int | None = None,
-                      mask_cap: int | None = None) -> dict:
+                      mask_cap: int | None = None, _mounted=None) -> dict:
         """pcp_simulate_scan: the fan of up to SCAN_MAX_POSES poses with every blocked ray
         resolved to the terrain point it hit.  -> dict: returns (SCAN_RETURN_DTYPE, the poses'
         segments in ray order), offsets [P + 1], n_points, hit_point / range / first_hit
@@ -1170,7 +1180,11 @@ class Context:
         n_seen_any (want_mask, else None).  returns_cap None: n * n_az * n_el; mask_cap None: the
         terrain cloud's size.  A short capacity raises PcpError(PCP_E_CAPACITY) whose `partial`
         attribute holds the same dict (counts, offsets and dense outputs valid)."""
-        poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 5)
+        # (_mounted: simulate_scan_mounted's (el_table,), the same call on poses6 rows)
+        poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 6 if _mounted else 5)
+        what = "pcp_simulate_scan_mounted" if _mounted else "pcp_simulate_scan"
+        fn = getattr(self.lib, what)
+        lead = (_ptr(_mounted[0]),) if _mounted else ()
         P = poses.shape[0]
         rays = int(fan.n_az) * int(fan.n_el)
         cap = P * rays if returns_cap is None else int(returns_cap)
@@ -1186,12 +1200,13 @@ class Context:
         mask = np.zeros(max(mcap, 1), np.uint64) if want_mask else None
         seen = np.zeros(max(P, 1), np.uint32) if want_mask else None
         nret, npts, nany = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        rc = self.lib.pcp_simulate_scan(
-            self.h, _ptr(poses) if P else None, P, C.byref(fan), _ptr(ret), cap, C.byref(nret),
+        rc = fn(
+            self.h, _ptr(poses) if P else None, P, C.byref(fan), *lead, _ptr(ret), cap,
+            C.byref(nret),
             _ptr(offsets), _ptr(hp), _ptr(rg), _ptr(fh), _ptr(mask), mcap, C.byref(npts),
             _ptr(seen), C.byref(nany) if want_mask else None)
         if rc not in (PCP_OK, PCP_E_CAPACITY):
-            self._check(rc, "pcp_simulate_scan")
+            self._check(rc, what)
         N = npts.value
         # (views of the call's own arrays: no second copy of a scan's tens of megabytes)
         out = {"returns": ret[:min(nret.value, cap)], "n_returns": nret.value,
@@ -1201,11 +1216,67 @@ class Context:
                "n_seen_any": nany.value if want_mask else None}
         if rc == PCP_E_CAPACITY:
             try:
-                self._check(rc, "pcp_simulate_scan")
+                self._check(rc, what)
             except PcpError as e:
                 e.partial = out
                 raise
         return out
+
+    @staticmethod
+    def _el_table(fan: FanParams, el_table):
+        if el_table is None:
+            return None
+        t = np.ascontiguousarray(el_table, np.float64).reshape(-1)
+        if t.shape[0] != int(fan.n_el):
+            raise ValueError(f"el_table: {t.shape[0]} entries for n_el = {int(fan.n_el)}")
+        return t
+
+    def simulate_scan_mounted(self, poses6, fan: FanParams, el_table=None,
+                              want_dense: bool = False, want_mask: bool = True,
+                              returns_cap: int | None = None,
+                              mask_cap: int | None = None) -> dict:
+        """pcp_simulate_scan_mounted: simulate_scan from tilted mounts -- poses6 rows x, y, z,
+        roll, pitch, yaw (pitch negative looks down) -- with an optional beam table el_table
+        [n_el] in radians.  -> simulate_scan's dict."""
+        return self.simulate_scan(poses6, fan, want_dense, want_mask, returns_cap, mask_cap,
+                                  _mounted=(self._el_table(fan, el_table),))
+
+    def raycast_fan_mounted(self, poses6, fan: FanParams, el_table=None, want_first_hit=False):
+        """pcp_raycast_fan_mounted -> raycast_fan's (blocked, units, first_hit, best_idx) for
+        poses6 rows x, y, z, roll, pitch, yaw and an optional beam table [n_el] (radians)."""
+        poses = np.ascontiguousarray(poses6, np.float64).reshape(-1, 6)
+        tab = self._el_table(fan, el_table)
+        P = poses.shape[0]
+        blocked = np.zeros(max(P, 1), np.uint32)
+        units = np.zeros(max(P, 1), np.uint64)
+        fh = np.empty((P, fan.n_el, fan.n_az), np.int16) if want_first_hit else None
+        best = C.c_int64()
+        self._check(self.lib.pcp_raycast_fan_mounted(self.h, _ptr(poses), P, C.byref(fan),
+                                                     _ptr(tab), _ptr(blocked), _ptr(units),
+                                                     _ptr(fh), C.byref(best)),
+                    "pcp_raycast_fan_mounted")
+        return blocked[:P].copy(), units[:P].copy(), fh, best.value
+
+    def raycast_fan_mounted_burst(self, poses6, fan: FanParams, el_table=None,
+                                  reps: int = 20) -> float:
+        """pcp_raycast_fan_mounted_burst -> the mounted launch's ms per launch."""
+        poses = np.ascontiguousarray(poses6, np.float64).reshape(-1, 6)
+        ms = C.c_double()
+        self._check(self.lib.pcp_raycast_fan_mounted_burst(
+            self.h, _ptr(poses), poses.shape[0], C.byref(fan),
+            _ptr(self._el_table(fan, el_table)), reps, C.byref(ms)),
+            "pcp_raycast_fan_mounted_burst")
+        return ms.value
+
+    def simulate_scan_mounted_burst(self, poses6, fan: FanParams, el_table=None, reps: int = 20):
+        """pcp_simulate_scan_mounted_burst -> (fan ms per launch, resolve ms per repetition)."""
+        poses = np.ascontiguousarray(poses6, np.float64).reshape(-1, 6)
+        ms = np.zeros(2, np.float64)
+        self._check(self.lib.pcp_simulate_scan_mounted_burst(
+            self.h, _ptr(poses), poses.shape[0], C.byref(fan),
+            _ptr(self._el_table(fan, el_table)), reps, _ptr(ms)),
+            "pcp_simulate_scan_mounted_burst")
+        return float(ms[0]), float(ms[1])
 
     def scan_points(self) -> int:
         """N of pcp_simulate_scan: the input point count of the cloud the terrain index was built

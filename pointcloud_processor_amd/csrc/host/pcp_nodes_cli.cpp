@@ -13,6 +13,8 @@
 //                         greedily, then refined by single-sensor exchanges; OUT_SELECTED: the
 //                         refined set; OUT_TOTALS: start, final, then the total after each move
 //   pcp_nodes_cli scan    TERRAIN.f32 TN POSES(5 per sensor) NAZ NEL MAXD OUT_SCANS.bin
+//   pcp_nodes_cli scan_mounted TERRAIN.f32 TN POSES(6 per sensor: x,y,z,roll,pitch,yaw) NAZ NEL
+//                         MAXD ELTABLE|- OUT_SCANS.bin ... (scan's outputs; ELTABLE: NEL radians)
 //                         OUT_OFFSETS.u64 OUT_BLIND.f32 OUT_MASK.u64
 //   pcp_nodes_cli drivable IN.f32 N STEP TF(7) R1(2) R2(2) OUT.i8
 //   pcp_nodes_cli replay  TERRAIN.f32 TN CELLS.f64 NORMALS.f32 CN BBOX(6) FRAMES POINTS
@@ -318,12 +320,14 @@ static int cmd_place(Device &dev, char **a, bool exact_pair = false, bool refine
 // the simulated scans of the given sensor poses against a terrain: every sensor's returns (24-byte
 // records, the sensors' segments one after the other), the segments' offsets, the terrain's
 // blind-spot records and the per-point sensor mask
-static int cmd_scan(Device &dev, char **a) {
+// mounted: scan_mounted -- six numbers per sensor and the beam table (or "-") before the outputs
+static int cmd_scan(Device &dev, char **a, bool mounted = false) {
     const auto t = read_file(a[0]);
     const size_t tn = std::strtoull(a[1], nullptr, 10);
     const auto pv = tuple(a[2]);
-    if (pv.size() % 5 != 0) {
-        std::fprintf(stderr, "scan: POSES holds %zu numbers, not 5 per sensor\n", pv.size());
+    const size_t per = mounted ? 6 : 5;
+    if (pv.size() % per != 0) {
+        std::fprintf(stderr, "scan: POSES holds %zu numbers, not %zu per sensor\n", pv.size(), per);
         return 2;
     }
     VirtualScan::Params sp;
@@ -333,7 +337,20 @@ static int cmd_scan(Device &dev, char **a) {
     SimplifiedDualLidarOptimizer node(dev, SimplifiedDualLidarOptimizer::Params{});
     const PointCloud2 terrain = cloud_from(t, tn, 32, "map");
     node.terrainCallback(terrain);
-    std::vector<SimplifiedDualLidarOptimizer::LidarPosition> sensors(pv.size() / 5);
+    if (mounted && std::strcmp(a[6], "-") != 0) {
+        sp.el_table = tuple(a[6]);
+        if (sp.el_table.size() != (size_t)sp.n_el) {
+            std::fprintf(stderr, "scan_mounted: ELTABLE holds %zu numbers, not NEL\n",
+                         sp.el_table.size());
+            return 2;
+        }
+    }
+    if (mounted) a += 1;   // (the outputs follow the table)
+    std::vector<VirtualScan::SensorPose> mounts(mounted ? pv.size() / 6 : 0);
+    for (size_t i = 0; i < mounts.size(); ++i)
+        mounts[i] = VirtualScan::SensorPose{pv[6 * i],     pv[6 * i + 1], pv[6 * i + 2],
+                                            pv[6 * i + 3], pv[6 * i + 4], pv[6 * i + 5]};
+    std::vector<SimplifiedDualLidarOptimizer::LidarPosition> sensors(mounted ? 0 : pv.size() / 5);
     for (size_t i = 0; i < sensors.size(); ++i) {
         sensors[i].x = pv[5 * i];
         sensors[i].y = pv[5 * i + 1];
@@ -342,7 +359,7 @@ static int cmd_scan(Device &dev, char **a) {
         sensors[i].yaw = pv[5 * i + 4];
     }
     VirtualScan vs(sp);
-    const auto r = vs.scan(dev, terrain, sensors);
+    const auto r = mounted ? vs.scan_mounted(dev, terrain, mounts) : vs.scan(dev, terrain, sensors);
     if (!r.ran) {
         std::fprintf(stderr, "scan: %s\n", vs.lastError().c_str());
         return 1;
@@ -360,7 +377,7 @@ static int cmd_scan(Device &dev, char **a) {
     write_file(a[9], r.point_mask.data(), r.point_mask.size() * 8);
     std::printf("{\"n_sensors\": %zu, \"n_returns\": %llu, \"n_points\": %llu, "
                 "\"n_seen_any\": %llu, \"n_blind\": %u}\n",
-                sensors.size(), (unsigned long long)off.back(), (unsigned long long)r.n_points,
+                r.scans.size(), (unsigned long long)off.back(), (unsigned long long)r.n_points,
                 (unsigned long long)r.n_seen_any, r.blind_spots.width);
     return 0;
 }
@@ -733,7 +750,7 @@ int main(int argc, char **argv) {
         if (!hp || std::atoi(hp) != 0) setenv("HSA_ENABLE_INTERRUPT", "0", 0);
     }
     if (argc < 2) {
-        std::fprintf(stderr, "usage: pcp_nodes_cli filter|merge|vlidar|place|place_pair|place_refine|scan|area|drivable|replay ...\n");
+        std::fprintf(stderr, "usage: pcp_nodes_cli filter|merge|vlidar|place|place_pair|place_refine|scan|scan_mounted|area|drivable|replay ...\n");
         return 2;
     }
     const std::string cmd = argv[1];
@@ -744,6 +761,7 @@ int main(int argc, char **argv) {
                      : cmd == "place_pair" ? 16
                      : cmd == "place_refine" ? 16
                      : cmd == "scan"   ? 10
+                     : cmd == "scan_mounted" ? 11
                      : cmd == "area"   ? 10
                      : cmd == "drivable" ? 7
                      : cmd == "replay" ? 8
@@ -762,6 +780,7 @@ int main(int argc, char **argv) {
         if (cmd == "place_refine")
             return cmd_place(dev, argv + 2, /*exact_pair=*/false, /*refine=*/true, argc - 2);
         if (cmd == "scan") return cmd_scan(dev, argv + 2);
+        if (cmd == "scan_mounted") return cmd_scan(dev, argv + 2, /*mounted=*/true);
         if (cmd == "area") return cmd_area(dev, argv + 2);
         if (cmd == "drivable") return cmd_drivable(dev, argv + 2);
         return cmd_replay(dev, argv + 2);

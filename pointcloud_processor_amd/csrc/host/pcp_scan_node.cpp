@@ -36,9 +36,35 @@ VirtualScan::Result VirtualScan::scan(
         poses[5 * i + 3] = c.pitch;
         poses[5 * i + 4] = c.yaw;
     }
+    return run(dev, terrain, poses, n, false, frame);
+}
+
+VirtualScan::Result VirtualScan::scan_mounted(Device &dev, const PointCloud2 &terrain,
+                                              const std::vector<SensorPose> &sensors,
+                                              const std::string &frame) {
+    const size_t n = sensors.size();
+    std::vector<double> poses(6 * n);
+    for (size_t i = 0; i < n; ++i) {
+        const SensorPose &c = sensors[i];
+        const double row[6] = {c.x, c.y, c.z, c.roll, c.pitch, c.yaw};
+        std::memcpy(poses.data() + 6 * i, row, sizeof row);
+    }
+    return run(dev, terrain, poses, n, true, frame);
+}
+
+VirtualScan::Result VirtualScan::run(Device &dev, const PointCloud2 &terrain,
+                                     const std::vector<double> &poses, size_t n, bool mounted,
+                                     const std::string &frame) {
+    Result r;
+    err_.clear();
     const pcp_fan_params fan{p_.n_az, p_.n_el, p_.el_min, p_.el_max, p_.max_distance};
     if (p_.n_az <= 0 || p_.n_el <= 0 || n > PCP_SCAN_MAX_POSES) {
         err_ = "VirtualScan: bad fan size or more than PCP_SCAN_MAX_POSES sensors";
+        return r;
+    }
+    const bool table = mounted && !p_.el_table.empty();
+    if (table && p_.el_table.size() != (size_t)p_.n_el) {
+        err_ = "VirtualScan: el_table does not hold n_el entries";
         return r;
     }
     const size_t np = terrain.size();
@@ -48,9 +74,17 @@ VirtualScan::Result VirtualScan::scan(
     r.point_mask.assign(np ? np : 1, 0);
     r.seen_points.assign(n ? n : 1, 0);
     uint64_t total = 0;
-    if (pcp_simulate_scan(dev.ctx(), n ? poses.data() : nullptr, n, &fan, rec.data(), cap, &total,
-                          off.data(), nullptr, nullptr, nullptr, r.point_mask.data(), np,
-                          &r.n_points, r.seen_points.data(), &r.n_seen_any) != PCP_OK) {
+    const int rc =
+        mounted ? pcp_simulate_scan_mounted(dev.ctx(), n ? poses.data() : nullptr, n, &fan,
+                                            table ? p_.el_table.data() : nullptr, rec.data(), cap,
+                                            &total, off.data(), nullptr, nullptr, nullptr,
+                                            r.point_mask.data(), np, &r.n_points,
+                                            r.seen_points.data(), &r.n_seen_any)
+                : pcp_simulate_scan(dev.ctx(), n ? poses.data() : nullptr, n, &fan, rec.data(), cap,
+                                    &total, off.data(), nullptr, nullptr, nullptr,
+                                    r.point_mask.data(), np, &r.n_points, r.seen_points.data(),
+                                    &r.n_seen_any);
+    if (rc != PCP_OK) {
         err_ = dev.error();
         return r;
     }

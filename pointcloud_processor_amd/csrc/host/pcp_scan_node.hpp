@@ -18,6 +18,15 @@ class VirtualScan {
         double el_min = -85.0 * 3.14159265358979323846 / 180.0;
         double el_max = 85.0 * 3.14159265358979323846 / 180.0;
         double max_distance = 15.0;
+        // scan_mounted only: the rings' elevations in radians, n_el entries in any order
+        // (pcp_simulate_scan_mounted's el_table); empty: the uniform rings el_min .. el_max
+        std::vector<double> el_table;
+    };
+    // a mounted sensor (pcp_simulate_scan_mounted's poses6 row): pitch is the elevation of the
+    // boresight, negative looks down -- a tf static transform "x y z yaw pitch_tf roll" is
+    // pitch = -pitch_tf
+    struct SensorPose {
+        double x = 0.0, y = 0.0, z = 0.0, roll = 0.0, pitch = 0.0, yaw = 0.0;
     };
     struct Result {
         bool ran = false;                  // false: the call failed (lastError)
@@ -41,9 +50,15 @@ class VirtualScan {
     Result scan(Device &dev, const PointCloud2 &terrain,
                 const std::vector<SimplifiedDualLidarOptimizer::LidarPosition> &sensors,
                 const std::string &frame = "map");
+    // the same from tilted mounts, with Params::el_table's beam model: the same Result
+    Result scan_mounted(Device &dev, const PointCloud2 &terrain,
+                        const std::vector<SensorPose> &sensors, const std::string &frame = "map");
     const std::string &lastError() const { return err_; }
 
    private:
+    // poses: 5 (level) or 6 (mounted) doubles per sensor
+    Result run(Device &dev, const PointCloud2 &terrain, const std::vector<double> &poses, size_t n,
+               bool mounted, const std::string &frame);
     Params p_;
     std::string err_;
 };

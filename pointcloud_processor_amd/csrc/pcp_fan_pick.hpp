@@ -28,6 +28,7 @@ struct FanPick {
     int NPW;          // poses per wave (Xcd; 1 elsewhere)
     bool full_grid;   // the launch covers every wave of every pose: no culled interval (Skip 4)
     int block;        // threads per workgroup
+    bool mounted = false;   // the kernel's mounted form (pcp_fan_dir.hpp): Plain, full grid
 };
 
 // Poses per wave of the production launch: the largest of the request, ..., 2, 1 that divides
@@ -42,15 +43,18 @@ inline int fan_npw(int P, int request) {
 // fan_batch: PCP_FAN_BATCH (an unknown value is 0); fine / ftile: GridView.frec, .ftile; ue:
 // FanArgs.uniform_el (n_az % 64 == 0); K: the step table's length; npw_request: PCP_FAN_NPW;
 // burst: pcp_raycast_fan_burst, which times the production rule whatever the variant.
+// mounted: pcp_raycast_fan_mounted / pcp_simulate_scan_mounted (Plain only): the production rule
+// whatever the variant, always on the full grid -- a tilted ring has no one dz, so no ring
+// liveness (Skip 4) holds for it.
 inline FanPick fan_pick(FanMode mode, int fan_batch, bool fine, int ftile, bool ue, int P, int K,
-                        int npw_request, bool burst) {
+                        int npw_request, bool burst, bool mounted = false) {
     const int FN = !fine ? 0 : ftile == 2 ? 8 : ftile != 0 ? 4 : 1;
     // the diagnostic modes write a slot per wave of the pose, and the pose-major grid is 2-D
-    const bool full = mode != FanMode::Plain || fan_batch == 1;
+    const bool full = mode != FanMode::Plain || fan_batch == 1 || mounted;
     const FanPick interleaved{fine ? FanFamily::Fine : FanFamily::Coarse, mode, FN, fine && ue, 1,
-                              full, 64};
+                              full, 64, mounted};
     if (mode != FanMode::Plain) return interleaved;
-    if (!burst) {
+    if (!burst && !mounted) {
         if (fan_batch == 1) return FanPick{FanFamily::PoseMajor, mode, 0, false, 1, true, 128};
         if (fan_batch == 2) return FanPick{FanFamily::OccBit, mode, 0, false, 1, false, 64};
         if (fan_batch == 4) return interleaved;
@@ -59,7 +63,7 @@ inline FanPick fan_pick(FanMode mode, int fan_batch, bool fine, int ftile, bool 
     // 0.63 ms on C2; several poses per wave over the tiled fine copies only
     if (fine && ue && P % 8 == 0 && K <= kStepLds)
         return FanPick{FanFamily::Xcd, mode, FN, true, ftile != 0 ? fan_npw(P, npw_request) : 1,
-                       full, 64};
+                       full, 64, mounted};
     return interleaved;
 }
 

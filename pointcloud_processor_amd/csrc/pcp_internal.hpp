@@ -414,6 +414,8 @@ struct pcp_ctx {
                                              // sizes stored by the kernels (one round trip)
     int32_t fan_naz = -1, fan_nel = -1;      // cached fan direction tables
     double fan_elmin = 0.0, fan_elmax = 0.0;
+    std::vector<double> fan_el_h;            // the beam table they were built from (a mounted
+                                             // query's el_table); empty: the uniform formula
     double steps_end = -1e300;               // cached step table
     int steps_K = 0;
     double steps_first = 0.0, steps_last = 0.0;   // its first and last entries (steps_K > 0)
@@ -569,6 +571,10 @@ struct FanEnq {
     const uint2 *wave_part = nullptr;
     uint32_t waves = 0, wave0 = 0, live_waves = 0;
     int K = 0;
+    // doubles per staged pose row: 8, or kFanDirRow of a mounted query (pcp_fan_dir.hpp); the
+    // pinned results start behind the rows
+    uint32_t pose_row = 8;
+    bool mounted = false;
 };
 struct FanOpts {
     bool want_fh = false;         // first hits [n][rays] to o.fh_d
@@ -580,12 +586,20 @@ struct FanOpts {
     // landing block (ctx->fan_host past the staged poses) instead of device memory; o.*_d stay
     // null
     bool host_out = false;
+    // the mounted query (pcp_raycast_fan_mounted): `poses5` holds poses6 rows (x, y, z, roll,
+    // pitch, yaw), the rays are pcp_fan_dir.hpp's, the launch covers the full grid; el_table
+    // (nullable, [n_el] radians, finite: the caller checked): the rings' elevations
+    bool mounted = false;
+    const double *el_table = nullptr;
 };
 // mode: the plain query, or a diagnostic launch -- Stats: the march's four counters summed to
 // o.stats_d[0..3]; Stamps: four clock stamps per (pose, wave) at o.stats_d, o.stats_bytes long.
 // Which kernel runs on which grid is fan_pick()'s answer (pcp_fan_pick.hpp).
 int fan_enqueue(pcp_ctx *ctx, const double *poses5, uint64_t n, const pcp_fan_params *fan,
                 FanEnq &o, FanMode mode = FanMode::Plain, const FanOpts &opt = FanOpts{});
+// a mounted query's beam table (nullable): PCP_E_INVALID for a non-finite entry
+int fan_el_table_check(pcp_ctx *ctx, const char *what, const pcp_fan_params *fan,
+                       const double *el_table);
 
 // runOptimization's scoring up to the per-pose sums, enqueued on ctx->stream (pcp_vlidar.hip)
 struct ScoreEnq {

@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <cstring>
 
+#include "pcp_fan_dir.hpp"
 #include "pcp_internal.hpp"
 #include "pcp_stencil.hpp"
 
@@ -31,6 +32,7 @@ struct ResolveArgs {
     GridView g;
     const double *ca, *sa, *ce, *se;
     const double *pose;                  // P x 8: x, y, z, pitch, yaw, cos(yaw), sin(yaw), pad
+                                         // (MT: P x kFanDirRow, pcp_fan_dir.hpp's rows)
     const double *steps;
     int n_az;
     uint32_t rays, waves, P;
@@ -86,6 +88,8 @@ k_scan_prepare(const uint2 *__restrict__ part, uint32_t nW, uint32_t waves, uint
 // rebuilds the march's query point of its first blocked sample, walks the eight cell runs of its
 // stencil in the cell-major copy (descending z per run: a point r below q ends the run) and
 // keeps the (acc, input index) minimum over the points within r.
+// MT: a mounted query -- the direction is the mounted march's own fan_dir() (pcp_fan_dir.hpp).
+template <bool MT>
 __global__ void __launch_bounds__(kST) k_scan_resolve(ResolveArgs a) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t gw = blockIdx.x * kSW + (threadIdx.x >> 6);
@@ -113,11 +117,20 @@ __global__ void __launch_bounds__(kST) k_scan_resolve(ResolveArgs a) {
     const uint32_t j = ray / (uint32_t)a.n_az, i = ray - j * (uint32_t)a.n_az;
     const double cej = a.ce[j];
     const double lx = cej * a.ca[i], ly = cej * a.sa[i], lz = a.se[j];
-    const double *Pq = a.pose + 8 * (size_t)p;
-    const double px = Pq[0], py = Pq[1], pz = Pq[2], cy = Pq[5], sy = Pq[6];
-    const double dx = cy * lx - sy * ly;
-    const double dy = sy * lx + cy * ly;
-    const double dz = lz;
+    const double *Pq = a.pose + (MT ? kFanDirRow : 8) * (size_t)p;
+    const double px = Pq[0], py = Pq[1], pz = Pq[2];
+    double dx, dy, dz;
+    if (MT) {
+        const FanDir d = fan_dir(Pq, lx, ly, lz);
+        dx = d.x;
+        dy = d.y;
+        dz = d.z;
+    } else {
+        const double cy = Pq[5], sy = Pq[6];
+        dx = cy * lx - sy * ly;
+        dy = sy * lx + cy * ly;
+        dz = lz;
+    }
     const double s = a.steps[k];
     const float qx = (float)(px + dx * s);
     const float qy = (float)(py + dy * s);
@@ -323,7 +336,8 @@ int resolve_enqueue(pcp_ctx *ctx, const ScanPlan &s, const pcp_fan_params *fan, 
     a.range_img = s.dense_rg ? reinterpret_cast<float *>(blk + s.rg_off) : nullptr;
     a.mask = mask;
     a.n_mask = s.mask ? s.N : 0;
-    hipLaunchKernelGGL(k_scan_resolve, dim3((nW + kSW - 1) / kSW), dim3(kST), 0, st, a);
+    hipLaunchKernelGGL(o.mounted ? k_scan_resolve<true> : k_scan_resolve<false>,
+                       dim3((nW + kSW - 1) / kSW), dim3(kST), 0, st, a);
     PCP_CHECK_LAUNCH(ctx);
     if (mask) {
         const unsigned g = (unsigned)std::min<uint64_t>((s.N / 2 + kST) / kST, 1024);
@@ -351,16 +365,19 @@ int check_args(pcp_ctx *ctx, const char *what, const double *poses5, uint64_t n,
 
 using namespace pcp;
 
-extern "C" int pcp_simulate_scan(pcp_ctx *ctx, const double *poses5, uint64_t n,
-                                 const pcp_fan_params *fan, pcp_scan_return *returns,
-                                 uint64_t returns_cap, uint64_t *n_returns, uint64_t *offsets,
-                                 int32_t *hit_point, float *range_img, int16_t *first_hit,
-                                 uint64_t *point_mask, uint64_t mask_cap, uint64_t *n_points,
-                                 uint32_t *seen_points, uint64_t *n_seen_any) {
+// pcp_simulate_scan and, mounted (poses5: poses6 rows, el_table nullable), its mounted twin
+static int simulate_scan_impl(pcp_ctx *ctx, const double *poses5, uint64_t n,
+                              const pcp_fan_params *fan, bool mounted, const double *el_table,
+                              pcp_scan_return *returns,
+                              uint64_t returns_cap, uint64_t *n_returns, uint64_t *offsets,
+                              int32_t *hit_point, float *range_img, int16_t *first_hit,
+                              uint64_t *point_mask, uint64_t mask_cap, uint64_t *n_points,
+                              uint32_t *seen_points, uint64_t *n_seen_any) {
     if (!ctx) return PCP_E_INVALID;
     if (!n_returns || !offsets)
         return set_err(ctx, PCP_E_INVALID, "pcp_simulate_scan: null argument");
     if (int rc = check_args(ctx, "pcp_simulate_scan", poses5, n, fan)) return rc;
+    if (int rc = fan_el_table_check(ctx, "pcp_simulate_scan_mounted", fan, el_table)) return rc;
     const uint64_t N = ctx->terrain.present ? ctx->terrain_index_n : 0;
     if (!returns) returns_cap = 0;
     if (n == 0) {
@@ -379,8 +396,10 @@ extern "C" int pcp_simulate_scan(pcp_ctx *ctx, const double *poses5, uint64_t n,
     // the production fan query: first hits, per-wave partials and per-pose blocked counts stay
     // on the device (a step table past PCP_MAX_STEPS is refused in there, before any launch)
     FanEnq o;
-    if (int rc = fan_enqueue(ctx, poses5, n, fan, o, FanMode::Plain, FanOpts{/*want_fh=*/true}))
-        return rc;
+    FanOpts fo{/*want_fh=*/true};
+    fo.mounted = mounted;
+    fo.el_table = el_table;
+    if (int rc = fan_enqueue(ctx, poses5, n, fan, o, FanMode::Plain, fo)) return rc;
     hipStream_t st = ctx->stream;
     const uint32_t P = (uint32_t)n;
     const bool want_mask = point_mask || seen_points || n_seen_any;
@@ -453,19 +472,46 @@ extern "C" int pcp_simulate_scan(pcp_ctx *ctx, const double *poses5, uint64_t n,
     return rc;
 }
 
-extern "C" int pcp_simulate_scan_burst(pcp_ctx *ctx, const double *poses5, uint64_t n,
-                                       const pcp_fan_params *fan, int reps, double ms[2]) {
+extern "C" int pcp_simulate_scan(pcp_ctx *ctx, const double *poses5, uint64_t n,
+                                 const pcp_fan_params *fan, pcp_scan_return *returns,
+                                 uint64_t returns_cap, uint64_t *n_returns, uint64_t *offsets,
+                                 int32_t *hit_point, float *range_img, int16_t *first_hit,
+                                 uint64_t *point_mask, uint64_t mask_cap, uint64_t *n_points,
+                                 uint32_t *seen_points, uint64_t *n_seen_any) {
+    return simulate_scan_impl(ctx, poses5, n, fan, false, nullptr, returns, returns_cap, n_returns,
+                              offsets, hit_point, range_img, first_hit, point_mask, mask_cap,
+                              n_points, seen_points, n_seen_any);
+}
+
+extern "C" int pcp_simulate_scan_mounted(pcp_ctx *ctx, const double *poses6, uint64_t n,
+                                         const pcp_fan_params *fan, const double *el_table,
+                                         pcp_scan_return *returns, uint64_t returns_cap,
+                                         uint64_t *n_returns, uint64_t *offsets,
+                                         int32_t *hit_point, float *range_img,
+                                         int16_t *first_hit, uint64_t *point_mask,
+                                         uint64_t mask_cap, uint64_t *n_points,
+                                         uint32_t *seen_points, uint64_t *n_seen_any) {
+    return simulate_scan_impl(ctx, poses6, n, fan, true, el_table, returns, returns_cap, n_returns,
+                              offsets, hit_point, range_img, first_hit, point_mask, mask_cap,
+                              n_points, seen_points, n_seen_any);
+}
+
+static int simulate_scan_burst_impl(pcp_ctx *ctx, const double *poses5, uint64_t n,
+                                    const pcp_fan_params *fan, bool mounted,
+                                    const double *el_table, int reps, double ms[2]) {
     if (!ctx) return PCP_E_INVALID;
     if (!ms || reps <= 0 || n == 0)
         return set_err(ctx, PCP_E_INVALID, "pcp_simulate_scan_burst: null argument or nothing to time");
     if (int rc = check_args(ctx, "pcp_simulate_scan_burst", poses5, n, fan)) return rc;
+    if (int rc = fan_el_table_check(ctx, "pcp_simulate_scan_mounted_burst", fan, el_table)) return rc;
     ms[0] = ms[1] = 0.0;
     // the fan kernel `reps` times between two events (first hits and partials written by each),
     // then the resolve phase `reps` times between two events
     FanEnq o;
-    if (int rc = fan_enqueue(ctx, poses5, n, fan, o, FanMode::Plain,
-                             FanOpts{/*want_fh=*/true, /*burst=*/reps, /*burst_ms=*/&ms[0]}))
-        return rc;
+    FanOpts fo{/*want_fh=*/true, /*burst=*/reps, /*burst_ms=*/&ms[0]};
+    fo.mounted = mounted;
+    fo.el_table = el_table;
+    if (int rc = fan_enqueue(ctx, poses5, n, fan, o, FanMode::Plain, fo)) return rc;
     hipStream_t st = ctx->stream;
     const uint64_t N = ctx->terrain.present ? ctx->terrain_index_n : 0;
     const ScanPlan s = make_plan((uint32_t)n, o.rays, o.waves, N, (uint64_t)n * o.rays, false,
@@ -488,4 +534,15 @@ extern "C" int pcp_simulate_scan_burst(pcp_ctx *ctx, const double *poses5, uint6
     ms[1] = (double)t / reps;
     prof_resolve(ctx);
     return PCP_OK;
+}
+
+extern "C" int pcp_simulate_scan_burst(pcp_ctx *ctx, const double *poses5, uint64_t n,
+                                       const pcp_fan_params *fan, int reps, double ms[2]) {
+    return simulate_scan_burst_impl(ctx, poses5, n, fan, false, nullptr, reps, ms);
+}
+
+extern "C" int pcp_simulate_scan_mounted_burst(pcp_ctx *ctx, const double *poses6, uint64_t n,
+                                               const pcp_fan_params *fan, const double *el_table,
+                                               int reps, double ms[2]) {
+    return simulate_scan_burst_impl(ctx, poses6, n, fan, true, el_table, reps, ms);
 }

@@ -18,6 +18,7 @@
 #include "pcp_fan_clear.hpp"
 #include "pcp_fan_clip.hpp"
 #include "pcp_fan_cull.hpp"
+#include "pcp_fan_dir.hpp"
 #include "pcp_internal.hpp"
 #include "pcp_stencil.hpp"
 
@@ -1349,7 +1350,8 @@ struct FanArgs {
     GridView g;
     const double *ca, *sa, *ce, *se;
     const double *pose;    // P x 8: x, y, z, pitch, yaw, cos(yaw), sin(yaw), and as two uint32
-                           // the pose's live rings [j0, j1) (pcp_fan_cull.hpp)
+                           // the pose's live rings [j0, j1) (pcp_fan_cull.hpp); the mounted
+                           // kernels: P x kFanDirRow, the rows of pcp_fan_dir.hpp
     const double *steps;
     int K;
     int n_az;
@@ -1394,9 +1396,15 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
 // termination on near-flat terrain).  Each wave writes its blocked-ray count and its
 // sample-query count to its own slot: the per-pose sums are formed by k_fan_reduce in a fixed
 // order (deterministic, no same-address atomics).
+// MT: the mounted form (pcp_raycast_fan_mounted, Plain only).  The pose rows are pcp_fan_dir.hpp's
+// and the direction is its fan_dir() -- roll, pitch and yaw per pose on the wave's shared local
+// direction; a tilted ring has no one dz, so there is no ring liveness (Skip 4) and the launch
+// covers the full grid.
 template <int MODE, int BS, bool ZB = true, int FN = 0, bool UE = false, int NPW = 1,
-          bool SL = false>
+          bool SL = false, bool MT = false>
 __device__ __forceinline__ void fan_body(const FanArgs &a, uint32_t p0, uint32_t rblock) {
+    static_assert(!MT || MODE == FAN_PLAIN, "the mounted march has no diagnostic modes");
+    constexpr int PR = MT ? kFanDirRow : 8;   // doubles per pose row
     const uint32_t ray = rblock * BS + threadIdx.x;
     const uint32_t wid = ray >> 6;
     const bool active = ray < a.rays;
@@ -1411,10 +1419,10 @@ __device__ __forceinline__ void fan_body(const FanArgs &a, uint32_t p0, uint32_t
     // pose's values and its live rings are then LDS broadcasts, not a round trip through
     // vector memory at the top of every pose
     __shared__ double s_steps[SL ? kStepLds : 1];
-    __shared__ double s_pose[SL ? 8 * NPW : 1];
+    __shared__ double s_pose[SL ? PR * NPW : 1];
     if (SL) {
         for (int q = threadIdx.x; q < a.K; q += BS) s_steps[q] = a.steps[q];
-        for (int q = threadIdx.x; q < 8 * NPW; q += BS) s_pose[q] = a.pose[8 * (size_t)p0 + q];
+        for (int q = threadIdx.x; q < PR * NPW; q += BS) s_pose[q] = a.pose[PR * (size_t)p0 + q];
         __syncthreads();
     }
     const double *steps = SL ? s_steps : a.steps;
@@ -1444,9 +1452,14 @@ __device__ __forceinline__ void fan_body(const FanArgs &a, uint32_t p0, uint32_t
     // Skip 4, per pose: a ring outside the pose's live interval has every sample of every ray
     // outside the clip box -- no rotation, no clip, no reductions (a uniform test: the ring
     // and the pose's interval are scalars)
-    const double *P = SL ? s_pose + 8 * q : a.pose + 8 * (size_t)p;
+    const double *P = SL ? s_pose + PR * q : a.pose + PR * (size_t)p;
     bool dead = false;
-    if (UE) {
+    FanDir md{0.0, 0.0, 0.0};
+    // (a per-wave early-out -- every lane's two end heights against the clip box with the ring
+    // test's arithmetic, the march skipped on a full ballot -- measured no gain over the clip's
+    // own immediate return: 0.0557 vs 0.0555 ms at zero tilt, profiles/mount_early_out_ab.json)
+    if (MT) md = fan_dir(P, lx, ly, lz);
+    if (UE && !MT) {
         const uint2 lr = *reinterpret_cast<const uint2 *>(P + 7);
         const uint32_t j0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)lr.x);
         const uint32_t j1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)lr.y);
@@ -1454,10 +1467,10 @@ __device__ __forceinline__ void fan_body(const FanArgs &a, uint32_t p0, uint32_t
         if (MODE == FAN_STAMPS && dead) t1 = t0;
     }
     if (!dead && active && a.present) {
-        const double cy = P[5], sy = P[6];
-        const double dx = cy * lx - sy * ly;
-        const double dy = sy * lx + cy * ly;
-        const double dz = lz;
+        const double cy = MT ? 0.0 : P[5], sy = MT ? 0.0 : P[6];
+        const double dx = MT ? md.x : cy * lx - sy * ly;
+        const double dy = MT ? md.y : sy * lx + cy * ly;
+        const double dz = MT ? md.z : lz;
         if (MODE == FAN_STAMPS) {
             asm volatile("" ::"v"(dx), "v"(dy));
             t1 = __builtin_amdgcn_s_memtime();
@@ -1471,7 +1484,7 @@ __device__ __forceinline__ void fan_body(const FanArgs &a, uint32_t p0, uint32_t
     }
     if (active && a.first_hit) a.first_hit[(size_t)p * a.rays + ray] = (int16_t)hit;
     uint2 part;
-    if (UE && dead) {   // (UE: every wave is full)
+    if (UE && !MT && dead) {   // (UE: every wave is full)
         part = make_uint2(0u, 64u * (uint32_t)a.K);
     } else {
         const uint64_t bal = __ballot(active && hit >= 0);
@@ -1508,10 +1521,11 @@ __device__ __forceinline__ void fan_body(const FanArgs &a, uint32_t p0, uint32_t
 // the rest of a workgroup), 1-D grid interleaving the poses (block b = ray block b / P of pose
 // b % P: the waves in flight at any time march the same ring of many poses), capped at 7 waves
 // per SIMD (94 SGPRs; the compiler's own choice, 106, admits only 6).
-template <int MODE, int BS = 64, bool ZB = true, int W = 7, int FN = 0, bool UE = false>
+template <int MODE, int BS = 64, bool ZB = true, int W = 7, int FN = 0, bool UE = false,
+          bool MT = false>
 __global__ void __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(W, W)))
 k_raycast_fan(FanArgs a, uint32_t P) {
-    fan_body<MODE, BS, ZB, FN, UE>(a, blockIdx.x % P, a.w0 + blockIdx.x / P);
+    fan_body<MODE, BS, ZB, FN, UE, 1, false, MT>(a, blockIdx.x % P, a.w0 + blockIdx.x / P);
 }
 
 // A/B: XCD-chunked placement (P % 8 == 0): workgroup b runs on XCD b % 8, which takes the
@@ -1522,12 +1536,13 @@ k_raycast_fan(FanArgs a, uint32_t P) {
 // a.rev: the launch's last wave first.  Workgroups are dispatched in index order and the rings
 // just below the horizon march 2-3 times as long as the steep ones: dispatched last they would
 // be the launch's tail
-template <int MODE, int BS = 64, bool ZB = true, int W = 8, int FN = 1, bool UE = true, int NPW = 1>
+template <int MODE, int BS = 64, bool ZB = true, int W = 8, int FN = 1, bool UE = true, int NPW = 1,
+          bool MT = false>
 __global__ void __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(W, W)))
 k_raycast_fan_xcd(FanArgs a, uint32_t P) {
     const uint32_t pc = P >> 3, gpc = pc / NPW, j = blockIdx.x >> 3;
     const uint32_t b = j / gpc;
-    fan_body<MODE, BS, ZB, FN, UE, NPW, true>(a, (blockIdx.x & 7u) * pc + (j % gpc) * NPW,
+    fan_body<MODE, BS, ZB, FN, UE, NPW, true, MT>(a, (blockIdx.x & 7u) * pc + (j % gpc) * NPW,
                                              a.w0 + (a.rev ? a.lw - 1u - b : b));
 }
 
@@ -1630,6 +1645,19 @@ constexpr FanKernel kFanXcd[3][6] = {
     {kXcd<1, 1>},   // (the untiled copy: one pose per wave only)
     {kXcd<4, 1>, kXcd<4, 2>, kXcd<4, 4>, kXcd<4, 8>, kXcd<4, 16>, kXcd<4, 32>},
     {kXcd<8, 1>, kXcd<8, 2>, kXcd<8, 4>, kXcd<8, 8>, kXcd<8, 16>, kXcd<8, 32>}};
+// the mounted forms (Plain only): the same two tables
+template <int FN, bool UE>
+constexpr FanKernel kFineMt = k_raycast_fan<FAN_PLAIN, 64, true, 8, FN, UE, true>;
+constexpr FanRows kFanInterleavedMt = {{{k_raycast_fan<FAN_PLAIN, 64, true, 7, 0, false, true>},
+                                        {kFineMt<1, false>, kFineMt<1, true>},
+                                        {kFineMt<4, false>, kFineMt<4, true>},
+                                        {kFineMt<8, false>, kFineMt<8, true>}}};
+template <int FN, int NPW>
+constexpr FanKernel kXcdMt = k_raycast_fan_xcd<FAN_PLAIN, 64, true, 8, FN, true, NPW, true>;
+constexpr FanKernel kFanXcdMt[3][6] = {
+    {kXcdMt<1, 1>},
+    {kXcdMt<4, 1>, kXcdMt<4, 2>, kXcdMt<4, 4>, kXcdMt<4, 8>, kXcdMt<4, 16>, kXcdMt<4, 32>},
+    {kXcdMt<8, 1>, kXcdMt<8, 2>, kXcdMt<8, 4>, kXcdMt<8, 8>, kXcdMt<8, 16>, kXcdMt<8, 32>}};
 
 // The one fan launch, and its error.  ev0 / ev1: hipExtLaunchKernelGGL's start / stop events
 // (null: none).  A pick without an instantiated kernel is an error.
@@ -1639,12 +1667,19 @@ static hipError_t fan_launch(const FanPick &k, FanGrid g, hipStream_t st, hipEve
     FanKernel f = nullptr;
     switch (k.family) {
     case FanFamily::Coarse:
-    case FanFamily::Fine: f = kFanInterleaved[(int)k.mode].k[fn][k.UE ? 1 : 0]; break;
-    case FanFamily::Xcd:   // (FAN_PLAIN only, over a fine copy)
-        f = fn > 0 && k.mode == FanMode::Plain ? kFanXcd[fn - 1][__builtin_ctz(k.NPW)] : nullptr;
+    case FanFamily::Fine:
+        if (k.mounted)
+            f = k.mode == FanMode::Plain ? kFanInterleavedMt.k[fn][k.UE ? 1 : 0] : nullptr;
+        else
+            f = kFanInterleaved[(int)k.mode].k[fn][k.UE ? 1 : 0];
         break;
-    case FanFamily::PoseMajor: f = k_raycast_fan_pm<128, true>; break;
-    case FanFamily::OccBit: f = k_raycast_fan<FAN_PLAIN, 64, false>; break;
+    case FanFamily::Xcd:   // (FAN_PLAIN only, over a fine copy)
+        f = fn > 0 && k.mode == FanMode::Plain
+                ? (k.mounted ? kFanXcdMt : kFanXcd)[fn - 1][__builtin_ctz(k.NPW)]
+                : nullptr;
+        break;
+    case FanFamily::PoseMajor: f = k.mounted ? nullptr : k_raycast_fan_pm<128, true>; break;
+    case FanFamily::OccBit: f = k.mounted ? nullptr : k_raycast_fan<FAN_PLAIN, 64, false>; break;
     }
     if (!f) return hipErrorInvalidDeviceFunction;
     hipExtLaunchKernelGGL(f, dim3(g.x, g.y), dim3((uint32_t)k.block), 0, st, ev0, ev1, 0, a, P);
@@ -2247,6 +2282,16 @@ int pcp_generate_and_score(pcp_ctx *ctx, const double bb[6], const pcp_vl_params
 }  // extern "C"
 
 namespace pcp {
+// a mounted query's beam table: every entry finite (fan: checked non-null by the caller)
+int fan_el_table_check(pcp_ctx *ctx, const char *what, const pcp_fan_params *fan,
+                       const double *el_table) {
+    if (!el_table) return PCP_OK;
+    for (int32_t j = 0; j < fan->n_el; ++j)
+        if (!std::isfinite(el_table[j]))
+            return set_err(ctx, PCP_E_INVALID, "%s: el_table[%d] is not finite", what, (int)j);
+    return PCP_OK;
+}
+
 // Everything of a fan query up to the per-pose sums, enqueued on ctx->stream (no host sync
 // unless the fan tables or the step table change): poses uploaded through the pinned block,
 // the march, k_fan_reduce.  On return o.blocked_d / o.units_d (and o.fh_d when opt.want_fh) are
@@ -2263,11 +2308,27 @@ int fan_enqueue(pcp_ctx *ctx, const double *poses5, uint64_t n, const pcp_fan_pa
     const uint32_t rays = (uint32_t)fan->n_az * (uint32_t)fan->n_el;
     // direction tables (host libm, identical to the oracle), cached per fan shape
     const size_t tab_doubles = 2 * (size_t)fan->n_az + 2 * (size_t)fan->n_el;
-    if (ctx->fan_naz != fan->n_az || ctx->fan_nel != fan->n_el || ctx->fan_elmin != fan->el_min ||
-        ctx->fan_elmax != fan->el_max) {
+    // (a beam table is part of the key: the cache holds the table it was built from, or none, so
+    // a level call after a mounted one of the same shape rebuilds the uniform rings, and another
+    // table its own)
+    const double *elt = opt.mounted ? opt.el_table : nullptr;
+    const bool same_rings =
+        elt ? ctx->fan_el_h.size() == (size_t)fan->n_el &&
+                  std::memcmp(ctx->fan_el_h.data(), elt, (size_t)fan->n_el * sizeof(double)) == 0
+            : ctx->fan_el_h.empty() && ctx->fan_elmin == fan->el_min &&
+                  ctx->fan_elmax == fan->el_max;
+    if (ctx->fan_naz != fan->n_az || ctx->fan_nel != fan->n_el || !same_rings) {
         std::vector<double> t(tab_doubles);
         fan_tables(fan->n_az, fan->n_el, fan->el_min, fan->el_max, t.data(), t.data() + fan->n_az,
                    t.data() + 2 * fan->n_az, t.data() + 2 * fan->n_az + fan->n_el);
+        if (elt)
+            for (int32_t j = 0; j < fan->n_el; ++j) {
+                t[2 * (size_t)fan->n_az + j] = std::cos(elt[j]);
+                t[2 * (size_t)fan->n_az + fan->n_el + j] = std::sin(elt[j]);
+            }
+        ctx->fan_naz = -1;   // (no valid key while the upload can still fail)
+        if (elt) ctx->fan_el_h.assign(elt, elt + fan->n_el);
+        else ctx->fan_el_h.clear();
         PCP_HIP(ctx, ctx->fan_tab.ensure(tab_doubles * sizeof(double)));
         PCP_HIP(ctx, hipMemcpyAsync(ctx->fan_tab.p, t.data(), tab_doubles * sizeof(double),
                                     hipMemcpyHostToDevice, st));
@@ -2286,10 +2347,12 @@ int fan_enqueue(pcp_ctx *ctx, const double *poses5, uint64_t n, const pcp_fan_pa
     // regrown) by this query, whichever entry point enqueues it
     if (ctx->keys_pending) PCP_HIP(ctx, hipEventSynchronize(ctx->keys_ev));
     ctx->keys_pending = false;
-    // pinned staging: poses in (P x 8 doubles), then {units u64[P], blocked u32[P]} out
-    PCP_HIP(ctx, ctx->fan_host.ensure((size_t)P * (8 * sizeof(double) + 12) + 64));
+    // pinned staging: poses in (P x 8 doubles; a mounted query: P x kFanDirRow), then {units
+    // u64[P], blocked u32[P]} out
+    const size_t row = opt.mounted ? (size_t)kFanDirRow : 8;
+    PCP_HIP(ctx, ctx->fan_host.ensure((size_t)P * (row * sizeof(double) + 12) + 64));
     double *pose8 = ctx->fan_host.as<double>();
-    for (int k = 0; k < P; ++k) {
+    for (int k = 0; k < P && !opt.mounted; ++k) {
         const double *s = poses5 + 5 * (size_t)k;
         double *d = pose8 + 8 * (size_t)k;
         for (int q = 0; q < 5; ++q) d[q] = s[q];
@@ -2297,7 +2360,9 @@ int fan_enqueue(pcp_ctx *ctx, const double *poses5, uint64_t n, const pcp_fan_pa
         d[6] = std::sin(s[4]);
         d[7] = 0.0;
     }
-    PCP_HIP(ctx, ctx->poses_d.ensure((size_t)P * 8 * sizeof(double)));
+    for (int k = 0; k < P && opt.mounted; ++k)   // (poses6 rows)
+        fan_dir_row(poses5 + 6 * (size_t)k, pose8 + row * (size_t)k);
+    PCP_HIP(ctx, ctx->poses_d.ensure((size_t)P * row * sizeof(double)));
     const uint32_t waves = (rays + 63) / 64;
     if ((uint64_t)waves * (uint64_t)P >= (1ull << 31))
         return set_err(ctx, PCP_E_INVALID, "pcp_raycast_fan: %d poses x %u rays exceed one launch",
@@ -2314,12 +2379,14 @@ int fan_enqueue(pcp_ctx *ctx, const double *poses5, uint64_t n, const pcp_fan_pa
     a.uniform_el = (fan->n_az % 64 == 0) ? 1 : 0;
     // the kernel and whether it runs on the full grid: asked once, here (pcp_fan_pick.hpp)
     const FanPick pick = fan_pick(mode, ctx->fan_batch, a.g.frec != nullptr, a.g.ftile,
-                                  a.uniform_el != 0, P, K, ctx->fan_npw, opt.burst > 0);
+                                  a.uniform_el != 0, P, K, ctx->fan_npw, opt.burst > 0, opt.mounted);
+    if (opt.mounted && mode != FanMode::Plain)
+        return set_err(ctx, PCP_E_INVALID, "pcp_raycast_fan_mounted: no diagnostic modes");
     // Skip 4: each pose's live rings [j0, j1) into its eighth slot (the UE
     // kernels leave a pose's dead rings at once), and the waves that hold a live ring of some
     // pose: only those are launched, unless the pick needs the full grid.
     uint32_t w0 = 0, lw = waves;
-    {
+    if (!opt.mounted) {   // (a mounted row has no live-ring slot: its kernels cover every ring)
         uint32_t *lr = reinterpret_cast<uint32_t *>(pose8 + 7);
         const bool rule = ctx->fan_cull && ctx->terrain.present && K > 0;
         if (rule) {
@@ -2346,12 +2413,12 @@ int fan_enqueue(pcp_ctx *ctx, const double *poses5, uint64_t n, const pcp_fan_pa
         : mode == FanMode::Stats ? ((size_t)P * waves * 4 + 4) * sizeof(uint64_t)
                                  : 64 * sizeof(uint64_t);
     PCP_HIP(ctx, ctx->stats_d.ensure(stats_bytes));
-    if (int rc0 = copy_pinned_async(ctx, ctx->poses_d.p, pose8, (size_t)P * 8 * sizeof(double), st))
+    if (int rc0 = copy_pinned_async(ctx, ctx->poses_d.p, pose8, (size_t)P * row * sizeof(double), st))
         return rc0;
     // results land in device memory, or (host_out) straight in the pinned block behind the
     // staged poses: one copy and its dispatch fewer per query
     unsigned long long *units_d =
-        opt.host_out ? reinterpret_cast<unsigned long long *>(pose8 + 8 * (size_t)P)
+        opt.host_out ? reinterpret_cast<unsigned long long *>(pose8 + row * (size_t)P)
                      : ctx->out_c.as<unsigned long long>();
     uint32_t *blocked_d = reinterpret_cast<uint32_t *>(units_d + P);
     int16_t *fh_d = nullptr;
@@ -2438,6 +2505,8 @@ int fan_enqueue(pcp_ctx *ctx, const double *poses5, uint64_t n, const pcp_fan_pa
     o.wave0 = w0;
     o.live_waves = lw;
     o.K = K;
+    o.pose_row = (uint32_t)row;
+    o.mounted = opt.mounted;
     return PCP_OK;
 }
 }  // namespace pcp
@@ -2448,10 +2517,12 @@ static int raycast_fan_impl(pcp_ctx *ctx, const double *poses5, uint64_t n,
                             const pcp_fan_params *fan, uint32_t *blocked, uint64_t *units,
                             int16_t *first_hit, int64_t *best_idx,
                             FanMode mode = FanMode::Plain, uint64_t *diag = nullptr,
-                            int burst = 0, double *burst_ms = nullptr) {
+                            int burst = 0, double *burst_ms = nullptr, bool mounted = false,
+                            const double *el_table = nullptr) {
     if (!ctx) return PCP_E_INVALID;
     if (!fan || (n && (!poses5 || !blocked)))
         return set_err(ctx, PCP_E_INVALID, "pcp_raycast_fan: null argument");
+    if (int rc = fan_el_table_check(ctx, "pcp_raycast_fan_mounted", fan, el_table)) return rc;
     if (best_idx) *best_idx = -1;
     if (n == 0) {
         if (fan->n_az <= 0 || fan->n_el <= 0 || (int64_t)fan->n_az * fan->n_el > (1ll << 30))
@@ -2462,7 +2533,8 @@ static int raycast_fan_impl(pcp_ctx *ctx, const double *poses5, uint64_t n,
     FanEnq o;   // (the kernel and its poses per wave: pcp_fan_pick.hpp, mirrored by bench._fan_npw)
     const bool host_out = ctx->fan_host_out;
     if (int rc = fan_enqueue(ctx, poses5, n, fan, o, mode,
-                             FanOpts{first_hit != nullptr, burst, burst_ms, host_out}))
+                             FanOpts{first_hit != nullptr, burst, burst_ms, host_out, mounted,
+                                     el_table}))
         return rc;
     hipStream_t st = ctx->stream;
     const int P = (int)n;
@@ -2473,7 +2545,7 @@ static int raycast_fan_impl(pcp_ctx *ctx, const double *poses5, uint64_t n,
                                     hipMemcpyDeviceToHost, st));
     // units and blocked are adjacent on the device: one copy into the pinned block
     double *pose8 = ctx->fan_host.as<double>();
-    uint64_t *u_h = reinterpret_cast<uint64_t *>(pose8 + 8 * (size_t)P);
+    uint64_t *u_h = reinterpret_cast<uint64_t *>(pose8 + (size_t)o.pose_row * (size_t)P);
     const uint32_t *b_h = reinterpret_cast<const uint32_t *>(u_h + P);
     if (!host_out)   // else k_fan_reduce stored them into u_h / b_h itself
         PCP_HIP(ctx, hipMemcpyAsync(u_h, o.units_d, (size_t)P * 12, hipMemcpyDeviceToHost, st));
@@ -2515,6 +2587,23 @@ int pcp_raycast_fan_burst(pcp_ctx *ctx, const double *poses5, uint64_t n,
     *ms_per_launch = 0.0;
     return raycast_fan_impl(ctx, poses5, n, fan, blocked.data(), nullptr, nullptr, nullptr,
                             FanMode::Plain, nullptr, reps, ms_per_launch);
+}
+
+int pcp_raycast_fan_mounted(pcp_ctx *ctx, const double *poses6, uint64_t n,
+                            const pcp_fan_params *fan, const double *el_table, uint32_t *blocked,
+                            uint64_t *units, int16_t *first_hit, int64_t *best_idx) {
+    return raycast_fan_impl(ctx, poses6, n, fan, blocked, units, first_hit, best_idx,
+                            FanMode::Plain, nullptr, 0, nullptr, true, el_table);
+}
+
+int pcp_raycast_fan_mounted_burst(pcp_ctx *ctx, const double *poses6, uint64_t n,
+                                  const pcp_fan_params *fan, const double *el_table, int reps,
+                                  double *ms_per_launch) {
+    if (!ctx || !ms_per_launch || reps <= 0) return PCP_E_INVALID;
+    std::vector<uint32_t> blocked(n ? n : 1);
+    *ms_per_launch = 0.0;
+    return raycast_fan_impl(ctx, poses6, n, fan, blocked.data(), nullptr, nullptr, nullptr,
+                            FanMode::Plain, nullptr, reps, ms_per_launch, true, el_table);
 }
 
 int pcp_raycast_fan_stamps(pcp_ctx *ctx, const double *poses5, uint64_t n,
