@@ -73,8 +73,9 @@ PCP_CLIP_HD double fan_clip_delta(int K, double fb_abs_max) {
 
 // The slab times of the ray p + d t against the box fb = {x0, x1, y0, y1, z0, z1}; inv[a] ~
 // 1 / d[a] comes from the caller.  False: the ray misses the box.
-PCP_CLIP_HD bool fan_clip_slabs(const float fb[6], const float p[3], const float inv[3], float &t0,
-                                float &t1) {
+// (rel: the six face differences fb[i] - p[i / 2], formed by the caller -- the fan's pose rows
+// carry them ready, pcp_fan_row.hpp)
+PCP_CLIP_HD bool fan_clip_slabs_rel(const float rel[6], const float inv[3], float &t0, float &t1) {
     // branch-free slabs: a zero (or flushed denormal) direction component gives +-inf slab
     // times, so a start strictly inside the slab leaves [t0, t1] as it is and one outside
     // empties it; a start exactly on a slab face (0 * inf = NaN, dropped by fmin/fmax, the
@@ -83,11 +84,17 @@ PCP_CLIP_HD bool fan_clip_slabs(const float fb[6], const float p[3], const float
     t0 = 0.0f;
     t1 = FLT_MAX;
     for (int a = 0; a < 3; ++a) {
-        const float ta = (fb[2 * a] - p[a]) * inv[a], tb = (fb[2 * a + 1] - p[a]) * inv[a];
+        const float ta = rel[2 * a] * inv[a], tb = rel[2 * a + 1] * inv[a];
         t0 = fmaxf(t0, fminf(ta, tb));
         t1 = fminf(t1, fmaxf(ta, tb));
     }
     return t0 <= t1;
+}
+PCP_CLIP_HD bool fan_clip_slabs(const float fb[6], const float p[3], const float inv[3], float &t0,
+                                float &t1) {
+    const float rel[6] = {fb[0] - p[0], fb[1] - p[0], fb[2] - p[1],
+                          fb[3] - p[1], fb[4] - p[2], fb[5] - p[2]};
+    return fan_clip_slabs_rel(rel, inv, t0, t1);
 }
 
 // [t0, t1] to sample bounds with e samples of slack each side, inv_step = fl(1 / 0.3)
@@ -105,6 +112,17 @@ PCP_CLIP_HD void fan_clip(const float fb[6], const float p[3], const float inv[3
                           float e, int K, int &klo, int &khi) {
     float t0, t1;
     if (!fan_clip_slabs(fb, p, inv, t0, t1)) {
+        klo = 0;
+        khi = -1;
+        return;
+    }
+    fan_clip_bounds(t0, t1, inv_step, e, K, klo, khi);
+}
+// the same from the six face differences
+PCP_CLIP_HD void fan_clip_rel(const float rel[6], const float inv[3], float inv_step, float e,
+                              int K, int &klo, int &khi) {
+    float t0, t1;
+    if (!fan_clip_slabs_rel(rel, inv, t0, t1)) {
         klo = 0;
         khi = -1;
         return;

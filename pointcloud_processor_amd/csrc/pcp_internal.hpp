@@ -571,9 +571,9 @@ struct FanEnq {
     const uint2 *wave_part = nullptr;
     uint32_t waves = 0, wave0 = 0, live_waves = 0;
     int K = 0;
-    // doubles per staged pose row: 8, or kFanDirRow of a mounted query (pcp_fan_dir.hpp); the
-    // pinned results start behind the rows
-    uint32_t pose_row = 8;
+    // doubles per staged pose row, set by fan_enqueue: kFanRow (pcp_fan_row.hpp), or kFanDirRow
+    // of a mounted query (pcp_fan_dir.hpp); the pinned results start behind the rows
+    uint32_t pose_row = 0;
     bool mounted = false;
 };
 struct FanOpts {

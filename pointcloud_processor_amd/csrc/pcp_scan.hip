@@ -13,6 +13,7 @@
 #include <cstring>
 
 #include "pcp_fan_dir.hpp"
+#include "pcp_fan_row.hpp"
 #include "pcp_internal.hpp"
 #include "pcp_stencil.hpp"
 
@@ -31,7 +32,7 @@ static_assert(sizeof(pcp_scan_return) == 24, "pcp_scan_return is a 24-byte recor
 struct ResolveArgs {
     GridView g;
     const double *ca, *sa, *ce, *se;
-    const double *pose;                  // P x 8: x, y, z, pitch, yaw, cos(yaw), sin(yaw), pad
+    const double *pose;                  // P x kFanRow, pcp_fan_row.hpp's rows
                                          // (MT: P x kFanDirRow, pcp_fan_dir.hpp's rows)
     const double *steps;
     int n_az;
@@ -117,7 +118,7 @@ __global__ void __launch_bounds__(kST) k_scan_resolve(ResolveArgs a) {
     const uint32_t j = ray / (uint32_t)a.n_az, i = ray - j * (uint32_t)a.n_az;
     const double cej = a.ce[j];
     const double lx = cej * a.ca[i], ly = cej * a.sa[i], lz = a.se[j];
-    const double *Pq = a.pose + (MT ? kFanDirRow : 8) * (size_t)p;
+    const double *Pq = a.pose + (MT ? kFanDirRow : kFanRow) * (size_t)p;
     const double px = Pq[0], py = Pq[1], pz = Pq[2];
     double dx, dy, dz;
     if (MT) {
@@ -126,7 +127,7 @@ __global__ void __launch_bounds__(kST) k_scan_resolve(ResolveArgs a) {
         dy = d.y;
         dz = d.z;
     } else {
-        const double cy = Pq[5], sy = Pq[6];
+        const double cy = Pq[FR_CY], sy = Pq[FR_SY];
         dx = cy * lx - sy * ly;
         dy = sy * lx + cy * ly;
         dz = lz;

@@ -19,6 +19,7 @@
 #include "pcp_fan_clip.hpp"
 #include "pcp_fan_cull.hpp"
 #include "pcp_fan_dir.hpp"
+#include "pcp_fan_row.hpp"
 #include "pcp_internal.hpp"
 #include "pcp_stencil.hpp"
 
@@ -111,11 +112,21 @@ __device__ __forceinline__ bool scan_stencil(const GridView &g, uint32_t lin, fl
 #define PCP_BLK_STEP 1   // block-walk points per step (build knob)
 #endif
 // a * b + c for a, b < 2^24 as one full-rate v_mad_u32_u24 (the compiler otherwise picks the
-// 64-bit multi-pass v_mad_u64_u32)
+// 64-bit multi-pass v_mad_u64_u32 -- also for masked operands and for __umul24 plus an add; the
+// operands are VGPRs, so a loop that multiplies by a scalar pins its copy first, vgpr_pin)
 __device__ __forceinline__ uint32_t mad_u24(uint32_t a, uint32_t b, uint32_t c) {
     uint32_t d;
     asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
     return d;
+}
+// A wave-uniform value as a VGPR the compiler keeps: ahead of a loop whose instructions need it
+// in a VGPR (mad_u24's operands, v_fmamk_f32's addend), instead of one v_mov_b32 per trip
+template <class T>
+__device__ __forceinline__ T vgpr_pin(T x) {
+#ifndef PCP_NO_VGPR_PIN   // (A/B build knob)
+    asm("" : "+v"(x));
+#endif
+    return x;
 }
 
 // a z-descending run pts[k0 .. e): the walk of one block (or one fine window)
@@ -211,6 +222,14 @@ __device__ __forceinline__ void clip_kf(const GridView &g, double px, double py,
                           __builtin_amdgcn_rcpf((float)dz)};
     fan_clip(g.fb, p, inv, (float)(1.0 / kRayStep), g.fclip_e, K, klo, khi);
 }
+// the same from a pose row's six face differences (pcp_fan_row.hpp: fb[i] - (float)p, the
+// subtractions fan_clip_slabs would do)
+__device__ __forceinline__ void clip_kf_row(const GridView &g, const float *rel, double dx,
+                                            double dy, double dz, int K, int &klo, int &khi) {
+    const float inv[3] = {__builtin_amdgcn_rcpf((float)dx), __builtin_amdgcn_rcpf((float)dy),
+                          __builtin_amdgcn_rcpf((float)dz)};
+    fan_clip_rel(rel, inv, (float)(1.0 / kRayStep), g.fclip_e, K, klo, khi);
+}
 
 // checkVisibilityWithRaycasting's march (virtual_lidar.cpp:765-797) from pos along unit dir:
 // the samples s_k < end in order, returns the first blocked k or -1.
@@ -243,27 +262,37 @@ __device__ __forceinline__ void clip_kf(const GridView &g, double px, double py,
 //  * PIV (the fan kernels, FN 8): Skip 6, a candidate tests its window's pivot first, below.
 //    Cell scoring, the scan and the placement leave it out: their rays end at a visible cell, so
 //    few of their candidates are hits.
-template <bool STATS, bool ZB = true, int NB = 1, int FN = 0, bool CLR = false, bool PIV = false>
+//  * ROW (the level fan kernels): rowf is the float block of the pose's row (pcp_fan_row.hpp) --
+//    the clip's face differences and the probe origin's pose part, formed once per pose on the
+//    host with the expressions below, bit for bit; the other callers form them here.
+//  * SP (the production fan kernel): the layout facts of the default build as compile-time
+//    facts -- packed walk entries (g.wpack), two skip thresholds (g.fskip == 2), a pivot table
+//    (g.fpiv) and clearance codes (g.fclear).  fan_launch picks an SP kernel only over a view that
+//    has all four; the flags and the pointers they guard are then not held across the pose loop.
+template <bool STATS, bool ZB = true, int NB = 1, int FN = 0, bool CLR = false, bool PIV = false,
+          bool ROW = false, bool SP = false>
 __device__ __forceinline__ int march(const GridView &g, double px, double py, double pz,
                                      double dx, double dy, double dz,
                                      const double *__restrict__ steps, int K, double end,
                                      float r2, float rexit, uint32_t *cnt = nullptr,
-                                     int koff = 0, int kstr = 1) {
+                                     int koff = 0, int kstr = 1, const float *rowf = nullptr) {
+    static_assert(!SP || FN == 8, "the layout facts are the split records'");
     if (FN == 2) {
         if (g.frec && g.ftile == 2)
-            return march<STATS, ZB, NB, 8, CLR, PIV>(g, px, py, pz, dx, dy, dz, steps, K, end,
-                                                     r2, rexit, cnt, koff, kstr);
+            return march<STATS, ZB, NB, 8, CLR, PIV, ROW>(g, px, py, pz, dx, dy, dz, steps, K,
+                                                          end, r2, rexit, cnt, koff, kstr, rowf);
         if (g.frec && g.ftile)
-            return march<STATS, ZB, NB, 4, CLR, PIV>(g, px, py, pz, dx, dy, dz, steps, K, end,
-                                                     r2, rexit, cnt, koff, kstr);
+            return march<STATS, ZB, NB, 4, CLR, PIV, ROW>(g, px, py, pz, dx, dy, dz, steps, K,
+                                                          end, r2, rexit, cnt, koff, kstr, rowf);
         if (g.frec)
-            return march<STATS, ZB, NB, 1, CLR, PIV>(g, px, py, pz, dx, dy, dz, steps, K, end,
-                                                     r2, rexit, cnt, koff, kstr);
-        return march<STATS, ZB, NB, 0, CLR, PIV>(g, px, py, pz, dx, dy, dz, steps, K, end, r2,
-                                                 rexit, cnt, koff, kstr);
+            return march<STATS, ZB, NB, 1, CLR, PIV, ROW>(g, px, py, pz, dx, dy, dz, steps, K,
+                                                          end, r2, rexit, cnt, koff, kstr, rowf);
+        return march<STATS, ZB, NB, 0, CLR, PIV, ROW>(g, px, py, pz, dx, dy, dz, steps, K, end,
+                                                      r2, rexit, cnt, koff, kstr, rowf);
     }
     int klo, khi;
-    clip_kf(g, px, py, pz, dx, dy, dz, K, klo, khi);
+    if (ROW) clip_kf_row(g, rowf + FRF_CLIP, dx, dy, dz, K, klo, khi);
+    else clip_kf(g, px, py, pz, dx, dy, dz, K, klo, khi);
     if (end < 1e299) {   // s_k < end: k <= (end - 0.5) / 0.3, with one sample of slack
         const double ke = floor((end - 0.5) / kRayStep) + 1.0;
         khi = (int)fmin((double)khi, fmax(ke, -1.0));
@@ -272,9 +301,9 @@ __device__ __forceinline__ int march(const GridView &g, double px, double py, do
     const float fdx = (float)dx, fdy = (float)dy, fdz = (float)dz;
     const float sc = (float)kRayStep * g.finv_c, h = 0.5f * g.finv_c;   // s_k = 0.5 + 0.3 k
     const float Dx = fdx * sc, Dy = fdy * sc, Dz = fdz * sc;
-    const float Ax = ((float)px - g.flo_x) * g.finv_c + fdx * h;
-    const float Ay = ((float)py - g.flo_y) * g.finv_c + fdy * h;
-    const float Az = ((float)pz - g.flo_z) * g.finv_c + fdz * h;
+    const float Ax = (ROW ? rowf[FRF_BASE] : ((float)px - g.flo_x) * g.finv_c) + fdx * h;
+    const float Ay = (ROW ? rowf[FRF_BASE + 1] : ((float)py - g.flo_y) * g.finv_c) + fdy * h;
+    const float Az = (ROW ? rowf[FRF_BASE + 2] : ((float)pz - g.flo_z) * g.finv_c) + fdz * h;
     const uint32_t nx = (uint32_t)g.nx, ny = (uint32_t)g.ny;
     if (FN == 1 || FN == 4 || FN == 8) {
         // fine units for x, y (the fine cell of the sample, (q - o) / c_f = F (f + fzoff)),
@@ -285,8 +314,14 @@ __device__ __forceinline__ int march(const GridView &g, double px, double py, do
         const float F = g.ffine;
         const float D2x = F * Dx, D2y = F * Dy, A2x = F * (Ax + g.fzoff), A2y = F * (Ay + g.fzoff);
         const uint32_t mx = g.frx - 1, my = g.fry - 1, mz = g.frz - 1;
-        const uint32_t rx = FN == 4 ? (g.frx + 3) >> 2 : FN == 8 ? (g.frx + 7) >> 3 : g.frx;
-        const uint32_t ry = FN == 4 ? (g.fry + 3) >> 2 : FN == 8 ? (g.fry + 7) >> 3 : g.fry;
+        const float fmx = (float)mx, fmy = (float)my, fmz = (float)mz;
+        (void)mx, (void)my, (void)mz, (void)fmx, (void)fmy, (void)fmz;
+        const uint32_t rxs = FN == 4 ? (g.frx + 3) >> 2 : FN == 8 ? (g.frx + 7) >> 3 : g.frx;
+        const uint32_t rys = FN == 4 ? (g.fry + 3) >> 2 : FN == 8 ? (g.fry + 7) >> 3 : g.fry;
+        // (FN 8, the fan's layout: the tile counts and the probe's height offset pinned in
+        // VGPRs for the loop -- three v_mov_b32 per probe fewer)
+        const uint32_t rx = FN == 8 ? vgpr_pin(rxs) : rxs, ry = FN == 8 ? vgpr_pin(rys) : rys;
+        const float fus_off = FN == 8 ? vgpr_pin(g.fus_off) : g.fus_off;
         // Skip 5 (FN 8 with CLR, pcp_fan_clear.hpp): a descending ray whose sample reads an
         // empty record with clearance code e jumps its next floor((e c_f - rb) / hs) samples.
         // They are lower than q_k and horizontally within e c_f - rb of it, q_k lies in the
@@ -295,7 +330,7 @@ __device__ __forceinline__ int march(const GridView &g, double px, double py, do
         // reads a border record, whose code is 0; a ray that does not descend (or the knob off)
         // has a = b = 0.
         const ClearRay cr = FN == 8 && CLR ? fan_clear_ray(fdx, fdy, fdz, (float)kRayStep, g.fclr_cf,
-                                                    g.fclr_rb, g.fclear != 0)
+                                                    g.fclr_rb, SP || g.fclear != 0)
                                     : ClearRay{0.0f, 0.0f};
         // jump: the samples skipped after sample k; the lane goes on at its next own sample
         // past k + jump (a group's lanes keep their residue)
@@ -304,9 +339,18 @@ __device__ __forceinline__ int march(const GridView &g, double px, double py, do
             const float fx = __builtin_fmaf(D2x, kf, A2x);
             const float fy = __builtin_fmaf(D2y, kf, A2y);
             const float fz = __builtin_fmaf(Dz, kf, Az);
+            // the clamp to [0, m] in float, one v_med3_f32 before the conversion: m < 2^24 is a
+            // float, a value in (m, m + 1) converts to m either way, and a NaN gives
+            // min(NaN, 0, m) = 0 as fmaxf(NaN, 0) did -- the same cell for every input
+#ifdef PCP_CLAMP_INT   // A/B build only: the former three instructions per axis
             const uint32_t ix = min((uint32_t)fmaxf(fx, 0.0f), mx);
             const uint32_t iy = min((uint32_t)fmaxf(fy, 0.0f), my);
             const uint32_t iz = min((uint32_t)fmaxf(fz, 0.0f), mz);
+#else
+            const uint32_t ix = (uint32_t)__builtin_amdgcn_fmed3f(fx, 0.0f, fmx);
+            const uint32_t iy = (uint32_t)__builtin_amdgcn_fmed3f(fy, 0.0f, fmy);
+            const uint32_t iz = (uint32_t)__builtin_amdgcn_fmed3f(fz, 0.0f, fmz);
+#endif
             // 24-bit multiply-adds (full rate): build_fine caps frx, fry * frz below 2^24.
             // FN 4: records in 4 x 4 xy tiles, one 128-byte line each (a wave's arc of probes
             // touches fewer lines whatever its direction); rx, ry are then the tile counts.
@@ -322,7 +366,7 @@ __device__ __forceinline__ int march(const GridView &g, double px, double py, do
             if (FN == 8) R.y = ld_u16o(g.fband, ri);
             else R = ld_rec(g.frec, ri);
             // height above the block floor in kZq steps against the record's thresholds
-            const float us = __builtin_fmaf(fz - (float)iz, 1.0f / kZq, g.fus_off);
+            const float us = __builtin_fmaf(fz - (float)iz, 1.0f / kZq, fus_off);
             const float lo = (float)(R.y & 255u);   // 255: an empty record
             const bool cand = (us < (float)((R.y >> 8) & 255u)) & (us > lo);
             // Skip 5: the samples to jump after this one (0 unless the record is empty)
@@ -344,7 +388,7 @@ __device__ __forceinline__ int march(const GridView &g, double px, double py, do
                 // walk start, no entry.  Otherwise nothing is concluded and the walk runs as it
                 // did.  The table's tiles are the band records' (rx = g.fptx; ri's low 6 bits
                 // are the cell's place in its tile); an empty window's sentinel is never within r.
-                if (FN == 8 && PIV && g.fpiv) {
+                if (FN == 8 && PIV && (SP || g.fpiv)) {
                     const uint32_t pi = (mad_u24(rx, iy >> 3, ix >> 3) << 6) | (ri & 63u);
                     const float *pf = reinterpret_cast<const float *>(
                         reinterpret_cast<const char *>(g.fpiv) + ((pi << 3) + (pi << 2)));
@@ -359,7 +403,7 @@ __device__ __forceinline__ int march(const GridView &g, double px, double py, do
                     // the thresholds are the record's double heights rounded through fzo, fzc
                     // and the fma (a few ulps of the larger magnitude): the margin grows with
                     // them, so far from the origin (|z| of km) the skip stays exact
-                    if (g.fskip == 2) {
+                    if (SP || g.fskip == 2) {
                         const float ha = __builtin_fmaf((float)iz + 1.375f, g.fzc, g.fzo);
                         const float hb = __builtin_fmaf((float)iz + 1.6875f, g.fzc, g.fzo);
                         const float marg = 1e-4f + 4.0f * FLT_EPSILON *
@@ -375,9 +419,10 @@ __device__ __forceinline__ int march(const GridView &g, double px, double py, do
                         w0 = (ws & 0x0FFFFFFFu) + (qz + (rexit + marg) < h2 ? ws >> 28 : 0u);
                     }
                 }
-                if (g.wpack ? scan_window3<STATS>(reinterpret_cast<const float *>(g.wpts), w0, qx,
-                                                  qy, qz, r2, rexit, cnt)
-                            : scan_window<STATS>(g.wpts, w0, qx, qy, qz, r2, rexit, cnt))
+                const bool packed = SP || g.wpack;
+                if (packed ? scan_window3<STATS>(reinterpret_cast<const float *>(g.wpts), w0, qx,
+                                                 qy, qz, r2, rexit, cnt)
+                           : scan_window<STATS>(g.wpts, w0, qx, qy, qz, r2, rexit, cnt))
                     return k;
             }
         }
@@ -1349,9 +1394,10 @@ k_cand_compact(const double *__restrict__ lat, int L, double *__restrict__ out, 
 struct FanArgs {
     GridView g;
     const double *ca, *sa, *ce, *se;
-    const double *pose;    // P x 8: x, y, z, pitch, yaw, cos(yaw), sin(yaw), and as two uint32
-                           // the pose's live rings [j0, j1) (pcp_fan_cull.hpp); the mounted
-                           // kernels: P x kFanDirRow, the rows of pcp_fan_dir.hpp
+    const double *pose;    // P x kFanRow, the rows of pcp_fan_row.hpp: the pose, cos / sin of its
+                           // yaw, its live rings [j0, j1) (pcp_fan_cull.hpp) and the preamble's
+                           // pose-uniform floats; the mounted kernels: P x kFanDirRow, the rows
+                           // of pcp_fan_dir.hpp
     const double *steps;
     int K;
     int n_az;
@@ -1400,11 +1446,15 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
 // and the direction is its fan_dir() -- roll, pitch and yaw per pose on the wave's shared local
 // direction; a tilted ring has no one dz, so there is no ring liveness (Skip 4) and the launch
 // covers the full grid.
+// SP: march's layout facts (the production kernel; fan_launch).
 template <int MODE, int BS, bool ZB = true, int FN = 0, bool UE = false, int NPW = 1,
-          bool SL = false, bool MT = false>
+          bool SL = false, bool MT = false, bool SP = false>
 __device__ __forceinline__ void fan_body(const FanArgs &a, uint32_t p0, uint32_t rblock) {
     static_assert(!MT || MODE == FAN_PLAIN, "the mounted march has no diagnostic modes");
-    constexpr int PR = MT ? kFanDirRow : 8;   // doubles per pose row
+    static_assert(!SP || !MT, "the mounted kernels keep the run-time layout tests");
+    constexpr int PR = MT ? kFanDirRow : kFanRow;   // doubles per pose row
+    static_assert(PR * 32 * sizeof(double) + kStepLds * sizeof(double) <= 160 * 1024 / 8,
+                  "at the widest NPW at least 8 one-wave workgroups per CU keep their LDS");
     const uint32_t ray = rblock * BS + threadIdx.x;
     const uint32_t wid = ray >> 6;
     const bool active = ray < a.rays;
@@ -1460,14 +1510,14 @@ __device__ __forceinline__ void fan_body(const FanArgs &a, uint32_t p0, uint32_t
     // own immediate return: 0.0557 vs 0.0555 ms at zero tilt, profiles/mount_early_out_ab.json)
     if (MT) md = fan_dir(P, lx, ly, lz);
     if (UE && !MT) {
-        const uint2 lr = *reinterpret_cast<const uint2 *>(P + 7);
+        const uint2 lr = *reinterpret_cast<const uint2 *>(P + FR_LIVE);
         const uint32_t j0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)lr.x);
         const uint32_t j1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)lr.y);
         dead = ju < j0 || ju >= j1;
         if (MODE == FAN_STAMPS && dead) t1 = t0;
     }
     if (!dead && active && a.present) {
-        const double cy = MT ? 0.0 : P[5], sy = MT ? 0.0 : P[6];
+        const double cy = MT ? 0.0 : P[FR_CY], sy = MT ? 0.0 : P[FR_SY];
         const double dx = MT ? md.x : cy * lx - sy * ly;
         const double dy = MT ? md.y : sy * lx + cy * ly;
         const double dz = MT ? md.z : lz;
@@ -1475,8 +1525,15 @@ __device__ __forceinline__ void fan_body(const FanArgs &a, uint32_t p0, uint32_t
             asm volatile("" ::"v"(dx), "v"(dy));
             t1 = __builtin_amdgcn_s_memtime();
         }
-        hit = march<MODE == FAN_STATS, ZB, 1, FN, true, true>(a.g, P[0], P[1], P[2], dx, dy, dz,
-                                                              steps, a.K, 1e300, a.r2, a.rexit, cnt);
+        // (the level rows carry the preamble's pose-uniform floats; a mounted row does not)
+#ifdef PCP_FAN_NO_ROW   // A/B build only: the row's floats unused, the preamble derives them
+        constexpr bool ROW = false;
+#else
+        constexpr bool ROW = !MT;
+#endif
+        hit = march<MODE == FAN_STATS, ZB, 1, FN, true, true, ROW, SP>(
+            a.g, P[0], P[1], P[2], dx, dy, dz, steps, a.K, 1e300, a.r2, a.rexit, cnt, 0, 1,
+            MT ? nullptr : fan_row_floats(P));
     }
     if (MODE == FAN_STAMPS) {
         asm volatile("" ::"v"(hit));
@@ -1537,13 +1594,13 @@ k_raycast_fan(FanArgs a, uint32_t P) {
 // just below the horizon march 2-3 times as long as the steep ones: dispatched last they would
 // be the launch's tail
 template <int MODE, int BS = 64, bool ZB = true, int W = 8, int FN = 1, bool UE = true, int NPW = 1,
-          bool MT = false>
+          bool MT = false, bool SP = false>
 __global__ void __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(W, W)))
 k_raycast_fan_xcd(FanArgs a, uint32_t P) {
     const uint32_t pc = P >> 3, gpc = pc / NPW, j = blockIdx.x >> 3;
     const uint32_t b = j / gpc;
-    fan_body<MODE, BS, ZB, FN, UE, NPW, true, MT>(a, (blockIdx.x & 7u) * pc + (j % gpc) * NPW,
-                                             a.w0 + (a.rev ? a.lw - 1u - b : b));
+    fan_body<MODE, BS, ZB, FN, UE, NPW, true, MT, SP>(a, (blockIdx.x & 7u) * pc + (j % gpc) * NPW,
+                                                      a.w0 + (a.rev ? a.lw - 1u - b : b));
 }
 
 // A/B: pose-major 2-D grid (blockIdx.y = pose), BS-thread workgroups (P: unused, fan_launch's)
@@ -1645,6 +1702,11 @@ constexpr FanKernel kFanXcd[3][6] = {
     {kXcd<1, 1>},   // (the untiled copy: one pose per wave only)
     {kXcd<4, 1>, kXcd<4, 2>, kXcd<4, 4>, kXcd<4, 8>, kXcd<4, 16>, kXcd<4, 32>},
     {kXcd<8, 1>, kXcd<8, 2>, kXcd<8, 4>, kXcd<8, 8>, kXcd<8, 16>, kXcd<8, 32>}};
+// the split records' kernels with the default build's layout as compile-time facts (march, SP)
+template <int NPW>
+constexpr FanKernel kXcdSp = k_raycast_fan_xcd<FAN_PLAIN, 64, true, 8, 8, true, NPW, false, true>;
+constexpr FanKernel kFanXcdSp[6] = {kXcdSp<1>, kXcdSp<2>,  kXcdSp<4>,
+                                    kXcdSp<8>, kXcdSp<16>, kXcdSp<32>};
 // the mounted forms (Plain only): the same two tables
 template <int FN, bool UE>
 constexpr FanKernel kFineMt = k_raycast_fan<FAN_PLAIN, 64, true, 8, FN, UE, true>;
@@ -1677,6 +1739,13 @@ static hipError_t fan_launch(const FanPick &k, FanGrid g, hipStream_t st, hipEve
         f = fn > 0 && k.mode == FanMode::Plain
                 ? (k.mounted ? kFanXcdMt : kFanXcd)[fn - 1][__builtin_ctz(k.NPW)]
                 : nullptr;
+        // the default build's layout (PCP_FINE_PACK, PCP_FINE_SKIP=2, the pivot table, the
+        // clearance codes): the kernel that knows it at compile time; any knob off keeps the
+        // kernel that tests at run time (PCP_FAN_NO_SP: an A/B build that never picks it)
+#ifndef PCP_FAN_NO_SP
+        if (f && fn == 3 && !k.mounted && a.g.wpack && a.g.fskip == 2 && a.g.fpiv && a.g.fclear)
+            f = kFanXcdSp[__builtin_ctz(k.NPW)];
+#endif
         break;
     case FanFamily::PoseMajor: f = k.mounted ? nullptr : k_raycast_fan_pm<128, true>; break;
     case FanFamily::OccBit: f = k.mounted ? nullptr : k_raycast_fan<FAN_PLAIN, 64, false>; break;
@@ -2347,19 +2416,11 @@ int fan_enqueue(pcp_ctx *ctx, const double *poses5, uint64_t n, const pcp_fan_pa
     // regrown) by this query, whichever entry point enqueues it
     if (ctx->keys_pending) PCP_HIP(ctx, hipEventSynchronize(ctx->keys_ev));
     ctx->keys_pending = false;
-    // pinned staging: poses in (P x 8 doubles; a mounted query: P x kFanDirRow), then {units
+    // pinned staging: poses in (P x kFanRow doubles; a mounted query: P x kFanDirRow), then {units
     // u64[P], blocked u32[P]} out
-    const size_t row = opt.mounted ? (size_t)kFanDirRow : 8;
+    const size_t row = opt.mounted ? (size_t)kFanDirRow : (size_t)kFanRow;
     PCP_HIP(ctx, ctx->fan_host.ensure((size_t)P * (row * sizeof(double) + 12) + 64));
     double *pose8 = ctx->fan_host.as<double>();
-    for (int k = 0; k < P && !opt.mounted; ++k) {
-        const double *s = poses5 + 5 * (size_t)k;
-        double *d = pose8 + 8 * (size_t)k;
-        for (int q = 0; q < 5; ++q) d[q] = s[q];
-        d[5] = std::cos(s[4]);
-        d[6] = std::sin(s[4]);
-        d[7] = 0.0;
-    }
     for (int k = 0; k < P && opt.mounted; ++k)   // (poses6 rows)
         fan_dir_row(poses5 + 6 * (size_t)k, pose8 + row * (size_t)k);
     PCP_HIP(ctx, ctx->poses_d.ensure((size_t)P * row * sizeof(double)));
@@ -2376,6 +2437,15 @@ int fan_enqueue(pcp_ctx *ctx, const double *poses5, uint64_t n, const pcp_fan_pa
         if (ctx->fan_batch == 2 && !a.g.occ2)
             return set_err(ctx, PCP_E_STATE, "pcp_raycast_fan: variant 2 needs a terrain set with PCP_FAN_BATCH=2");
     }
+    // the level rows (pcp_fan_row.hpp): the pose and, against this query's view, the march
+    // preamble's pose-uniform floats (no terrain: a zero view, the march does not run)
+    if (!opt.mounted) {
+        const FanRowGrid rg{{a.g.fb[0], a.g.fb[1], a.g.fb[2], a.g.fb[3], a.g.fb[4], a.g.fb[5]},
+                            {a.g.flo_x, a.g.flo_y, a.g.flo_z},
+                            a.g.finv_c};
+        for (int k = 0; k < P; ++k)
+            fan_row_fill(poses5 + 5 * (size_t)k, rg, pose8 + row * (size_t)k);
+    }
     a.uniform_el = (fan->n_az % 64 == 0) ? 1 : 0;
     // the kernel and whether it runs on the full grid: asked once, here (pcp_fan_pick.hpp)
     const FanPick pick = fan_pick(mode, ctx->fan_batch, a.g.frec != nullptr, a.g.ftile,
@@ -2387,12 +2457,13 @@ int fan_enqueue(pcp_ctx *ctx, const double *poses5, uint64_t n, const pcp_fan_pa
     // pose: only those are launched, unless the pick needs the full grid.
     uint32_t w0 = 0, lw = waves;
     if (!opt.mounted) {   // (a mounted row has no live-ring slot: its kernels cover every ring)
-        uint32_t *lr = reinterpret_cast<uint32_t *>(pose8 + 7);
+        uint32_t *lr = reinterpret_cast<uint32_t *>(pose8) + kFanRowLiveU32;
         const bool rule = ctx->fan_cull && ctx->terrain.present && K > 0;
         if (rule) {
-            const FanLive L = fan_live_rings((double)a.g.fb[4], (double)a.g.fb[5], pose8 + 2,
-                                             (uint64_t)P, 8, ctx->fan_se_h.data(), fan->n_el,
-                                             ctx->steps_first, ctx->steps_last, lr, 16);
+            const FanLive L = fan_live_rings((double)a.g.fb[4], (double)a.g.fb[5], pose8 + FR_Z,
+                                             (uint64_t)P, kFanRow, ctx->fan_se_h.data(), fan->n_el,
+                                             ctx->steps_first, ctx->steps_last, lr,
+                                             kFanRowStrideU32);
             if (!pick.full_grid) {
                 const FanWaves W = fan_live_waves(L, fan->n_az, fan->n_el);
                 w0 = W.w0;
@@ -2400,8 +2471,8 @@ int fan_enqueue(pcp_ctx *ctx, const double *poses5, uint64_t n, const pcp_fan_pa
             }
         } else {
             for (int k = 0; k < P; ++k) {
-                lr[16 * (size_t)k] = 0u;
-                lr[16 * (size_t)k + 1] = (uint32_t)fan->n_el;
+                lr[kFanRowStrideU32 * (size_t)k] = 0u;
+                lr[kFanRowStrideU32 * (size_t)k + 1] = (uint32_t)fan->n_el;
             }
         }
     }
