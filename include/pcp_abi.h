@@ -464,6 +464,58 @@ int pcp_place_pair(pcp_ctx *ctx, const double *poses5, uint64_t n, const double 
 int pcp_place_pair_burst(pcp_ctx *ctx, const double *poses5, uint64_t n, const double zx120_pose5[5],
                          const pcp_vl_params *p, const pcp_pair_params *pp, int reps, double *ms_per_rep);
 
+/* The exact best triple of mobile sensors: every triple of the poses evaluated (greedy's three can
+ * be 1-exchange optimal and still not the best three: two sensors may have to move together).
+ * S[p][c], Z[c], max(a, b), osum(v), base, the owners, admissibility and the separation expression
+ * are pcp_place_pair's, and so is pp.
+ *   1.-4. pcp_place_pair's steps 1 to 4: *base_total / *base_covered, the singles with
+ *      *best_single / *single_total / *single_covered, the pairs with best_pair / *pair_total /
+ *      *pair_covered -- the values that call returns for the same arguments (its dense tables are
+ *      not returned here).
+ *   5. For a < b < c, all three admissible and (min_separation > 0) no two of them closer to each
+ *      other than it: t[a][b][c] = osum(max(max(max(base, S[a]), S[b]), S[c])); triple_totals
+ *      [n][n][n] holds t[a][b][c], every other entry -inf.  first_totals[a] = the first maximum
+ *      of t[a][.][.] over (b, c) in row-major order (b ascending, then c; strict '>' from -inf),
+ *      first_partners[a] its (b, c); -inf and (-1, -1) where pose a starts no triple.
+ *      best_triple = the first maximum over a of first_totals, i.e. the lexicographically first
+ *      maximal triple, (-1, -1, -1) when there is no admissible triple; *triple_total /
+ *      *triple_covered its total and its count of positive elements (-inf / 0 without one).
+ *   6. The answer: T = *base_total, *n_selected = 0; if a single exists and *single_total > T:
+ *      *n_selected = 1, T = *single_total; if a pair exists and *pair_total > T: *n_selected = 2,
+ *      T = *pair_total; if a triple exists and *triple_total > T: *n_selected = 3.  (A single's or
+ *      a pair's total is never below the base's, so the first two steps are pcp_place_pair's
+ *      rule; under a separation the best triple can lose to a pair or a single.)  cell_score /
+ *      cell_owner describe that answer: the base, then the chosen poses folded in ascending index
+ *      order with owners n_fixed, n_fixed + 1, n_fixed + 2, ties to the earlier owner.
+ * PCP_E_INVALID before any launch, nothing written: everything pcp_place_pair refuses, n >
+ * PCP_TRIPLE_MAX_POSES, triple_totals given with n > PCP_TRIPLE_TABLE_MAX_POSES, a null required
+ * pointer (everything not marked nullable), a null context.  n == 0 or no cells: PCP_OK,
+ * *n_selected = 0, every index -1, the base totals as defined (0 without cells); n < 3 just has no
+ * triple.  One synchronisation; deterministic (two calls give identical bytes); the caller's
+ * GridCell flags are neither read nor written; the call's scratch is its own, so the other queries
+ * on the context are unchanged by it. */
+#define PCP_TRIPLE_MAX_POSES        512   /* 22.2 M triples */
+#define PCP_TRIPLE_TABLE_MAX_POSES  128   /* the dense table is offered up to here (16.8 MB) */
+int pcp_place_triple(pcp_ctx *ctx, const double *poses5, uint64_t n, const double zx120_pose5[5],
+                     const pcp_vl_params *p, const pcp_pair_params *pp,   /* the pair call's struct */
+                     int64_t best_triple[3], double *triple_total, int32_t *triple_covered,
+                     int64_t best_pair[2], double *pair_total, int32_t *pair_covered,
+                     int64_t *best_single, double *single_total, int32_t *single_covered,
+                     double *base_total, int32_t *base_covered,
+                     double *first_totals,    /* nullable [n]       */
+                     int64_t *first_partners, /* nullable [n][2]    */
+                     double *triple_totals,   /* nullable [n][n][n] */
+                     double *cell_score, int32_t *cell_owner,   /* nullable [n_cells] */
+                     int32_t *n_selected);
+
+/* Kernel timing of pcp_place_triple (the timing tool only): the query's setup (the scoring) once,
+ * then `reps` repetitions of its triple phase -- the pair phase it builds on (preparation, pair
+ * tiles, selection), the triple tiles, the rows' maxima and the selection, no dense table --
+ * between two stream events; *ms_per_rep = the interval / reps.  n >= 3, cells present. */
+int pcp_place_triple_burst(pcp_ctx *ctx, const double *poses5, uint64_t n, const double zx120_pose5[5],
+                           const pcp_vl_params *p, const pcp_pair_params *pp, int reps,
+                           double *ms_per_rep);
+
 /* 1-exchange refinement of a placement: a set of k sensors (greedy's answer, or a deployment as
  * it stands) is improved by moving one sensor at a time to the pose that raises the total most,
  * until no single move raises it.  S[p][c], Z[c], max(a, b), osum(v) and the separation expression

@@ -95,6 +95,9 @@ class PairParams(C.Structure):
                 ("fixed", C.c_int64 * PLACE_MAX)]
 
 
+TRIPLE_MAX_POSES = 512         # PCP_TRIPLE_MAX_POSES: poses one pcp_place_triple call searches
+TRIPLE_TABLE_MAX_POSES = 128   # PCP_TRIPLE_TABLE_MAX_POSES: the dense [n][n][n] table's limit
+
 REFINE_MAX_MOVES = 64   # PCP_REFINE_MAX_MOVES: moves one pcp_place_refine call records at most
 
 
@@ -233,6 +236,11 @@ _SIGS = [
                                  _P, _P, _P]),
     ("pcp_place_pair_burst", C.c_int, [_P, _P, C.c_uint64, _P, C.POINTER(VlParams),
                                        C.POINTER(PairParams), C.c_int, C.POINTER(C.c_double)]),
+    ("pcp_place_triple", C.c_int, [_P, _P, C.c_uint64, _P, C.POINTER(VlParams),
+                                   C.POINTER(PairParams), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                   _P, _P, _P, _P, _P, _P, _P]),
+    ("pcp_place_triple_burst", C.c_int, [_P, _P, C.c_uint64, _P, C.POINTER(VlParams),
+                                         C.POINTER(PairParams), C.c_int, C.POINTER(C.c_double)]),
     ("pcp_place_refine", C.c_int, [_P, _P, C.c_uint64, _P, C.POINTER(VlParams),
                                    C.POINTER(RefineParams), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                    _P, _P, _P, _P, _P]),
@@ -1095,6 +1103,69 @@ class Context:
         self._check(self.lib.pcp_place_pair_burst(self.h, _ptr(poses), poses.shape[0], _ptr(zx),
                                                   C.byref(params), C.byref(pp), int(reps),
                                                   C.byref(ms)), "pcp_place_pair_burst")
+        return ms.value
+
+    def place_triple(self, poses5, zx120_pose5, params: VlParams, fixed=(),
+                     min_separation: float = 0.0, want_first: bool = False,
+                     want_triple_totals: bool = False, want_cells: bool = False,
+                     reserved: int = 0) -> dict:
+        """pcp_place_triple: the exact best triple of the poses beside zx120 and the `fixed` poses
+        (every admissible triple a < b < c evaluated; the lexicographically first maximum), with
+        the best pair, the best single pose and the base for comparison.  -> dict: n_selected (3:
+        the triple beats the pair, the single and the base; 2, 1, 0 as place_pair), best_triple
+        (3,), triple_total, triple_covered, best_pair (2,), pair_total, pair_covered, best_single,
+        single_total, single_covered, base_total, base_covered, and on request first_totals [P] /
+        first_partners [P, 2] (the best (b, c) of every first sensor a), triple_totals [P, P, P]
+        (-inf off the admissible a < b < c; P <= TRIPLE_TABLE_MAX_POSES), cell_score /
+        cell_owner [n_cells] of the answer."""
+        poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 5)
+        zx = np.ascontiguousarray(zx120_pose5, np.float64)
+        P = poses.shape[0]
+        pp = self._pair_params(fixed, min_separation, reserved)
+        bt3, bp = np.full(3, -1, np.int64), np.full(2, -1, np.int64)
+        tt, pt, st, bt = C.c_double(), C.c_double(), C.c_double(), C.c_double()
+        tc, pc, sc, bc, ns = (C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32())
+        bs = C.c_int64(-1)
+        n1 = max(P, 1) if P <= TRIPLE_MAX_POSES else 1   # (a refused call writes nothing)
+        ft = np.zeros(n1, np.float64) if want_first else None
+        fp = np.zeros((n1, 2), np.int64) if want_first else None
+        # (past the table's limit the call is refused: one entry stands for the argument)
+        nt = max(P, 1) if P <= TRIPLE_TABLE_MAX_POSES else 1
+        tab = np.zeros((nt, nt, nt), np.float64) if want_triple_totals else None
+        C_ = self.cells_count() if want_cells else 0
+        cs = np.zeros(max(C_, 1), np.float64) if want_cells else None
+        co = np.zeros(max(C_, 1), np.int32) if want_cells else None
+        self._check(self.lib.pcp_place_triple(
+            self.h, _ptr(poses) if P else None, P, _ptr(zx), C.byref(params), C.byref(pp),
+            _ptr(bt3), C.byref(tt), C.byref(tc), _ptr(bp), C.byref(pt), C.byref(pc),
+            C.byref(bs), C.byref(st), C.byref(sc), C.byref(bt), C.byref(bc), _ptr(ft), _ptr(fp),
+            _ptr(tab), _ptr(cs), _ptr(co), C.byref(ns)), "pcp_place_triple")
+        out = {"n_selected": ns.value, "best_triple": bt3, "triple_total": tt.value,
+               "triple_covered": tc.value, "best_pair": bp, "pair_total": pt.value,
+               "pair_covered": pc.value, "best_single": bs.value, "single_total": st.value,
+               "single_covered": sc.value, "base_total": bt.value, "base_covered": bc.value}
+        if want_first:
+            out["first_totals"] = ft[:P].copy()
+            out["first_partners"] = fp[:P].copy()
+        if want_triple_totals:
+            out["triple_totals"] = tab[:P, :P, :P].copy()
+        if want_cells:
+            out["cell_score"] = cs[:C_].copy()
+            out["cell_owner"] = co[:C_].copy()
+        return out
+
+    def place_triple_burst(self, poses5, zx120_pose5, params: VlParams, fixed=(),
+                           min_separation: float = 0.0, reps: int = 20) -> float:
+        """pcp_place_triple_burst -> ms per repetition of the triple phase (the pair phase it
+        builds on, the triple tiles, the rows' maxima and the selection; the scoring once before
+        the interval)."""
+        poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 5)
+        zx = np.ascontiguousarray(zx120_pose5, np.float64)
+        pp = self._pair_params(fixed, min_separation, 0)
+        ms = C.c_double(0.0)
+        self._check(self.lib.pcp_place_triple_burst(self.h, _ptr(poses), poses.shape[0], _ptr(zx),
+                                                    C.byref(params), C.byref(pp), int(reps),
+                                                    C.byref(ms)), "pcp_place_triple_burst")
         return ms.value
 
     @staticmethod

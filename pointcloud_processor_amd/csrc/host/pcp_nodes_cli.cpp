@@ -9,6 +9,8 @@
 //                         MAXD KMAX MINSEP OUT_SELECTED.i64 OUT_TOTALS.f64 OUT_REPORT.txt
 //   pcp_nodes_cli place_pair  (place's arguments; KMAX: the greedy placement it is compared with)
 //                         OUT_SELECTED: the exact answer; OUT_TOTALS: base, single, pair
+//   pcp_nodes_cli place_triple  (place's arguments; KMAX as for place_pair)
+//                         OUT_SELECTED: the exact answer; OUT_TOTALS: base, single, pair, triple
 //   pcp_nodes_cli place_refine  (place's arguments) [N_LOCKED [MAX_MOVES]]: KMAX sensors placed
 //                         greedily, then refined by single-sensor exchanges; OUT_SELECTED: the
 //                         refined set; OUT_TOTALS: start, final, then the total after each move
@@ -197,7 +199,7 @@ static int cmd_vlidar(Device &dev, char **a, int argc) {
 // one tick of the virtual-LiDAR node (vlidar's inputs), then KMAX mobile sensors placed greedily
 // among its candidates: the selected candidates, the totals after each and the placement's table
 static int cmd_place(Device &dev, char **a, bool exact_pair = false, bool refine = false,
-                     int argc = 16) {
+                     int argc = 16, bool exact_triple = false) {
     const auto t = read_file(a[0]), ax = read_file(a[2]), c = read_file(a[4]),
                nr = read_file(a[5]);
     const size_t tn = std::strtoull(a[1], nullptr, 10), an = std::strtoull(a[3], nullptr, 10),
@@ -251,6 +253,35 @@ static int cmd_place(Device &dev, char **a, bool exact_pair = false, bool refine
                     tick.candidates.size(), r.n_selected, (long long)r.pair[0],
                     (long long)r.pair[1], r.pair_covered, (long long)r.single, r.single_covered,
                     r.base_covered, r.total_cells);
+        return 0;
+    }
+    if (exact_triple) {
+        // place_triple: the exact best triple beside the greedy placement's first three (KMAX
+        // sensors placed greedily for the comparison); the chosen candidates, {base, single, pair,
+        // triple} totals and the triple table
+        if (placement.place_triple(dev, SimplifiedDualLidarOptimizer::Result{}, p).ran) return 3;
+        const auto greedy = placement.place(dev, tick, p);
+        const auto r = placement.place_triple(dev, tick, p, {}, greedy.ran ? &greedy : nullptr);
+        if (!r.ran) {
+            std::fprintf(stderr, "place_triple: %s\n", placement.lastError().c_str());
+            return 1;
+        }
+        std::vector<int64_t> sel;
+        if (r.n_selected == 3) sel = {r.triple[0], r.triple[1], r.triple[2]};
+        if (r.n_selected == 2) sel = {r.pair[0], r.pair[1]};
+        if (r.n_selected == 1) sel = {r.single};
+        const double tot[4] = {r.base_total, r.single_total, r.pair_total, r.triple_total};
+        write_file(a[13], sel.data(), sel.size() * 8);
+        write_file(a[14], tot, sizeof(tot));
+        write_file(a[15], r.log.data(), r.log.size());
+        std::printf("{\"n_candidates\": %zu, \"n_selected\": %d, \"best_triple\": [%lld, %lld, "
+                    "%lld], \"triple_covered\": %d, \"best_pair\": [%lld, %lld], "
+                    "\"pair_covered\": %d, \"best_single\": %lld, \"single_covered\": %d, "
+                    "\"base_covered\": %d, \"total_cells\": %d}\n",
+                    tick.candidates.size(), r.n_selected, (long long)r.triple[0],
+                    (long long)r.triple[1], (long long)r.triple[2], r.triple_covered,
+                    (long long)r.pair[0], (long long)r.pair[1], r.pair_covered, (long long)r.single,
+                    r.single_covered, r.base_covered, r.total_cells);
         return 0;
     }
     if (refine) {
@@ -750,7 +781,7 @@ int main(int argc, char **argv) {
         if (!hp || std::atoi(hp) != 0) setenv("HSA_ENABLE_INTERRUPT", "0", 0);
     }
     if (argc < 2) {
-        std::fprintf(stderr, "usage: pcp_nodes_cli filter|merge|vlidar|place|place_pair|place_refine|scan|scan_mounted|area|drivable|replay ...\n");
+        std::fprintf(stderr, "usage: pcp_nodes_cli filter|merge|vlidar|place|place_pair|place_triple|place_refine|scan|scan_mounted|area|drivable|replay ...\n");
         return 2;
     }
     const std::string cmd = argv[1];
@@ -759,6 +790,7 @@ int main(int argc, char **argv) {
                      : cmd == "vlidar" ? 14
                      : cmd == "place"  ? 16
                      : cmd == "place_pair" ? 16
+                     : cmd == "place_triple" ? 16
                      : cmd == "place_refine" ? 16
                      : cmd == "scan"   ? 10
                      : cmd == "scan_mounted" ? 11
@@ -777,6 +809,9 @@ int main(int argc, char **argv) {
         if (cmd == "vlidar") return cmd_vlidar(dev, argv + 2, argc - 2);
         if (cmd == "place") return cmd_place(dev, argv + 2);
         if (cmd == "place_pair") return cmd_place(dev, argv + 2, /*exact_pair=*/true);
+        if (cmd == "place_triple")
+            return cmd_place(dev, argv + 2, /*exact_pair=*/false, /*refine=*/false, 16,
+                             /*exact_triple=*/true);
         if (cmd == "place_refine")
             return cmd_place(dev, argv + 2, /*exact_pair=*/false, /*refine=*/true, argc - 2);
         if (cmd == "scan") return cmd_scan(dev, argv + 2);

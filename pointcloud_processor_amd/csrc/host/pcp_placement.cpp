@@ -188,6 +188,126 @@ MobileLidarPlacement::PairResult MobileLidarPlacement::place_pair(
     return r;
 }
 
+std::string placement_triple_log(const MobileLidarPlacement::TripleResult &r,
+                                 const MobileLidarPlacement::Result *greedy) {
+    std::string log;
+    const int tc = r.total_cells;
+    auto pct = [tc](int v) { return tc > 0 ? (double)v / tc * 100.0 : 0.0; };
+    const char *rule = "========================================";
+    const char *thin = "----------------------------------------";
+    appendf(log, "%s", rule);
+    appendf(log, "Exact Triple Placement (ZX120 + %d Fixed + %d Mobile)", r.n_fixed, r.n_selected);
+    appendf(log, "%s", rule);
+    appendf(log, "Total Score (ZX120%s): %.2f", r.n_fixed ? " + fixed" : " only", r.base_total);
+    appendf(log, "  Covered cells: %d of %d (%.1f%%)", r.base_covered, tc, pct(r.base_covered));
+    appendf(log, "%s", thin);
+    if (r.single >= 0) {
+        const auto &p = r.single_pos;
+        appendf(log, "Best Single Position: (%.2f, %.2f, %.2f)  [candidate %lld]", p.x, p.y, p.z,
+                (long long)r.single);
+        appendf(log, "  Total Score: %.2f (gain %.2f)", r.single_total,
+                r.single_total - r.base_total);
+        appendf(log, "  Covered cells: %d of %d (%.1f%%)", r.single_covered, tc,
+                pct(r.single_covered));
+    } else {
+        appendf(log, "Best Single Position: none admissible");
+    }
+    appendf(log, "%s", thin);
+    if (r.pair[0] >= 0) {
+        for (int i = 0; i < 2; ++i) {
+            const auto &p = r.pair_pos[i];
+            appendf(log, "Best Pair LiDAR %d Position: (%.2f, %.2f, %.2f)  [candidate %lld]", i + 1,
+                    p.x, p.y, p.z, (long long)r.pair[i]);
+        }
+        appendf(log, "  Total Score: %.2f (gain over single %.2f)", r.pair_total,
+                r.pair_total - r.single_total);
+        appendf(log, "  Covered cells: %d of %d (%.1f%%)", r.pair_covered, tc,
+                pct(r.pair_covered));
+    } else {
+        appendf(log, "Best Pair: no admissible pair");
+    }
+    appendf(log, "%s", thin);
+    if (r.triple[0] >= 0) {
+        for (int i = 0; i < 3; ++i) {
+            const auto &p = r.triple_pos[i];
+            appendf(log, "Best Triple LiDAR %d Position: (%.2f, %.2f, %.2f)  [candidate %lld]",
+                    i + 1, p.x, p.y, p.z, (long long)r.triple[i]);
+        }
+        appendf(log, "  Total Score: %.2f (gain over pair %.2f)", r.triple_total,
+                r.triple_total - r.pair_total);
+        appendf(log, "  Covered cells: %d of %d (%.1f%%)", r.triple_covered, tc,
+                pct(r.triple_covered));
+        if (greedy && greedy->ran && greedy->rounds.size() >= 3)
+            appendf(log,
+                    "  Greedy triple [candidates %lld, %lld, %lld]: %.2f (exact triple gains %.2f)",
+                    (long long)greedy->rounds[0].candidate, (long long)greedy->rounds[1].candidate,
+                    (long long)greedy->rounds[2].candidate, greedy->rounds[2].total,
+                    r.triple_total - greedy->rounds[2].total);
+    } else {
+        appendf(log, "Best Triple: no admissible triple");
+    }
+    appendf(log, "%s", rule);
+    return log;
+}
+
+MobileLidarPlacement::TripleResult MobileLidarPlacement::place_triple(
+    Device &dev, const SimplifiedDualLidarOptimizer::Result &tick,
+    const SimplifiedDualLidarOptimizer::Params &vl, const std::vector<int64_t> &fixed,
+    const Result *greedy) {
+    TripleResult r;
+    err_.clear();
+    if (!tick.ran) return r;
+    if (fixed.size() > PCP_PLACE_MAX) {
+        err_ = "place_triple: more fixed sensors than PCP_PLACE_MAX";
+        return r;
+    }
+    const double zx[5] = {tick.zx120.x, tick.zx120.y, tick.zx120.z, tick.zx120.pitch,
+                          tick.zx120.yaw};
+    const pcp_vl_params p{vl.grid_resolution, vl.sensor_height, vl.search_radius, vl.max_distance,
+                          vl.num_candidates,  vl.vertical_layers};
+    pcp_pair_params pp{};
+    pp.n_fixed = (int32_t)fixed.size();
+    pp.min_separation = p_.min_separation;
+    for (size_t i = 0; i < fixed.size(); ++i) pp.fixed[i] = fixed[i];
+    const size_t n = tick.candidates.size();
+    std::vector<double> poses(5 * n);
+    for (size_t i = 0; i < n; ++i) {
+        const auto &c = tick.candidates[i];
+        poses[5 * i] = c.x;
+        poses[5 * i + 1] = c.y;
+        poses[5 * i + 2] = c.z;
+        poses[5 * i + 3] = c.pitch;
+        poses[5 * i + 4] = c.yaw;
+    }
+    if (pcp_place_triple(dev.ctx(), poses.data(), n, zx, &p, &pp, r.triple, &r.triple_total,
+                         &r.triple_covered, r.pair, &r.pair_total, &r.pair_covered, &r.single,
+                         &r.single_total, &r.single_covered, &r.base_total, &r.base_covered,
+                         nullptr, nullptr, nullptr, nullptr, nullptr, &r.n_selected) != PCP_OK) {
+        err_ = dev.error();
+        return r;
+    }
+    r.ran = true;
+    r.n_fixed = pp.n_fixed;
+    r.total_cells = tick.report.total_cells;
+    if (r.single >= 0) {
+        r.single_pos = tick.candidates[(size_t)r.single];
+        r.single_pos.total_score = r.single_total;
+    }
+    for (int i = 0; i < 2 && r.pair[0] >= 0; ++i) {
+        r.pair_pos[i] = tick.candidates[(size_t)r.pair[i]];
+        r.pair_pos[i].total_score = r.pair_total;
+    }
+    for (int i = 0; i < 3 && r.triple[0] >= 0; ++i) {
+        r.triple_pos[i] = tick.candidates[(size_t)r.triple[i]];
+        r.triple_pos[i].total_score = r.triple_total;
+    }
+    if (r.n_selected == 3) r.placed = {r.triple_pos[0], r.triple_pos[1], r.triple_pos[2]};
+    if (r.n_selected == 2) r.placed = {r.pair_pos[0], r.pair_pos[1]};
+    if (r.n_selected == 1) r.placed = {r.single_pos};
+    r.log = placement_triple_log(r, greedy);
+    return r;
+}
+
 std::string placement_refine_log(const MobileLidarPlacement::RefineResult &r) {
     std::string log;
     const int tc = r.total_cells;

@@ -69,6 +69,37 @@ class MobileLidarPlacement {
                           const SimplifiedDualLidarOptimizer::Params &vl,
                           const std::vector<int64_t> &fixed = {}, const Result *greedy = nullptr);
 
+    // The exact best triple (pcp_place_triple): every triple of the tick's candidates evaluated
+    // beside zx120 and the `fixed` candidates, with the best pair, the best single and the base it
+    // is compared with.
+    struct TripleResult {
+        bool ran = false;              // false: the tick did not run, or the call failed
+        int32_t n_selected = 0;        // 3: the triple beats the pair, the single and the base;
+                                       // 2, 1, 0: as PairResult
+        int64_t triple[3] = {-1, -1, -1};   // candidate indices, a < b < c; -1: no admissible triple
+        double triple_total = 0;
+        int32_t triple_covered = 0;
+        int64_t pair[2] = {-1, -1};
+        double pair_total = 0;
+        int32_t pair_covered = 0;
+        int64_t single = -1;
+        double single_total = 0;
+        int32_t single_covered = 0;
+        double base_total = 0;         // zx120 and the fixed sensors alone
+        int32_t base_covered = 0;
+        int32_t n_fixed = 0;
+        int32_t total_cells = 0;
+        std::vector<SimplifiedDualLidarOptimizer::LidarPosition> placed;   // the n_selected chosen
+        SimplifiedDualLidarOptimizer::LidarPosition triple_pos[3], pair_pos[2], single_pos;
+        std::string log;
+    };
+    // min_separation is params()'s; num_mobile_lidars plays no part.  greedy (nullable): a
+    // place() result for the same tick, whose first three sensors the log compares the triple with
+    TripleResult place_triple(Device &dev, const SimplifiedDualLidarOptimizer::Result &tick,
+                              const SimplifiedDualLidarOptimizer::Params &vl,
+                              const std::vector<int64_t> &fixed = {},
+                              const Result *greedy = nullptr);
+
     // 1-exchange refinement (pcp_place_refine): the set `start` of the tick's candidates -- a
     // place() answer, or a deployment as it stands -- improved by moving one sensor at a time to
     // the candidate that raises the total most, until no single move raises it.
@@ -113,6 +144,11 @@ std::string placement_log(const MobileLidarPlacement::Result &r);
 // gain over the single, and (greedy given, two sensors placed) its gain over greedy's two
 std::string placement_pair_log(const MobileLidarPlacement::PairResult &r,
                                const MobileLidarPlacement::Result *greedy = nullptr);
+// the triple search's table in the same format: the base, the best single, the best pair and the
+// best triple with its gain over the pair, and (greedy given, three sensors placed) its gain over
+// greedy's three
+std::string placement_triple_log(const MobileLidarPlacement::TripleResult &r,
+                                 const MobileLidarPlacement::Result *greedy = nullptr);
 // the refinement's table in the same format: the start set, every move (slot, from and to with
 // their positions, the gain), and either "1-exchange optimal" or "stopped after N moves"
 std::string placement_refine_log(const MobileLidarPlacement::RefineResult &r);

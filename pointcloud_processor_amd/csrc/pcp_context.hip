@@ -784,6 +784,8 @@ void pcp_destroy(pcp_ctx *ctx) {
     ctx->refine_d.release();
     ctx->refine_m.release();
     ctx->refine_host.release();
+    ctx->triple_d.release();
+    ctx->triple_host.release();
     ctx->vscan_d.release();
     ctx->vscan_host.release();
     if (ctx->area_stream) (void)hipStreamDestroy(ctx->area_stream);

@@ -367,6 +367,11 @@ struct pcp_ctx {
     // (refine_m), and the pinned landing of its one download (its own, as the pair's)
     pcp::DevBuf refine_d, refine_m;
     pcp::PinnedBuf refine_host;
+    // pcp_place_triple (pcp_triples.hip): its state, cell_score / cell_owner, the per-first-sensor
+    // bests, the blocks' bests and the dense triple table (triple_d), and the pinned landing of its
+    // one download; its pair phase runs in pair_d / pair_m, which no call reads across calls
+    pcp::DevBuf triple_d;
+    pcp::PinnedBuf triple_host;
     // pcp_simulate_scan (pcp_scan.hip): wave bases, offsets, records, dense images, point mask and
     // counts, and the pinned landing of its downloads (its own: the fan's buffers stay as
     // pcp_raycast_fan leaves and expects them)

@@ -1,5 +1,6 @@
-// What the placement calls share (pcp_place_sensors, pcp_place_pair, pcp_place_refine:
-// pcp_place.hip, pcp_pairs.hip, pcp_refine.hip): the first-maximum order, the
+// What the placement calls share (pcp_place_sensors, pcp_place_pair, pcp_place_refine,
+// pcp_place_triple: pcp_place.hip, pcp_pairs.hip, pcp_refine.hip, pcp_triples.hip; DESIGN.md
+// §6h/§6i/§6k): the first-maximum order, the
 // ordered walk of a staged chunk, the last-block ticket, the one-lane ordered total, the fold with
 // owners, the separation test, the front of the calls' blocks and the timing entries' scaffold.
 // The first part is plain C++ (no HIP dependency): tests/native/place_shared_selftest.cpp builds
