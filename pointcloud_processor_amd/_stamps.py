@@ -15,12 +15,12 @@ CSRC = ROOT / "pointcloud_processor_amd" / "csrc"
 _COMMON = ["pcp_internal.hpp", "Makefile", "../../include/pcp_abi.h"]
 # the sources each profiled workload's kernels are compiled from
 WORKLOAD_SOURCES = {
-    "fan": ["pcp_vlidar.hip", "pcp_fine.hip", "pcp_index.hip", "pcp_stencil.hpp",
+    "fan": ["pcp_fan.hip", "pcp_march.hpp", "pcp_fine.hip", "pcp_index.hip", "pcp_stencil.hpp",
             "pcp_grid.hpp", "pcp_fan_band.hpp", "pcp_fan_clear.hpp", "pcp_fan_clip.hpp",
             "pcp_fan_pivot.hpp", "pcp_fan_row.hpp"] + _COMMON,
     "filter": ["pcp_filter.hip", "pcp_rigid.hpp"] + _COMMON,
     # reference mode (k_score_cells: the same march over the same terrain copy)
-    "cells": ["pcp_vlidar.hip", "pcp_fine.hip", "pcp_index.hip", "pcp_stencil.hpp",
+    "cells": ["pcp_score.hip", "pcp_march.hpp", "pcp_fine.hip", "pcp_index.hip", "pcp_stencil.hpp",
               "pcp_grid.hpp", "pcp_fan_band.hpp", "pcp_fan_clear.hpp", "pcp_fan_clip.hpp",
               "pcp_fan_pivot.hpp", "pcp_fan_row.hpp"] + _COMMON,
 }

@@ -241,6 +241,42 @@ std::vector<double> step_table(double end) {
     return s;
 }
 
+// PCP_MAX_STEPS (include/pcp_abi.h): a longer table is refused before anything is launched,
+// whether or not first hits are asked for.  A table certainly past the bound is not even built
+// (s_k = 0.5 + 0.3 k to ~1e-9 at these k); the sample in doubt is settled by counting.  The
+// cached table has passed already.
+int steps_within_bound(pcp_ctx *ctx, double end) {
+    if (ctx->steps_end == end) return PCP_OK;
+    if (end > 0.5 + kRayStep * (double)(PCP_MAX_STEPS + 1) ||
+        step_table(end).size() > (size_t)PCP_MAX_STEPS)
+        return set_err(ctx, PCP_E_INVALID,
+                       "max_distance %.17g: the march's step table would pass PCP_MAX_STEPS = %d "
+                       "samples", end + kVisRadius, PCP_MAX_STEPS);
+    return PCP_OK;
+}
+
+// (a refused table leaves the cached one as it was)
+int ensure_steps(pcp_ctx *ctx, double end, int *K) {
+    if (ctx->steps_end == end) {
+        *K = ctx->steps_K;
+        return PCP_OK;
+    }
+    if (int rc = steps_within_bound(ctx, end)) return rc;
+    std::vector<double> s = step_table(end);
+    PCP_HIP(ctx, ctx->steps_d.ensure((s.size() + 1) * sizeof(double)));
+    if (!s.empty()) {
+        PCP_HIP(ctx, hipMemcpyAsync(ctx->steps_d.p, s.data(), s.size() * sizeof(double),
+                                    hipMemcpyHostToDevice, ctx->stream));
+        PCP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    ctx->steps_end = end;
+    ctx->steps_K = (int)s.size();
+    ctx->steps_first = s.empty() ? 0.0 : s.front();
+    ctx->steps_last = s.empty() ? 0.0 : s.back();
+    *K = ctx->steps_K;
+    return PCP_OK;
+}
+
 // ---- profiling -------------------------------------------------------------------------
 static hipEvent_t take_event(pcp_ctx *ctx) {
     if (!ctx->event_pool.empty()) {

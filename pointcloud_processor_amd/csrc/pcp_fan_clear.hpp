@@ -1,6 +1,6 @@
 // Clearance codes of the fine copy's empty probe records and the march's jump over them
 // ("Skip 5").  Plain C++ with no HIP dependency: pcp_fine.hip builds the codes and
-// pcp_vlidar.hip's march reads them through these functions, and
+// pcp_march.hpp's march reads them through these functions, and
 // tests/native/fan_clear_selftest.cpp checks the rule stand-alone.
 //
 // The record of (fine cell w, coarse corner iz) is empty (0x00FF: low byte 255, no sample passes

@@ -1,6 +1,6 @@
 // The march's clip interval ("Skip 3"): the samples k of a ray p + d s_k,
 // s_k = 0.5 + 0.3 k, that can lie inside the terrain's clip box.  Plain C++ with no HIP
-// dependency: pcp_vlidar.hip's clip_kf calls fan_clip with the device's approximate reciprocals,
+// dependency: pcp_march.hpp's clip_kf calls fan_clip with the device's approximate reciprocals,
 // tests/native/fan_clip_selftest.cpp checks the rule stand-alone with exact and perturbed ones.
 //
 // The rule.  Slab times in float, t0 = max over the axes of the entry time (and 0), t1 = min of

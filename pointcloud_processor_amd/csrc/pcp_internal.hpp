@@ -554,7 +554,7 @@ int exclusive_scan_u32_pair(pcp_ctx *ctx, const uint32_t *in_a, uint32_t *out_a,
                             uint32_t *out2_a, const uint32_t *in_b, uint32_t *out_b, uint64_t n_b,
                             uint32_t *out2_b, void *tmp, bool zero2);
 
-// fan query up to the per-pose sums, enqueued on ctx->stream (pcp_vlidar.hip): device results
+// fan query up to the per-pose sums, enqueued on ctx->stream (pcp_fan.hip): device results
 // in flight on return, the caller synchronizes.  n > 0.
 struct FanEnq {
     // input (pcp_raycast_fan_allreduce): k_fan_reduce also writes the one-collective vector --
@@ -606,7 +606,7 @@ int fan_enqueue(pcp_ctx *ctx, const double *poses5, uint64_t n, const pcp_fan_pa
 int fan_el_table_check(pcp_ctx *ctx, const char *what, const pcp_fan_params *fan,
                        const double *el_table);
 
-// runOptimization's scoring up to the per-pose sums, enqueued on ctx->stream (pcp_vlidar.hip)
+// runOptimization's scoring up to the per-pose sums, enqueued on ctx->stream (pcp_score.hip)
 struct ScoreEnq {
     int P = 0, C = 0;
     double *comb = nullptr;        // [P][C] mobile scores
@@ -641,7 +641,8 @@ int score_enqueue(pcp_ctx *ctx, const double *poses5, uint64_t n, const double z
                   const pcp_vl_params *p, ScoreEnq &o, const uint8_t *cell_flags = nullptr,
                   bool fuse_tail = false, bool zc = false, const uint32_t *P_dev = nullptr,
                   const double *poses_dev = nullptr);
-// key kernels of the pose-sharded search (pcp_vlidar.hip; used by pcp_multi.hip)
+// key kernels of the pose-sharded search (pcp_score.hip, launch_fan_keys: pcp_fan.hip; used by
+// pcp_multi.hip)
 // identity: the value of the other ranks' slots (~0 for ncclUint64 MIN, INT64_MAX for a signed
 // int64 MIN as torch.distributed reduces it)
 void launch_fan_keys(hipStream_t st, const uint32_t *blocked_d, uint32_t lo, uint32_t cnt,
@@ -737,5 +738,34 @@ float exit_dist(float r2);
 void fan_tables(int32_t n_az, int32_t n_el, double el_min, double el_max, double *ca,
                 double *sa, double *ce, double *se);
 std::vector<double> step_table(double end);
+// the context's device copy of step_table(end), cached by its end (the scoring and the fan share
+// it): *K = its length.  A table past PCP_MAX_STEPS is refused, steps_within_bound alone says so
+// before anything is launched
+int steps_within_bound(pcp_ctx *ctx, double end);
+int ensure_steps(pcp_ctx *ctx, double end, int *K);
+
+// The timing entries: warm() once untimed (the phase's first touches), then body() reps times
+// between two events on st; *ms = the time per repetition.
+template <class Warm, class Body>
+int time_reps(pcp_ctx *ctx, const char *what, hipStream_t st, int reps, Warm warm, Body body,
+              double *ms) {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    PCP_HIP(ctx, hipEventCreate(&e0));
+    PCP_HIP(ctx, hipEventCreate(&e1));
+    int rc = warm();
+    hipError_t e = rc ? hipSuccess : hipEventRecord(e0, st);
+    for (int r = 0; r < reps && !rc && e == hipSuccess; ++r) rc = body();
+    if (!rc && e == hipSuccess) e = hipEventRecord(e1, st);
+    if (!rc && e == hipSuccess) e = hipEventSynchronize(e1);
+    float t = 0.0f;
+    if (!rc && e == hipSuccess) e = hipEventElapsedTime(&t, e0, e1);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    if (rc) return rc;
+    if (e != hipSuccess) return hip_fail(ctx, e, what, __FILE__, __LINE__);
+    *ms = (double)t / reps;
+    prof_resolve(ctx);
+    return PCP_OK;
+}
 
 }  // namespace pcp

@@ -1,7 +1,7 @@
 // pcp_multi.hip -- one process, n GPUs: the virtual-LiDAR pose search sharded over devices
 // (SURVEY.md §8b `pcp_multi_create`, §8e).  Host code only (the key kernels live in
-// pcp_vlidar.hip): n contexts, one RCCL communicator over them (ncclCommInitAll), poses
-// partitioned contiguously (rank r takes [r*P/n, (r+1)*P/n), the first P % n ranks one more),
+// pcp_score.hip and pcp_fan.hip): n contexts, one RCCL communicator over them
+// (ncclCommInitAll), poses partitioned contiguously (rank r takes [r*P/n, (r+1)*P/n), the first P % n ranks one more),
 // the terrain index replicated, and ONE collective per query:
 //   fan:            ncclAllReduce(ncclUint64, ncclMin) over P keys (blocked << 32) | pose
 //   reference mode: ncclAllReduce(ncclUint64, ncclMax) over [P totals | P covered | 3 x C

@@ -65,7 +65,7 @@ k_place_init(const double *__restrict__ score_z, int C, int P, const double *__r
 }
 
 // One placement round.  Blocks of kPRows rows laid out as the scoring's row sums
-// (row_group_body, pcp_vlidar.hip): waves 1..3 load chunks of kPCh cells of the block's rows and
+// (row_group_body, pcp_score.hip): waves 1..3 load chunks of kPCh cells of the block's rows and
 // of base (coalesced, two register sets two chunks ahead), form max(base, S) with the
 // reference's std::max, x > 0 ? x : +0.0 and the covered counts, and stage the values in a ring
 // of three LDS buffers; lane r of wave 0 walks row r of each chunk in cell order, one dependent

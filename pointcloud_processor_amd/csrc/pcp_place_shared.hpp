@@ -2,7 +2,8 @@
 // pcp_place_triple: pcp_place.hip, pcp_pairs.hip, pcp_refine.hip, pcp_triples.hip; DESIGN.md
 // §6h/§6i/§6k): the first-maximum order, the
 // ordered walk of a staged chunk, the last-block ticket, the one-lane ordered total, the fold with
-// owners, the separation test, the front of the calls' blocks and the timing entries' scaffold.
+// owners, the separation test and the front of the calls' blocks (the timing entries' scaffold,
+// time_reps, is pcp_internal.hpp's: the scoring and the fan time their bursts with it too).
 // The first part is plain C++ (no HIP dependency): tests/native/place_shared_selftest.cpp builds
 // it with the host compiler.
 #pragma once
@@ -250,30 +251,6 @@ inline int check_pose_list(pcp_ctx *ctx, const char *what, const char *name, con
         return set_err(ctx, PCP_E_INVALID, "%s: pose %lld is %s twice", what, (long long)list[i],
                        twice);
     for (i = 0; i < count; ++i) idx[i] = (int32_t)list[i];
-    return PCP_OK;
-}
-
-// The timing entries: warm() once untimed (the phase's first touches), then body() reps times
-// between two events on st; *ms = the time per repetition.
-template <class Warm, class Body>
-int time_reps(pcp_ctx *ctx, const char *what, hipStream_t st, int reps, Warm warm, Body body,
-              double *ms) {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    PCP_HIP(ctx, hipEventCreate(&e0));
-    PCP_HIP(ctx, hipEventCreate(&e1));
-    int rc = warm();
-    hipError_t e = rc ? hipSuccess : hipEventRecord(e0, st);
-    for (int r = 0; r < reps && !rc && e == hipSuccess; ++r) rc = body();
-    if (!rc && e == hipSuccess) e = hipEventRecord(e1, st);
-    if (!rc && e == hipSuccess) e = hipEventSynchronize(e1);
-    float t = 0.0f;
-    if (!rc && e == hipSuccess) e = hipEventElapsedTime(&t, e0, e1);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (rc) return rc;
-    if (e != hipSuccess) return hip_fail(ctx, e, what, __FILE__, __LINE__);
-    *ms = (double)t / reps;
-    prof_resolve(ctx);
     return PCP_OK;
 }
 

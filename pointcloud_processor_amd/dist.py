@@ -15,7 +15,7 @@ Each position of the vector is written by exactly one rank, so MIN/MAX reduction
 The GPU path's reference mode reduces a wider vector in ONE collective
 (pcp_score_poses_allreduce / pcp_multi_score_poses): [P totals | P covered | 3 x C newest-pose
 flag keys | health].  `score_keys` and `flags_from_keys` restate its two kernels (k_score_keys,
-k_flags_from_keys in pcp_vlidar.hip) on the host, so the gloo tests can check that one rank's
+k_flags_from_keys in pcp_score.hip) on the host, so the gloo tests can check that one rank's
 vector per shard, reduced by MAX, is the single-process vector and resolves to the reference's
 stale GridCell flags (virtual_lidar.cpp:480-519).  `dist_mod` is torch.distributed (gloo: the CPU tests) or a
 hostgroup.HostGroup (bench.py's ranks, whose processes never import torch); the GPU data path's

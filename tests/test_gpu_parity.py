@@ -839,7 +839,7 @@ def test_raycast_fan_stamps_mode(oracle):
 def test_raycast_fan_far_from_origin(oracle, scene, cells, dz, skip, monkeypatch):
     """The terrain and the poses shifted by kilometres in z, where float spacing (~2.4e-4 m)
     exceeds the fixed 1e-4 m margins: the split-record walk skip widens its margin with |z|
-    (pcp_vlidar.hip), so first hits, blocked counts and ray-hit tests stay exact on the
+    (pcp_march.hpp), so first hits, blocked counts and ray-hit tests stay exact on the
     fine-window copy (built at the first query), with one or two skip thresholds."""
     monkeypatch.setenv("PCP_TERRAIN_BLOCKS", "2")
     monkeypatch.setenv("PCP_FINE_SKIP", skip)

@@ -1,7 +1,7 @@
-"""VALU lines per region of the production fan kernel, from the device assembly of pcp_vlidar.hip
+"""VALU lines per region of the production fan kernel, from the device assembly of pcp_fan.hip
 (hipcc with the Makefile's FLAGS plus --cuda-device-only -S; it cross-compiles without a GPU).
 
-    python tools/fan_valu_regions.py vlidar.s [MANGLED_KERNEL_NAME]
+    python tools/fan_valu_regions.py fan.s [MANGLED_KERNEL_NAME]
 
 Regions by the compiler's own loop comments: the pose loop is the kernel's depth-1 loop that holds
 a depth-2 loop (the probe loop), whose depth-3 loops are the walks.  Inside the probe loop the

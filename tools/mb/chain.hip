@@ -1,4 +1,4 @@
-// Dependent f64 add latency on gfx950 (the row-sum chain floor, pcp_vlidar.hip row_group_body).
+// Dependent f64 add latency on gfx950 (the row-sum chain floor, pcp_score.hip row_group_body).
 // hipcc --offload-arch=gfx950 -O3 -o chain chain.hip; measured: ~6 clocks per dependent
 // v_add_f64, 2.6 ns wall per add on one wave with 4 or 16 active lanes.
 #include <hip/hip_runtime.h>

@@ -1,7 +1,7 @@
 // Ceiling of divergent lane-loads on gfx950 -- the bound the fan kernel's roofline is quoted
 // against (bench.py _fan_roofline; profiles/r05_gather_ceiling.json via tools/gather_ceiling.sh).
 //
-// The fan kernel (pcp_vlidar.hip k_raycast_fan_xcd) is one wave per workgroup, 8 waves per SIMD,
+// The fan kernel (pcp_fan.hip k_raycast_fan_xcd) is one wave per workgroup, 8 waves per SIMD,
 // and every lane of its probe / walk-start / point-record loads reads its own cache line: 2-byte
 // z-band thresholds, 4-byte walk starts, 12-byte (x, y, z) window entries, each lane's next
 // address depending on what it loaded before (a probe decides the walk, a walk entry the next).
