@@ -406,7 +406,13 @@ void orc_excavate(const float *pts, int64_t n, int64_t stride_floats, const orc_
                   const double t[3], const double q[4], uint8_t *keep, float *surf,
                   int64_t cap_surf, int64_t *n_surf, float *area, int64_t cap_area,
                   int64_t *n_area, double pose_out[4]) {
-    /* tf2::Matrix3x3::setRotation (quaternion x, y, z, w) and Transform * (ox, oy, 0) */
+    /* tf2::Matrix3x3::setRotation (quaternion x, y, z, w) and Transform * (ox, oy, 0).
+     * One known difference: the reference reads getRPY from Matrix3x3(zx120_tf.getRotation()),
+     * the matrix -> quaternion -> matrix round trip of excavated_surface_generator.cpp:298-301;
+     * here (as in the library and tests/carve_cases.py) it is read from this matrix, built from
+     * the message quaternion.  The yaw can differ from the reference's in its last bits even
+     * for a pure yaw; getRotation is not restated, and how often that reaches an output float
+     * is not measured. */
     const double qx = q[0], qy = q[1], qz = q[2], qw = q[3];
     const double d = qx * qx + qy * qy + qz * qz + qw * qw;
     const double s = 2.0 / d;

@@ -430,6 +430,11 @@ static int excavate_impl(pcp_ctx *ctx, const pcp_cloud_view *in, const pcp_excav
     ProfScope prof(ctx, PCP_K_EXCAVATE);
     hipStream_t st = ctx->stream;
     // ---- pose: tf2 Transform * (offset_x, offset_y, 0), Matrix3x3::getRPY (solution 1)
+    // One known difference: the reference reads getRPY from Matrix3x3(zx120_tf.getRotation()),
+    // the matrix -> quaternion -> matrix round trip of excavated_surface_generator.cpp:298-301;
+    // here (as in the oracle and tests/carve_cases.py) it is read from the message quaternion's
+    // matrix.  The yaw can differ from the reference's in its last bits even for a pure yaw;
+    // getRotation is not restated, and how often that reaches an output float is not measured.
     const double qx = zx120_base->q[0], qy = zx120_base->q[1], qz = zx120_base->q[2],
                  qw = zx120_base->q[3];
     const double d = qx * qx + qy * qy + qz * qz + qw * qw;
