@@ -12,7 +12,7 @@ from pathlib import Path
 
 ROOT = Path(__file__).resolve().parents[1]
 CSRC = ROOT / "pointcloud_processor_amd" / "csrc"
-_COMMON = ["pcp_internal.hpp", "Makefile", "../../include/pcp_abi.h"]
+_COMMON = ["pcp_internal.hpp", "pcp_knobs.hpp", "Makefile", "../../include/pcp_abi.h"]
 # the sources each profiled workload's kernels are compiled from
 WORKLOAD_SOURCES = {
     "fan": ["pcp_fan.hip", "pcp_march.hpp", "pcp_fine.hip", "pcp_index.hip", "pcp_stencil.hpp",

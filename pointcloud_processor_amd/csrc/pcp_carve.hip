@@ -560,7 +560,7 @@ static int excavate_impl(pcp_ctx *ctx, const pcp_cloud_view *in, const pcp_excav
         if (xl && ctx->tc_host.p && d0 >= l0 && d0 + raw_b <= l0 + ctx->tc_host.cap) {
             raw = static_cast<const unsigned char *>(in->data);
             raw_copy = ctx->stage.as<unsigned char>();
-            if (!ctx->carve_fuse_copy) {   // (A/B: the copy launch first)
+            if (!ctx->knob.carve_fuse_copy) {   // (A/B: the copy launch first)
                 if (int rc0 = copy_pinned_async(ctx, raw_copy, raw, raw_b, st)) return rc0;
                 raw = raw_copy;
                 raw_copy = nullptr;
@@ -619,7 +619,7 @@ static int excavate_impl(pcp_ctx *ctx, const pcp_cloud_view *in, const pcp_excav
     // the records: straight into pinned memory for message-sized results (the kernels store
     // them there, no D2H copy), else a device buffer copied out
     const size_t land_b = (n + nsurf + narea) * 32;
-    const bool land = (ctx->zc_in && land_b <= kPinDirectMax * 8) || (xl && xl->keep);
+    const bool land = (ctx->knob.zc_in && land_b <= kPinDirectMax * 8) || (xl && xl->keep);
     float4 *kept;
     if (land && xl) {
         PCP_HIP(ctx, ctx->exc_land.ensure(land_b + 256));

@@ -31,8 +31,6 @@ void comm_release(pcp_ctx *ctx) {
         if (e) (void)hipEventDestroy(e);
         e = nullptr;
     }
-    ctx->comm_keys.release();
-    ctx->comm_host.release();
 }
 }  // namespace pcp
 

@@ -8,7 +8,6 @@
 #include <cstring>
 #include <new>
 
-#include "pcp_fan_clip.hpp"
 #include "pcp_internal.hpp"
 
 namespace pcp {
@@ -94,7 +93,7 @@ int copy_pinned_async(pcp_ctx *ctx, void *dst_d, const void *src_pinned, size_t 
                       hipStream_t st) {
     if (!bytes) return PCP_OK;
     // both 16-byte aligned (device allocations and pinned slots are; offsets are the caller's)
-    if (!ctx->copy_kernel || (((uintptr_t)dst_d | (uintptr_t)src_pinned) & 15u)) {
+    if (!ctx->knob.copy_kernel || (((uintptr_t)dst_d | (uintptr_t)src_pinned) & 15u)) {
         PCP_HIP(ctx, hipMemcpyAsync(dst_d, src_pinned, bytes, hipMemcpyHostToDevice, st));
         return PCP_OK;
     }
@@ -110,7 +109,7 @@ int copy_pinned_async(pcp_ctx *ctx, void *dst_d, const void *src_pinned, size_t 
 int copy_to_pinned_async(pcp_ctx *ctx, void *dst_pinned, const void *src_d, size_t bytes,
                          hipStream_t st) {
     if (!bytes) return PCP_OK;
-    if (!ctx->copy_kernel || (((uintptr_t)dst_pinned | (uintptr_t)src_d) & 15u)) {
+    if (!ctx->knob.copy_kernel || (((uintptr_t)dst_pinned | (uintptr_t)src_d) & 15u)) {
         PCP_HIP(ctx, hipMemcpyAsync(dst_pinned, src_d, bytes, hipMemcpyDeviceToHost, st));
         return PCP_OK;
     }
@@ -568,7 +567,7 @@ int exclusive_scan_u32(pcp_ctx *ctx, const uint32_t *in, uint32_t *out, uint64_t
     // one pass only where the look-back is one window (tiles <= 64: tile 0's inclusive prefix
     // in every tile's first window); longer scans walk windows of aggregates back to tile 0,
     // which measured slower than the three short launches (terrain grids, ~430 tiles)
-    if (tiles > 1 && tiles <= 64 && ctx->scan_onepass) {
+    if (tiles > 1 && tiles <= 64 && ctx->knob.scan_onepass) {
         const size_t cap0 = ctx->scan_state.cap;
         PCP_HIP(ctx, ctx->scan_state.ensure(tiles * sizeof(unsigned long long) + 64));
         if (++ctx->scan_epoch >= (1u << 30) || ctx->scan_state.cap != cap0) {   // wrap / new buffer
@@ -618,21 +617,15 @@ extern "C" int pcp_debug_exclusive_scan(pcp_ctx *ctx, const uint32_t *in, uint64
     PCP_HIP(ctx, din.ensure((n + 1) * sizeof(uint32_t)));
     PCP_HIP(ctx, dout.ensure((n + 1) * sizeof(uint32_t)));
     PCP_HIP(ctx, dtmp.ensure(scan_tmp_bytes(n) + 256));
-    int rc = PCP_OK;
-    hipError_t e = n ? hipMemcpyAsync(din.p, in, n * sizeof(uint32_t), hipMemcpyHostToDevice,
-                                      ctx->stream)
-                     : hipSuccess;
-    if (e == hipSuccess)
-        rc = exclusive_scan_u32(ctx, din.as<const uint32_t>(), dout.as<uint32_t>(), n, dtmp.p);
-    if (e == hipSuccess && rc == PCP_OK)
-        e = hipMemcpyAsync(out, dout.p, (n + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost,
-                           ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    din.release();
-    dout.release();
-    dtmp.release();
-    if (rc) return rc;
-    if (e != hipSuccess) return hip_fail(ctx, e, "pcp_debug_exclusive_scan", __FILE__, __LINE__);
+    // an early return frees the three buffers, and a hipFree waits for the device
+    if (n)
+        PCP_HIP(ctx, hipMemcpyAsync(din.p, in, n * sizeof(uint32_t), hipMemcpyHostToDevice,
+                                    ctx->stream));
+    if (int rc = exclusive_scan_u32(ctx, din.as<const uint32_t>(), dout.as<uint32_t>(), n, dtmp.p))
+        return rc;
+    PCP_HIP(ctx, hipMemcpyAsync(out, dout.p, (n + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                                ctx->stream));
+    PCP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return PCP_OK;
 }
 
@@ -642,7 +635,7 @@ namespace pcp {
 int exclusive_scan_u32_pair(pcp_ctx *ctx, const uint32_t *in_a, uint32_t *out_a, uint64_t n_a,
                             uint32_t *out2_a, const uint32_t *in_b, uint32_t *out_b, uint64_t n_b,
                             uint32_t *out2_b, void *tmp, bool zero2) {
-    if (n_a && n_b && n_a <= (uint64_t)kScanTile && n_b <= (uint64_t)kScanTile && ctx->scan_pair) {
+    if (n_a && n_b && n_a <= (uint64_t)kScanTile && n_b <= (uint64_t)kScanTile && ctx->knob.scan_pair) {
         hipLaunchKernelGGL(k_scan_pair, dim3(2), dim3(kScanThreads), 0, ctx->stream,
                            ScanOne{in_a, n_a, out_a, out2_a}, ScanOne{in_b, n_b, out_b, out2_b},
                            zero2 ? 1 : 0);
@@ -656,6 +649,28 @@ int exclusive_scan_u32_pair(pcp_ctx *ctx, const uint32_t *in_a, uint32_t *out_a,
 }  // namespace pcp
 
 using namespace pcp;
+
+// What is no buffer, in the order that matters: the streams drained first, the communicator gone
+// before its key buffers and the copy helpers before pinned memory (both members, freed after
+// this body), the streams last (CtxStreams).  A context that never opened its stream (a failed
+// pcp_create, a host-only test) makes no HIP call here: every handle is still null.
+pcp_ctx::~pcp_ctx() {
+    if (stream) {
+        (void)hipSetDevice(device);
+        (void)hipStreamSynchronize(stream);
+        if (area_stream) (void)hipStreamSynchronize(area_stream);
+        prof_resolve(this);
+    }
+    for (hipEvent_t e : event_pool) (void)hipEventDestroy(e);
+    for (hipEvent_t e : up_ev)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {area_fork_ev, area_join_ev, keys_ev})
+        if (e) (void)hipEventDestroy(e);
+    if (fm_exec) (void)hipGraphExecDestroy(fm_exec);
+    if (fm_graph) (void)hipGraphDestroy(fm_graph);
+    comm_release(this);
+    host_copy_release(this);
+}
 
 // ======================================================================================
 // C ABI: context
@@ -689,67 +704,17 @@ int pcp_create(int device, pcp_ctx **out) {
     pcp_ctx *ctx = new (std::nothrow) pcp_ctx();
     if (!ctx) return PCP_E_NOMEM;
     ctx->device = device;
-    if (const char *fb = std::getenv("PCP_FAN_BATCH")) ctx->fan_batch = std::atoi(fb);
-    if (const char *fw = std::getenv("PCP_FAN_NPW")) {
-        const int v = std::atoi(fw);
-        ctx->fan_npw = (v == 2 || v == 4 || v == 8 || v == 16 || v == 32) ? v : 1;
+    std::string bad;   // no context exists to carry the message: it goes to stderr
+    if (knobs_from_env(ctx->knob, [](const char *n) -> const char * { return std::getenv(n); },
+                       &bad)) {
+        std::fprintf(stderr, "libpcp: pcp_create: %s\n", bad.c_str());
+        delete ctx;
+        return PCP_E_INVALID;
     }
-    if (const char *fc = std::getenv("PCP_FAN_CULL")) ctx->fan_cull = std::atoi(fc) != 0;
-    if (const char *cl = std::getenv("PCP_FAN_CLEAR")) ctx->terrain.fan_clear = std::atoi(cl) != 0;
-    if (const char *pv = std::getenv("PCP_FAN_PIVOT")) ctx->terrain.fan_pivot = std::atoi(pv) != 0;
-    if (const char *bd = std::getenv("PCP_FAN_BAND")) ctx->terrain.fan_band = std::atoi(bd) != 0;
-    if (const char *cp = std::getenv("PCP_FAN_CLIP"))
-        ctx->terrain.fan_clip_e = std::atoi(cp) != 0 ? pcp::kClipSlack : pcp::kClipSlackWhole;
-    if (const char *fo = std::getenv("PCP_FAN_ORDER")) ctx->fan_horizon_first = std::atoi(fo) != 0;
-    if (const char *ho = std::getenv("PCP_FAN_HOST_OUT")) ctx->fan_host_out = std::atoi(ho) != 0;
-    if (const char *ne = std::getenv("PCP_NORMALS_EXACT")) ctx->normals_exact = std::atoi(ne) != 0;
-    if (const char *sw = std::getenv("PCP_SCORE_WIDE")) ctx->score_wide = std::atoi(sw) != 0;
-    if (const char *wr = std::getenv("PCP_SCORE_WIDE_RAYS")) ctx->score_wide_rays = std::atoll(wr);
-    if (const char *wg = std::getenv("PCP_SCORE_WIDE_G")) {
-        // the instantiated widths only: no context exists to carry the message, so it goes to
-        // stderr and the creation fails (no silent fall-back to the default)
-        char *end = nullptr;
-        const long v = std::strtol(wg, &end, 10);
-        if (end == wg || *end != '\0' || !(v == 2 || v == 4 || v == 8 || v == 16)) {
-            std::fprintf(stderr, "libpcp: pcp_create: PCP_SCORE_WIDE_G=\"%s\" is not one of 2, 4, 8, 16\n",
-                         wg);
-            delete ctx;
-            return PCP_E_INVALID;
-        }
-        ctx->score_wide_g = (int)v;
-    }
-    if (const char *co = std::getenv("PCP_CELLS_ORDER_FREE")) ctx->cells_all_ordered = std::atoi(co) == 0;
-    if (const char *nbk = std::getenv("PCP_NB_BLOCKS")) ctx->nb_blocks = std::atoi(nbk);
-    if (const char *sp = std::getenv("PCP_SCAN_ONEPASS")) ctx->scan_onepass = std::atoi(sp) != 0;
-    if (const char *ip = std::getenv("PCP_INDEX_PAIR")) ctx->index_pair = std::atoi(ip) != 0;
-    if (const char *as = std::getenv("PCP_AREA_STREAM")) ctx->area_side = std::atoi(as) != 0;
-    if (const char *ns = std::getenv("PCP_NB_SMALL")) ctx->nb_small = std::atoi(ns) != 0;
-    if (const char *rp = std::getenv("PCP_NB_REGION_PCT"))
-        ctx->nb_region_pct = std::min(100, std::max(1, std::atoi(rp)));
-    if (const char *gw = std::getenv("PCP_NB_GUESS_WORDS"))
-        ctx->nb_guess_max = std::max<uint64_t>(1, std::strtoull(gw, nullptr, 10));
-    if (const char *ct = std::getenv("PCP_COPY_THREADS")) ctx->copy_threads = std::atoi(ct);
-    if (const char *fo = std::getenv("PCP_FM_HOST_OUT")) ctx->fm_host_out = std::atoi(fo) != 0;
-    if (const char *ff = std::getenv("PCP_FM_FAST")) {   // an unknown value is the default
-        const int v = std::atoi(ff);
-        ctx->fm_fast = (v == 0 || v == 1) ? v : 2;
-    }
-    if (const char *bg = std::getenv("PCP_BK_GT")) ctx->bk_gt = std::atoi(bg);
-    if (const char *sp = std::getenv("PCP_SCAN_PAIR")) ctx->scan_pair = std::atoi(sp) != 0;
-    if (const char *fc = std::getenv("PCP_CARVE_FUSE_COPY")) ctx->carve_fuse_copy = std::atoi(fc) != 0;
-    if (const char *bp = std::getenv("PCP_BK_PTS")) ctx->bk_pts = std::atoi(bp);
-    if (const char *zc = std::getenv("PCP_ZC_IN")) ctx->zc_in = std::atoi(zc) != 0;
-    if (const char *ck = std::getenv("PCP_COPY_KERNEL")) ctx->copy_kernel = std::atoi(ck) != 0;
-    if (const char *tb = std::getenv("PCP_TERRAIN_BLOCKS")) ctx->terrain_blocks = std::atoi(tb);
-    if (const char *tf = std::getenv("PCP_TERRAIN_FINE")) ctx->terrain_fine = std::atoi(tf);
-    if (const char *tt = std::getenv("PCP_FINE_TILE")) ctx->fine_tile = std::atoi(tt);
-    if (const char *fs = std::getenv("PCP_FINE_SKIP")) ctx->fine_skip = std::atoi(fs) == 2 ? 2 : 1;
-    if (const char *fp = std::getenv("PCP_FINE_PACK")) ctx->fine_pack = std::atoi(fp) != 0;
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess &&
         cus > 0)
         ctx->num_cus = cus;
-    if (const char *ng = std::getenv("PCP_NO_GRAPHS")) ctx->use_graphs = std::atoi(ng) == 0;
     if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) {
         delete ctx;
         return PCP_E_HIP;
@@ -758,76 +723,7 @@ int pcp_create(int device, pcp_ctx **out) {
     return PCP_OK;
 }
 
-void pcp_destroy(pcp_ctx *ctx) {
-    if (!ctx) return;
-    (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->area_stream) (void)hipStreamSynchronize(ctx->area_stream);
-    prof_resolve(ctx);
-    for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
-    if (ctx->area_fork_ev) (void)hipEventDestroy(ctx->area_fork_ev);
-    if (ctx->area_join_ev) (void)hipEventDestroy(ctx->area_join_ev);
-    if (ctx->keys_ev) (void)hipEventDestroy(ctx->keys_ev);
-    comm_release(ctx);
-    host_copy_release(ctx);
-    for (int k = 0; k < pcp_ctx::kUpRing; ++k) {
-        if (ctx->up_ev[k]) (void)hipEventDestroy(ctx->up_ev[k]);
-        ctx->up_buf[k].release();
-    }
-    ctx->cand_host.release();
-    ctx->tc_host.release();
-    ctx->cv_host.release();
-    ctx->terrain.release();
-    ctx->aux.release();
-    ctx->exc_norm.release();
-    ctx->exc_near.release();
-    ctx->area_nrm.release();
-    ctx->nb_list.release();
-    ctx->nb_meta.release();
-    ctx->nb_ctl.release();
-    ctx->nb_pts.release();
-    ctx->nb_list_c.release();
-    ctx->nb_meta_c.release();
-    ctx->nb_sel.release();
-    ctx->carve.release();
-    ctx->carve_buf.release();
-    ctx->cell_cnt.release();
-    ctx->cell_cnt2.release();
-    ctx->carve_gen.release();
-    ctx->fan_host.release();
-    ctx->res_host.release();
-    ctx->fm_res_host.release();
-    ctx->small_host.release();
-    ctx->area_host.release();
-    DevBuf *bufs[] = {&ctx->cells_xyz, &ctx->cells_nrm, &ctx->cells_n_d, &ctx->stage, &ctx->fan_tab,
-                      &ctx->poses_d,   &ctx->steps_d,   &ctx->out_a, &ctx->out_b,
-                      &ctx->out_c,     &ctx->out_d,     &ctx->stats_d, &ctx->f_in,
-                      &ctx->f_misc,    &ctx->bk_stat};
-    for (DevBuf *b : bufs) b->release();
-    for (auto &b : ctx->scratch) b.release();
-    for (auto &b : ctx->fbuf) b.release();
-    if (ctx->fm_exec) (void)hipGraphExecDestroy(ctx->fm_exec);
-    if (ctx->fm_graph) (void)hipGraphDestroy(ctx->fm_graph);
-    ctx->lat_flags.release();
-    ctx->scan_state.release();
-    ctx->carve_ctr.release();
-    ctx->exc_land.release();
-    ctx->place_d.release();
-    ctx->place_host.release();
-    ctx->pair_d.release();
-    ctx->pair_m.release();
-    ctx->pair_host.release();
-    ctx->refine_d.release();
-    ctx->refine_m.release();
-    ctx->refine_host.release();
-    ctx->triple_d.release();
-    ctx->triple_host.release();
-    ctx->vscan_d.release();
-    ctx->vscan_host.release();
-    if (ctx->area_stream) (void)hipStreamDestroy(ctx->area_stream);
-    (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
-}
+void pcp_destroy(pcp_ctx *ctx) { delete ctx; }
 
 const char *pcp_last_error(const pcp_ctx *ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 

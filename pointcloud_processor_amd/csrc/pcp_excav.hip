@@ -1169,7 +1169,7 @@ namespace pcp {
 static NbLists nb_lists_view(const pcp_ctx *ctx, const DevBuf &list, const DevBuf &meta,
                              uint32_t *need, uint32_t *overflow, uint32_t *cursor, uint32_t grid) {
     const uint64_t words = std::min<uint64_t>(list.cap / 4, 0xffffffffull);
-    const uint32_t per_block = (uint32_t)(words * (uint64_t)ctx->nb_region_pct / 100 / grid);
+    const uint32_t per_block = (uint32_t)(words * (uint64_t)ctx->knob.nb_region_pct / 100 / grid);
     const uint64_t pool_base = (uint64_t)per_block * grid;
     return NbLists{list.as<uint32_t>(), meta.as<uint2>(), need, overflow,
                    per_block, cursor, pool_base, words - pool_base};
@@ -1182,7 +1182,7 @@ static void nb_area_launch(pcp_ctx *ctx, hipStream_t st) {
     const uint64_t n = ctx->area_n;
     uint32_t *ctl = ctx->nb_ctl.as<uint32_t>();
     const NbLists La = nb_lists_view(ctx, ctx->nb_list, ctx->nb_meta, ctl, ctl + 2, ctl + 3, grid_a);
-    if (n <= 65536 && ctx->nb_small)   // (input indices in 16 bits)
+    if (n <= 65536 && ctx->knob.nb_small)   // (input indices in 16 bits)
         hipLaunchKernelGGL((k_nb_lists<false, true>), dim3(grid_a), dim3(kNbT), 0, st, gn, r2n,
                            bscale, (const double *)nullptr, (const uint32_t *)nullptr, La,
                            (const uint32_t *)nullptr);
@@ -1210,8 +1210,8 @@ static void nb_cells_launch(pcp_ctx *ctx, hipStream_t st) {
     if (total) {
         hipLaunchKernelGGL(k_cell_sums_exact, dim3(grid_c), dim3(kNbT), 0, st, gn, r2n,
                            (const double *)ctx->cells_xyz.as<double>(), n_d, nrm4,
-                           ctx->cells_nrm.as<float>(), sel, ctx->cells_all_ordered ? 1 : 0);
-        if (ctx->area_n <= 65536 && ctx->nb_small)
+                           ctx->cells_nrm.as<float>(), sel, ctx->knob.cells_all_ordered ? 1 : 0);
+        if (ctx->area_n <= 65536 && ctx->knob.nb_small)
             hipLaunchKernelGGL((k_nb_lists<true, true>), dim3(grid_c), dim3(kNbT), 0, st, gn, r2n,
                                bscale, (const double *)ctx->cells_xyz.as<double>(), n_d, Lc,
                                (const uint32_t *)sel);
@@ -1311,7 +1311,7 @@ int area_setup_from(pcp_ctx *ctx, const pcp_cloud_view *area, double grid_resolu
     // the exact path: both grids from one pass over the records, which also lays out the points
     // by input index for the sums and the non-finite points' NaN normals (k_area_prep's work)
     bool paired = false;
-    if (ctx->normals_exact) {
+    if (ctx->knob.normals_exact) {
         PCP_HIP(ctx, ctx->nb_pts.ensure(2 * n * sizeof(float4) + 64));
         if ((rc = build_index_pair(ctx, ctx->exc_norm, kNormalRadius, ctx->exc_near, r_near,
                                    *area, &raw, ctx->nb_pts.as<float4>(),
@@ -1363,7 +1363,7 @@ int area_setup_from(pcp_ctx *ctx, const pcp_cloud_view *area, double grid_resolu
         return set_err(ctx, PCP_E_CAPACITY, "pcp_set_excavation_area: %llu lattice points",
                        (unsigned long long)total);
     L.total = (uint32_t)total;
-    const bool exact = ctx->normals_exact;
+    const bool exact = ctx->knob.normals_exact;
     defer = defer && exact;   // (the order-free A/B kernels settle before the return)
     PCP_HIP(ctx, ctx->area_host.ensure(64));
     uint32_t *n_h = ctx->area_host.as<uint32_t>();
@@ -1417,14 +1417,16 @@ int area_setup_from(pcp_ctx *ctx, const pcp_cloud_view *area, double grid_resolu
     // area_finish).  The cells go through k_cell_sums_exact first (any order where no order can
     // change the sums); only those it leaves in nb_sel take the ordered lists.  Every buffer is
     // sized before the launches.
-    const uint32_t nbb = ctx->nb_blocks > 0 ? (uint32_t)ctx->nb_blocks : (uint32_t)kNbBlocks;
+    const uint32_t nbb =
+        ctx->knob.nb_blocks > 0 ? (uint32_t)ctx->knob.nb_blocks : (uint32_t)kNbBlocks;
     ctx->area_grid_a = std::min<uint32_t>(npts, nbb);
     ctx->area_grid_c = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(total, nbb));
     ctx->area_npts = npts;
     ctx->area_total = total;
     const uint64_t per_pt = std::min<uint64_t>(npts, 4096);
-    const uint64_t guess_a = std::min<uint64_t>((uint64_t)npts * per_pt, ctx->nb_guess_max);
-    const uint64_t guess_c = std::min<uint64_t>(std::max<uint64_t>(total, 1) * per_pt, ctx->nb_guess_max);
+    const uint64_t guess_a = std::min<uint64_t>((uint64_t)npts * per_pt, ctx->knob.nb_guess_max);
+    const uint64_t guess_c =
+        std::min<uint64_t>(std::max<uint64_t>(total, 1) * per_pt, ctx->knob.nb_guess_max);
     PCP_HIP(ctx, ctx->nb_list.ensure(std::max<uint64_t>(guess_a, ctx->nb_need) * 4 + 64));
     PCP_HIP(ctx, ctx->nb_list_c.ensure(std::max<uint64_t>(guess_c, ctx->nb_need_c) * 4 + 64));
     PCP_HIP(ctx, ctx->nb_meta.ensure((size_t)npts * sizeof(uint2) + 64));
@@ -1443,7 +1445,8 @@ int area_setup_from(pcp_ctx *ctx, const pcp_cloud_view *area, double grid_resolu
     // cells_*, lat_flags, area_host) and nothing on ctx->stream reads those before the join
     // (not when the raw records sit in ctx->stage: a large area's, DMA'd there, which the next
     // upload on ctx->stream may overwrite while k_area_prep still reads them)
-    const bool side = defer && ctx->area_side && (paired || raw != ctx->stage.as<unsigned char>());
+    const bool side =
+        defer && ctx->knob.area_side && (paired || raw != ctx->stage.as<unsigned char>());
     if (side) {
         if (!ctx->area_stream)
             PCP_HIP(ctx, hipStreamCreateWithFlags(&ctx->area_stream, hipStreamNonBlocking));

@@ -489,9 +489,9 @@ int fan_enqueue(pcp_ctx *ctx, const double *poses5, uint64_t n, const pcp_fan_pa
     FanArgs a{};
     a.present = ctx->terrain.present ? 1 : 0;
     if (a.present) {
-        a.g = ctx->terrain.view();
+        a.g = ctx->terrain.view(ctx->knob);
         if (!a.g.occz) return set_err(ctx, PCP_E_INVALID, "pcp_raycast_fan: terrain index has no z bands");
-        if (ctx->fan_batch == 2 && !a.g.occ2)
+        if (ctx->knob.fan_batch == 2 && !a.g.occ2)
             return set_err(ctx, PCP_E_STATE, "pcp_raycast_fan: variant 2 needs a terrain set with PCP_FAN_BATCH=2");
     }
     // the level rows (pcp_fan_row.hpp): the pose and, against this query's view, the march
@@ -505,8 +505,9 @@ int fan_enqueue(pcp_ctx *ctx, const double *poses5, uint64_t n, const pcp_fan_pa
     }
     a.uniform_el = (fan->n_az % 64 == 0) ? 1 : 0;
     // the kernel and whether it runs on the full grid: asked once, here (pcp_fan_pick.hpp)
-    const FanPick pick = fan_pick(mode, ctx->fan_batch, a.g.frec != nullptr, a.g.ftile,
-                                  a.uniform_el != 0, P, K, ctx->fan_npw, opt.burst > 0, opt.mounted);
+    const FanPick pick = fan_pick(mode, ctx->knob.fan_batch, a.g.frec != nullptr, a.g.ftile,
+                                  a.uniform_el != 0, P, K, ctx->knob.fan_npw, opt.burst > 0,
+                                  opt.mounted);
     if (opt.mounted && mode != FanMode::Plain)
         return set_err(ctx, PCP_E_INVALID, "pcp_raycast_fan_mounted: no diagnostic modes");
     // Skip 4: each pose's live rings [j0, j1) into its eighth slot (the UE
@@ -515,7 +516,7 @@ int fan_enqueue(pcp_ctx *ctx, const double *poses5, uint64_t n, const pcp_fan_pa
     uint32_t w0 = 0, lw = waves;
     if (!opt.mounted) {   // (a mounted row has no live-ring slot: its kernels cover every ring)
         uint32_t *lr = reinterpret_cast<uint32_t *>(pose8) + kFanRowLiveU32;
-        const bool rule = ctx->fan_cull && ctx->terrain.present && K > 0;
+        const bool rule = ctx->knob.fan_cull && ctx->terrain.present && K > 0;
         if (rule) {
             const FanLive L = fan_live_rings((double)a.g.fb[4], (double)a.g.fb[5], pose8 + FR_Z,
                                              (uint64_t)P, kFanRow, ctx->fan_se_h.data(), fan->n_el,
@@ -569,7 +570,7 @@ int fan_enqueue(pcp_ctx *ctx, const double *poses5, uint64_t n, const pcp_fan_pa
     a.lw = lw;
     // the live rings nearest the horizon first: they are the far end of the interval when the
     // near end is the steeper one
-    a.rev = (ctx->fan_horizon_first && lw > 0 && lw < waves &&
+    a.rev = (ctx->knob.fan_horizon_first && lw > 0 && lw < waves &&
              std::fabs(ctx->fan_se_h[std::min<size_t>((size_t)(w0 + lw - 1) * 64 / (size_t)fan->n_az,
                                                       (size_t)fan->n_el - 1)]) <
                  std::fabs(ctx->fan_se_h[(size_t)w0 * 64 / (size_t)fan->n_az]))
@@ -657,7 +658,7 @@ static int raycast_fan_impl(pcp_ctx *ctx, const double *poses5, uint64_t n,
         return PCP_OK;
     }
     FanEnq o;   // (the kernel and its poses per wave: pcp_fan_pick.hpp, mirrored by bench._fan_npw)
-    const bool host_out = ctx->fan_host_out;
+    const bool host_out = ctx->knob.fan_host_out;
     if (int rc = fan_enqueue(ctx, poses5, n, fan, o, mode,
                              FanOpts{first_hit != nullptr, burst, burst_ms, host_out, mounted,
                                      el_table}))

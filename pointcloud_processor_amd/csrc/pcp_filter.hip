@@ -1732,14 +1732,14 @@ static void plan_facts(const pcp_ctx *ctx, const std::vector<CloudJob> &jobs, Fi
                        CallGeo &geo) {
     const int k = (int)jobs.size();
     in.clouds = k;
-    in.fm_fast = ctx->fm_fast;
-    in.fm_host_out = ctx->fm_host_out;
-    in.use_graphs = ctx->use_graphs;
+    in.fm_fast = ctx->knob.fm_fast;
+    in.fm_host_out = ctx->knob.fm_host_out;
+    in.use_graphs = ctx->knob.use_graphs;
     for (int i = 0; i < k; ++i) {
         const CloudJob &J = jobs[i];
         geo.fast[i] = fast_geometry(J.box, J.leaf, J.in.n, J.nb, k, ctx->num_cus);
-        geo.bucket[i] = bucket_geometry(J.box, J.leaf, J.in.n, J.nb, k, ctx->num_cus, ctx->bk_gt,
-                                        ctx->bk_pts);
+        geo.bucket[i] = bucket_geometry(J.box, J.leaf, J.in.n, J.nb, k, ctx->num_cus,
+                                        ctx->knob.bk_gt, ctx->knob.bk_pts);
         in.voxelises[i] = certainly_voxelises(J.box, J.leaf, J.in.n);
         in.fast[i] = geo.fast[i].ok ? Geo::Available : Geo::Unavailable;
         in.bucket[i] = geo.bucket[i].ok ? Geo::Available : Geo::Unavailable;
@@ -2042,8 +2042,8 @@ static int run_single(pcp_ctx *ctx, FilterEntry entry, const pcp_cloud_view *in,
     // a message-sized cloud that may take a quick chain: read in place from the pinned ring (no
     // DMA; the input stays where it was staged until the last attempt)
     const uint64_t in_bytes = in->n * (uint64_t)in->point_step;
-    const bool zc = entry != FilterEntry::CropBox && !idx_out && ctx->zc_in && ctx->fm_fast &&
-                    in_bytes <= kPinDirectMax;
+    const bool zc = entry != FilterEntry::CropBox && !idx_out && ctx->knob.zc_in &&
+                    ctx->knob.fm_fast && in_bytes <= kPinDirectMax;
     if (zc) {
         if ((rc = stage_cloud(ctx, *in, true, ctx->f_in, 0, c))) return rc;   // fields only
         const HostPiece pc{0, in->data, in_bytes};
@@ -2219,7 +2219,7 @@ int pcp_transform_concat(pcp_ctx *ctx, int k, const pcp_cloud_view *clouds, cons
     std::vector<size_t> soff(k + 1, 0);
     for (int i = 0; i < k; ++i)
         soff[i + 1] = soff[i] + align256(clouds[i].n * (uint64_t)clouds[i].point_step);
-    if (ctx->zc_in && k <= kXfMax && soff[k] <= kPinDirectMax) {
+    if (ctx->knob.zc_in && k <= kXfMax && soff[k] <= kPinDirectMax) {
         // message-sized: every cloud read in place from one pinned slot, one launch, the
         // records stored straight into pinned memory -- no DMA either way, one synchronisation
         std::vector<HostPiece> pc(k);
@@ -2453,7 +2453,7 @@ int pcp_filter_merge_nodes(pcp_ctx *ctx, int k, const pcp_cloud_view *clouds,
     if (rc) return rc;
     if ((int)ctx->fbuf.size() < k) ctx->fbuf.resize(k);
     // inputs: one pinned-ring slot holding every cloud (message-sized), else DMA'd staging
-    const bool zc = ctx->zc_in && in_bytes <= kPinDirectMax;
+    const bool zc = ctx->knob.zc_in && in_bytes <= kPinDirectMax;
     std::vector<size_t> soff(k + 1, 0);
     for (int i = 0; i < k; ++i)
         soff[i + 1] = soff[i] + align256(clouds[i].n * clouds[i].point_step);

@@ -427,8 +427,8 @@ int build_fine(pcp_ctx *ctx, GridIndex &g) {
     if (g.fine_ok || g.fine_fail || !g.present || !g.occz_ok || g.n_pts == 0) return PCP_OK;
     hipStream_t st = ctx->stream;
     ProfScope prof(ctx, PCP_K_INDEX_BUILD);
-    const FinePlan plan = fine_plan(g, std::max(2, std::min(ctx->terrain_fine, 8)),
-                                    ctx->fine_tile == 2 ? 2 : ctx->fine_tile ? 1 : 0);
+    const FinePlan plan = fine_plan(g, std::max(2, std::min(ctx->knob.terrain_fine, 8)),
+                                    ctx->knob.fine_tile == 2 ? 2 : ctx->knob.fine_tile ? 1 : 0);
     const CellMap m = plan.m;
     const FineGeo f = plan.f;
     const int F = plan.F, tile = plan.tile;
@@ -496,7 +496,7 @@ int build_fine(pcp_ctx *ctx, GridIndex &g) {
     PCP_CHECK_LAUNCH(ctx);
     // the copy is an optional speed-up: an allocation failure keeps the other layouts
     const size_t nent = (size_t)np + nw;
-    const bool pack = ctx->fine_pack != 0;
+    const bool pack = ctx->knob.fine_pack != 0;
     // the pivot table goes with the split records; its 12-byte records are addressed with
     // 32-bit byte offsets (a plane past 2^28 cells keeps the copy and goes without)
     const bool pivots = tile == 2 && plan.npiv < (1ull << 28);
@@ -519,7 +519,7 @@ int build_fine(pcp_ctx *ctx, GridIndex &g) {
     PCP_CHECK_LAUNCH(ctx);
     // 5. records (and the sentinels), one thread per window; two skip thresholds need a 25-bit
     // walk start
-    const bool skip2 = tile == 2 && ctx->fine_skip == 2 && nent < (1ull << 25);
+    const bool skip2 = tile == 2 && ctx->knob.fine_skip == 2 && nent < (1ull << 25);
     const uint32_t tsteps = plan.tsteps;
     const uint64_t nthr = std::max<uint64_t>(nw, tile ? nrec / rz : 0);
     hipLaunchKernelGGL(k_frec, dim3((unsigned)((nthr + kThreads - 1) / kThreads)), dim3(kThreads), 0,
@@ -663,7 +663,7 @@ extern "C" int pcp_debug_fine_pivot(pcp_ctx *ctx, pcp_fine_pivot_geo *geo, void 
     if (!g.present || !g.fine_ok || !g.fpiv_ok) return PCP_OK;   // built = 0
     const FinePlan p = fine_plan(g, (int)g.ffine, g.ftile);
     geo->built = 1;
-    geo->enabled = g.fan_pivot ? 1 : 0;
+    geo->enabled = ctx->knob.fan_pivot ? 1 : 0;
     geo->fnx = p.f.fnx;
     geo->fny = p.f.fny;
     geo->tx = (int32_t)pivot_tiles((uint32_t)p.fnx);
@@ -692,7 +692,7 @@ extern "C" int pcp_debug_fine_band(pcp_ctx *ctx, uint64_t *bytes, int32_t *enabl
     if (!ctx || !bytes) return PCP_E_INVALID;
     const GridIndex &g = ctx->terrain;
     *bytes = 0;
-    if (enabled) *enabled = g.fan_band ? 1 : 0;
+    if (enabled) *enabled = ctx->knob.fan_band ? 1 : 0;
     if (!g.present || !g.fine_ok || !g.fband_ok) return PCP_OK;
     const FinePlan p = fine_plan(g, (int)g.ffine, g.ftile);
     *bytes = (uint64_t)p.nrec * 2;

@@ -134,11 +134,12 @@ struct CopyPool {
 };
 
 void host_copy(pcp_ctx *ctx, void *dst, const void *src, size_t bytes) {
-    if (bytes < kSplitMin || ctx->copy_threads <= 0) {
+    if (bytes < kSplitMin || ctx->knob.copy_threads <= 0) {
         std::memcpy(dst, src, bytes);
         return;
     }
-    if (!ctx->copy_pool) ctx->copy_pool = new (std::nothrow) CopyPool(std::min(ctx->copy_threads, kMaxHelpers));
+    if (!ctx->copy_pool)
+        ctx->copy_pool = new (std::nothrow) CopyPool(std::min(ctx->knob.copy_threads, kMaxHelpers));
     if (!ctx->copy_pool) {
         std::memcpy(dst, src, bytes);
         return;

@@ -18,7 +18,7 @@ namespace pcp {
 constexpr uint64_t kMaxCells = 1ull << 25;
 constexpr int kThreads = 256;
 
-GridView GridIndex::view() const {
+GridView GridIndex::view(const Knobs &k) const {
     GridView v{};
     v.pts = pts.as<const float4>();
     v.start = start.as<const uint32_t>();
@@ -68,7 +68,7 @@ GridView GridIndex::view() const {
     v.ffine = fine_ok ? ffine : 0.0f;
     v.ftile = fine_ok ? ftile : 0;
     v.fband = !(fine_ok && ftile == 2) ? nullptr
-              : (fband_ok && fan_band)   ? fband2.as<const uint16_t>()
+              : (fband_ok && k.fan_band) ? fband2.as<const uint16_t>()
                                          : frec.as<const uint16_t>();
     v.fzc = (float)c;
     v.wpack = fine_ok ? wpack : 0;
@@ -78,14 +78,14 @@ GridView GridIndex::view() const {
                    : nullptr;
     v.fus_off = (float)(rm * v.inv_c / (double)kZq);
     v.fskip = fine_ok ? fskip : 1;
-    v.fclear = (fine_ok && ftile == 2 && fan_clear) ? 1 : 0;
+    v.fclear = (fine_ok && ftile == 2 && k.fan_clear) ? 1 : 0;
     v.fclr_cf = fine_ok ? (float)(c / (double)ffine) : 0.0f;
     v.fclr_rb = std::nextafter((float)rb, INFINITY);
     const bool piv = fine_ok && ftile == 2 && fpiv_ok;
-    v.fpiv = (piv && fan_pivot) ? fpiv.as<const float>() : nullptr;
+    v.fpiv = (piv && k.fan_pivot) ? fpiv.as<const float>() : nullptr;
     v.fptx = piv ? (frx + 7u) >> 3 : 0u;
     v.fpty = piv ? (fry + 7u) >> 3 : 0u;
-    v.fclip_e = fan_clip_e;
+    v.fclip_e = k.fan_clip_e;
     return v;
 }
 
@@ -487,12 +487,12 @@ constexpr uint64_t kHostBboxMax = 1ull << 17;
 // zero, which no grid geometry below can see: bmin - c, bmax - bmin are the same either way)
 typedef float HostF4 __attribute__((ext_vector_type(4)));
 typedef int HostI4 __attribute__((ext_vector_type(4)));
-static void host_bbox(const pcp_cloud_view &v, float bb[10], uint32_t &nfin) {
+// vec false (knob.host_bbox_scalar, A/B): the scalar loop for every record
+static void host_bbox(const pcp_cloud_view &v, float bb[10], uint32_t &nfin, bool vec) {
     float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
     uint32_t c = 0;
     const unsigned char *raw = static_cast<const unsigned char *>(v.data);
     uint64_t i0 = 0;
-    static const bool vec = !std::getenv("PCP_HOST_BBOX_SCALAR");   // (A/B: the scalar loop)
     if (vec && v.off_y == v.off_x + 4 && v.off_z == v.off_x + 8 &&
         v.off_x + 16 <= v.point_step) {
         constexpr int U = 4;
@@ -613,10 +613,10 @@ int build_index_pair(pcp_ctx *ctx, GridIndex &ga, double ra, GridIndex &gb, doub
                      float *prep_nrm, bool *paired) {
     *paired = false;
     const uint64_t n = v.n;
-    if (n == 0 || n > kHostBboxMax || !ctx->index_pair) return PCP_OK;   // (the two builds)
+    if (n == 0 || n > kHostBboxMax || !ctx->knob.index_pair) return PCP_OK;   // (the two builds)
     float bb_h[10];
     uint32_t nfin = 0;
-    host_bbox(v, bb_h, nfin);
+    host_bbox(v, bb_h, nfin, !ctx->knob.host_bbox_scalar);
     if (nfin == 0) return PCP_OK;
     hipStream_t st = ctx->stream;
     ProfScope prof(ctx, PCP_K_INDEX_BUILD);
@@ -628,7 +628,7 @@ int build_index_pair(pcp_ctx *ctx, GridIndex &ga, double ra, GridIndex &gb, doub
     const uint64_t raw_bytes = n * (uint64_t)v.point_step;
     const unsigned char *raw = raw_io ? *raw_io : nullptr;
     bool pinned = false;
-    if (!raw && ctx->zc_in && raw_bytes <= kPinDirectMax) {
+    if (!raw && ctx->knob.zc_in && raw_bytes <= kPinDirectMax) {
         const HostPiece pc{0, v.data, raw_bytes};
         const void *dv = nullptr;
         if (int rc0 = pin_stage(ctx, &pc, 1, raw_bytes, &dv)) return rc0;
@@ -718,7 +718,7 @@ int build_index(pcp_ctx *ctx, GridIndex &g, const pcp_cloud_view &v, double r_q,
     const uint64_t raw_bytes = n * (uint64_t)v.point_step;
     const unsigned char *raw = raw_io ? *raw_io : nullptr;
     bool pinned = false;
-    if (!raw && n && ctx->zc_in && raw_bytes <= kPinDirectMax) {
+    if (!raw && n && ctx->knob.zc_in && raw_bytes <= kPinDirectMax) {
         const HostPiece pc{0, v.data, raw_bytes};
         const void *dv = nullptr;
         if (int rc0 = pin_stage(ctx, &pc, 1, raw_bytes, &dv)) return rc0;
@@ -758,7 +758,7 @@ int build_index(pcp_ctx *ctx, GridIndex &g, const pcp_cloud_view &v, double r_q,
     // same float min / max over the finite points, order-free) -- no round trip through the
     // stream; the extraction is launched below, fused with the cell count
     if (host_bb) {
-        host_bbox(v, bb_h, nfin);
+        host_bbox(v, bb_h, nfin, !ctx->knob.host_bbox_scalar);
     } else {
         hipLaunchKernelGGL(k_extract, dim3(nb), dim3(kThreads), 0, st, raw, n, v.point_step,
                            v.off_x, v.off_y, v.off_z, ctx->scratch[0].as<float4>(), part, part_n,
@@ -929,11 +929,11 @@ int build_blocks(pcp_ctx *ctx, GridIndex &g) {
 
 int terrain_blocks_before_query(pcp_ctx *ctx) {
     GridIndex &t = ctx->terrain;
-    if (ctx->terrain_blocks <= 0 || t.blk_ok || t.fine_ok || t.blk_fail || !t.present)
+    if (ctx->knob.terrain_blocks <= 0 || t.blk_ok || t.fine_ok || t.blk_fail || !t.present)
         return PCP_OK;
     ++ctx->terrain_queries;
-    if (ctx->terrain_blocks == 1 && ctx->terrain_queries < 2) return PCP_OK;
-    if (ctx->terrain_fine && !t.fine_fail) {
+    if (ctx->knob.terrain_blocks == 1 && ctx->terrain_queries < 2) return PCP_OK;
+    if (ctx->knob.terrain_fine && !t.fine_fail) {
         if (int rc = build_fine(ctx, t)) return rc;
         if (t.fine_ok) return PCP_OK;
     }
@@ -949,7 +949,7 @@ int set_terrain_from(pcp_ctx *ctx, const pcp_cloud_view *terrain, const unsigned
     if (terrain->n == 0) return PCP_OK;   // terrainCallback: no rebuild on an empty cloud
     // the march probes the z bands; occupancy bits only for the fan's A/B variant 2
     const unsigned char *raw = raw_pre;
-    rc = build_index(ctx, ctx->terrain, *terrain, kRayRadius, true, ctx->fan_batch == 2,
+    rc = build_index(ctx, ctx->terrain, *terrain, kRayRadius, true, ctx->knob.fan_batch == 2,
                      raw ? &raw : nullptr);
     ctx->terrain_queries = 0;
     ctx->terrain_index_n = terrain->n;

@@ -8,10 +8,13 @@
 #include <cstdint>
 #include <cstdio>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "pcp_abi.h"
 #include "pcp_fan_pick.hpp"
+#include "pcp_knobs.hpp"
 
 namespace pcp {
 struct CopyPool;
@@ -31,67 +34,57 @@ constexpr double kCellMargin = 4e-3;   // conservative margin of the stencil (se
 constexpr double kQueryMargin = 1e-3;
 
 // ---------------------------------------------------------------------------------------
-// device buffer (grow-only).  A buffer that must grow is reallocated with 25 % headroom (and at
-// least 64 KiB): a hipFree synchronizes the whole device, so a per-frame chain whose sizes
-// wander (C5) must converge to few reallocations instead of one per new maximum.  Every
-// reallocation is counted process-wide (pcp_alloc_stats).
+// device buffer and pinned (page-locked) host staging buffer, both grow-only.  A buffer that must
+// grow is reallocated with 25 % headroom (and at least 64 KiB): a hipFree synchronizes the whole
+// device, so a per-frame chain whose sizes wander (C5) must converge to few reallocations instead
+// of one per new maximum.  Every reallocation is counted process-wide (pcp_alloc_stats).  Small
+// per-call H2D / D2H transfers from a pinned buffer skip the runtime's pageable staging copy.
+// A buffer owns its memory: move-only, freed by its destructor; release() drops it mid-life.
 // ---------------------------------------------------------------------------------------
 void note_realloc(size_t bytes, bool pinned);
 uint64_t alloc_count(int which);   // 0 device, 1 pinned reallocations, 2 bytes allocated
 
 constexpr size_t kHeadroomMax = 16u << 20;   // first allocations below this get +25 %
 
-struct DevBuf {
+template <bool Pinned>
+struct Buf {
     void *p = nullptr;
     size_t cap = 0;
+    Buf() = default;
+    Buf(const Buf &) = delete;
+    Buf &operator=(const Buf &) = delete;
+    Buf(Buf &&o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
+    Buf &operator=(Buf &&o) noexcept {
+        if (this != &o) {
+            release();
+            p = std::exchange(o.p, nullptr);
+            cap = std::exchange(o.cap, 0);
+        }
+        return *this;
+    }
+    ~Buf() { release(); }
     hipError_t ensure(size_t bytes) {
         if (bytes <= cap) return hipSuccess;
         const bool grow = cap != 0;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        size_t want = bytes < 256 ? 256 : bytes;
+        release();
+        size_t want = std::max<size_t>(bytes, Pinned ? 4096 : 256);
         // message-sized buffers start with the headroom a growth would add: streamed clouds
         // vary by a few percent frame to frame, and each growth is a free + malloc in a frame
         if (grow || want < kHeadroomMax) want = std::max<size_t>(want + want / 4, 64u << 10);
-        hipError_t e = hipMalloc(&p, want);
+        hipError_t e = Pinned ? hipHostMalloc(&p, want, hipHostMallocDefault) : hipMalloc(&p, want);
         if (e == hipSuccess) cap = want;
-        note_realloc(want, false);
+        note_realloc(want, Pinned);
         return e;
     }
     void release() {
-        if (p) (void)hipFree(p);
+        if (p) (void)(Pinned ? hipHostFree(p) : hipFree(p));
         p = nullptr;
         cap = 0;
     }
     template <class T> T *as() const { return static_cast<T *>(p); }
 };
-
-// pinned (page-locked) host staging buffer (grow-only, same growth rule): small per-call H2D /
-// D2H transfers from it skip the runtime's pageable staging copy
-struct PinnedBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        const bool grow = cap != 0;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-        size_t want = bytes < 4096 ? 4096 : bytes;
-        if (grow || want < kHeadroomMax) want = std::max<size_t>(want + want / 4, 64u << 10);
-        hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
-        if (e == hipSuccess) cap = want;
-        note_realloc(want, true);
-        return e;
-    }
-    void release() {
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-    template <class T> T *as() const { return static_cast<T *>(p); }
-};
+using DevBuf = Buf<false>;
+using PinnedBuf = Buf<true>;
 
 // ---------------------------------------------------------------------------------------
 // Uniform-grid spatial index (replaces pcl::KdTreeFLANN).  Points sorted by cell, cell
@@ -188,42 +181,14 @@ struct GridIndex {
     float ffine = 0.0f;
     int32_t ftile = 0;
     int32_t fskip = 1;           // walk-start skip thresholds (PCP_FINE_SKIP)
-    bool fan_clear = true;       // the march jumps by the empty records' clearance codes
-                                 // (PCP_FAN_CLEAR, set once by pcp_create; release() keeps it)
     bool fpiv_ok = false;        // pivot table built (fpiv; with the split records)
-    bool fan_pivot = true;       // the fan march tests a window's pivot before its walk
-                                 // (PCP_FAN_PIVOT, set once by pcp_create; release() keeps it)
     bool fband_ok = false;       // the thresholds' tight twin built (fband2; with the split records)
-    bool fan_band = true;        // the march's probe reads the twin (pcp_fan_band.hpp;
-                                 // PCP_FAN_BAND, set once by pcp_create; release() keeps it)
-    float fan_clip_e = 1.0f / 64.0f;   // clip slack in samples, kClipSlack of pcp_fan_clip.hpp
-                                 // (PCP_FAN_CLIP=0: 1; set once by pcp_create; release() keeps it)
     size_t fstart_off = 0;       // ftile 2: byte offset of the start array inside frec
     uint64_t fnent = 0;          // entries of wpts, sentinels included (pcp_debug_fine_copy)
     bool occ2_ok = false;        // occ2 built (only indices queried by stencil_any need it)
-    GridView view() const;
-    void release() {
-        pts.release();
-        start.release();
-        occ2.release();
-        occz.release();
-        bstart.release();
-        bpts.release();
-        frec.release();
-        wpts.release();
-        fpiv.release();
-        fband2.release();
-        fpiv_ok = false;
-        fband_ok = false;
-        occz_ok = false;
-        blk_ok = false;
-        blk_fail = false;
-        fine_ok = false;
-        fine_fail = false;
-        occ2_ok = false;
-        present = false;
-        n_pts = 0;
-    }
+    // k: the fan knobs of the view (fan_clear, fan_pivot, fan_band, fan_clip_e).  The terrain
+    // index is viewed with the context's; every other index runs with the defaults
+    GridView view(const Knobs &k = Knobs{}) const;
 };
 
 // ---------------------------------------------------------------------------------------
@@ -237,28 +202,36 @@ struct ProfSlot {
 struct CloudBufs {                 // one cloud's filter-pipeline scratch
     DevBuf xyz, idx, keys[2], sparse, sparse_idx, hist, out;
     DevBuf skeys;                  // the fast chain: crop tiles' keys + digit-0 rows
-    void release() {
-        skeys.release();
-        xyz.release();
-        idx.release();
-        for (int q = 0; q < 2; ++q) keys[q].release();
-        sparse.release();
-        sparse_idx.release();
-        hist.release();
-        out.release();
-    }
 };
+
+template <class T>
+constexpr bool kMoveOnly = !std::is_copy_constructible_v<T> && std::is_nothrow_move_constructible_v<T>;
+static_assert(kMoveOnly<DevBuf> && kMoveOnly<PinnedBuf>, "a buffer has one owner");
+static_assert(kMoveOnly<GridIndex> && kMoveOnly<CloudBufs>, "move-only through their buffers");
 
 struct PendingEvent {
     int kid;
     hipEvent_t a, b;
 };
 
+// the context's two streams, as its base: destroyed after every member, i.e. after the last free
+struct CtxStreams {
+    hipStream_t stream = nullptr;
+    hipStream_t area_stream = nullptr;   // the async area setup's side stream (knob.area_side)
+    ~CtxStreams() {
+        if (area_stream) (void)hipStreamDestroy(area_stream);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
 }  // namespace pcp
 
-struct pcp_ctx {
+// Nothing here is freed by hand: the buffers free themselves, ~pcp_ctx (pcp_context.hip) drains
+// the streams and destroys what is no buffer, the streams go last (CtxStreams).
+struct pcp_ctx : pcp::CtxStreams {
+    ~pcp_ctx();
     int device = 0;
-    hipStream_t stream = nullptr;
+    pcp::Knobs knob;             // the environment's settings, read once by pcp_create
     std::string err;
     // virtual_lidar state
     pcp::GridIndex terrain;      // raycast index (r_q = 0.056)
@@ -279,12 +252,10 @@ struct pcp_ctx {
     uint64_t area_total = 0;
     pcp::PinnedBuf area_host;        // the setup's landing: [cells, area list use, cell list use,
                                      // overflow, pool cursors]
-    // the async setup's normals + lattice on a stream of their own (PCP_AREA_STREAM, default 1):
-    // forked from ctx->stream after the indices, joined by the scoring (score_enqueue) or by
-    // area_finish, so the terrain / zx120 index builds in between overlap the neighbour lists
-    bool area_side = true;
+    // the async setup's normals + lattice on a stream of their own (knob.area_side): forked from
+    // ctx->stream after the indices, joined by the scoring (score_enqueue) or by area_finish, so
+    // the terrain / zx120 index builds in between overlap the neighbour lists
     bool area_forked = false;        // side work enqueued and not yet joined into ctx->stream
-    hipStream_t area_stream = nullptr;
     hipEvent_t area_fork_ev = nullptr, area_join_ev = nullptr;
     pcp::DevBuf lat_flags;           // the lattice's per-point flags (k_lattice_flags)
     // pcp_filter_merge_nodes' outputs in tc_host (pcp_filter_merge_landed), until tc_host's
@@ -302,25 +273,14 @@ struct pcp_ctx {
     // the next call uses (no memset launch in front of it)
     pcp::DevBuf carve_ctr;
     int carve_ctr_sel = 0;
-    bool carve_ctr_clean[2] = {false, false};         // pcp_excavate_area_async: the carve's records, read in place
-                                     // by the setup + terrain index it enqueues
+    bool carve_ctr_clean[2] = {false, false};
     // excavation area (pcp_set_excavation_area): indices for the normal radius (1.5 m) and the
     // lattice test radius (1.5 * grid_resolution), and the per-point normals
     pcp::GridIndex exc_norm, exc_near;
     pcp::DevBuf area_nrm;
     uint64_t area_n = 0;
-    // the normals in the reference's summation order (PCP_NORMALS_EXACT, default 1; 0: the
-    // order-free fixed-point kernels, A/B only): sorted neighbour lists, their per-query
-    // {base, count}, cursors + overflow word; list entries the last call needed
-    bool normals_exact = true;       // PCP_NORMALS_EXACT=0: round 3's order-free normals (A/B)
-    bool score_wide = true;          // k_score_cells_wide for few-ray launches (PCP_SCORE_WIDE=0: A/B)
-    int64_t score_wide_rays = -1;    // PCP_SCORE_WIDE_RAYS: rays up to which it runs (A/B; -1: default)
-    int score_wide_g = 0;            // PCP_SCORE_WIDE_G: its lanes per ray, 2 / 4 / 8 / 16 (A/B; 0: default)
-    bool cells_all_ordered = false;  // PCP_CELLS_ORDER_FREE=0: every cell through the lists (A/B)
-    int nb_blocks = 0;               // PCP_NB_BLOCKS: k_nb_lists grid (A/B; 0 = kNbBlocks)
-    bool nb_small = true;            // PCP_NB_SMALL=0: 32-bit list keys below 2^16 points too (A/B)
-    int nb_region_pct = 75;          // PCP_NB_REGION_PCT: list words in the blocks' regions (rest: spill pool)
-    uint64_t nb_guess_max = 64ull << 20;   // PCP_NB_GUESS_WORDS: cap of a first list buffer (words)
+    // the normals in the reference's summation order (knob.normals_exact): sorted neighbour lists,
+    // their per-query {base, count}, cursors + overflow word; list entries the last call needed
     pcp::DevBuf nb_list, nb_meta, nb_ctl, nb_pts;   // nb_pts: input points by index
     pcp::DevBuf nb_list_c, nb_meta_c;                // the cells' lists
     pcp::DevBuf nb_sel;                              // cells left to the ordered path
@@ -338,7 +298,6 @@ struct pcp_ctx {
     bool cell_cnt_dirty = false;
     pcp::DevBuf cell_cnt2;           // the second grid's counters of build_index_pair
     bool cell_cnt2_dirty = false;
-    bool index_pair = true;          // PCP_INDEX_PAIR=0: the area's two grids by two builds (A/B)
     // the generated lattice (surface + area records, their height queries) on the device:
     // [GenPoint surf | GenPoint area | queries (G generated + n input) | area records].  It
     // depends on the parameters and the excavation pose alone; while carve_key matches, the
@@ -399,21 +358,15 @@ struct pcp_ctx {
     bool up_used[kUpRing] = {};
     int up_next = 0;
     int pin_held = -1;                       // ring slot held by pin_stage until pin_release
-    bool copy_kernel = true;                 // pinned -> device uploads by a copy kernel on the
-                                             // stream (PCP_COPY_KERNEL; 0: DMA)
-    bool zc_in = true;                       // message-sized inputs read in place from pinned
-                                             // memory (PCP_ZC_IN; 0: DMA'd first)
     pcp::PinnedBuf tc_host;                  // transform_concat / carve: records stored by the
                                              // kernels straight into pinned memory
     pcp::PinnedBuf cand_host;                // generate_candidates: poses + count in one readback
-    // host copies of message-sized buffers split over helper threads (pcp_hostcopy.hip,
-    // PCP_COPY_THREADS, default 3; 0: plain memcpy)
-    int copy_threads = 3;
-    // exclusive_scan_u32's one-pass form (PCP_SCAN_ONEPASS, default 1): the tiles' status words
+    // exclusive_scan_u32's one-pass form (knob.scan_onepass): the tiles' status words
     // (value | epoch, flag) and the ticket that orders the tiles; epoch = the call's number
-    bool scan_onepass = true;
     pcp::DevBuf scan_state;
     uint32_t scan_epoch = 0, scan_ticket = 0;
+    // host copies of message-sized buffers split over helper threads (pcp_hostcopy.hip,
+    // knob.copy_threads)
     pcp::CopyPool *copy_pool = nullptr;
     pcp::PinnedBuf cv_host;                  // pcp_crop_voxel's fast chain: centroids + result
                                              // sizes stored by the kernels (one round trip)
@@ -426,34 +379,7 @@ struct pcp_ctx {
     double steps_first = 0.0, steps_last = 0.0;   // its first and last entries (steps_K > 0)
     std::vector<double> fan_se_h;            // host copy of the cached table's sin(elevation)
     int num_cus = 256;                       // multiprocessors of the device
-    int fan_batch = 0;                       // fan kernel variant (PCP_FAN_BATCH), A/B only
-    int fan_npw = 8;                         // poses per wave of the fan kernel (PCP_FAN_NPW)
-    bool fan_cull = true;                    // launch only the rings that can reach the terrain,
-                                             // leave a pose's dead rings early (PCP_FAN_CULL)
-    bool fan_horizon_first = true;           // dispatch the live rings nearest the horizon first
-                                             // (PCP_FAN_ORDER; 0: in ring order)
-    bool fan_host_out = true;                // k_fan_reduce stores into the pinned landing
-                                             // block, no D2H copy (PCP_FAN_HOST_OUT)
-    int fm_fast = 2;                         // the filter's voxel chain (PCP_FM_FAST, filter_plan()): 2
-                                             // the bucket chain, 1 the LSD fast chain, 0 the general one
     pcp::DevBuf bk_stat;                     // the bucket chain's per-bucket words
-    int bk_gt = 0;                           // crop tiles per k_bk_group group (PCP_BK_GT; 0: one
-                                             // round of blocks)
-    bool carve_fuse_copy = true;             // the composed carve's records copied by its
-                                             // index's extraction (PCP_CARVE_FUSE_COPY)
-    bool scan_pair = true;                   // a grid pair's two one-tile scans in one launch
-                                             // (PCP_SCAN_PAIR)
-    int bk_pts = 512;                        // bucket chain: input points per bucket at least
-                                             // (PCP_BK_PTS; 0: buckets from the voxel count only)
-    bool fm_host_out = true;                 // pcp_filter_merge's result sizes stored by its
-                                             // kernels into pinned memory (PCP_FM_HOST_OUT)
-    int terrain_blocks = 1;                  // block-major terrain copy (PCP_TERRAIN_BLOCKS)
-    int fine_pack = 1;                       // fine-window entries as 12 bytes (PCP_FINE_PACK)
-    int fine_skip = 2;                       // split records' skip thresholds: 1 or 2
-    int fine_tile = 2;                       // fine records: 0 x-fastest, 1 4 x 4 tiles, 2 split
-                                             // in 8 x 8 tiles (PCP_FINE_TILE)
-    int terrain_fine = 2;                    // fine-window layout of that copy, cells of c / F
-                                             // (PCP_TERRAIN_FINE = F; 0: the 2x2x2 blocks)
     int terrain_queries = 0;                 // queries since the last pcp_set_terrain
     // filter/merge scratch
     pcp::DevBuf f_in, f_misc;
@@ -463,7 +389,6 @@ struct pcp_ctx {
     hipGraphExec_t fm_exec = nullptr;
     std::vector<uint8_t> fm_key;
     bool capturing = false;
-    bool use_graphs = true;
     // profiling
     bool prof = false;
     pcp::ProfSlot slots[PCP_K_COUNT];
@@ -684,10 +609,10 @@ int area_setup_from(pcp_ctx *ctx, const pcp_cloud_view *area, double grid_resolu
 // pcp_set_terrain over records already device-readable (raw_pre), or staged (nullptr)
 int set_terrain_from(pcp_ctx *ctx, const pcp_cloud_view *terrain, const unsigned char *raw_pre);
 
-// the context's RCCL communicator and its buffers (pcp_comm.hip), at pcp_destroy
+// the context's RCCL communicator and its events (pcp_comm.hip), by ~pcp_ctx
 void comm_release(pcp_ctx *ctx);
 // memcpy for host buffers, split over the context's helper threads from 256 KiB on
-// (pcp_hostcopy.hip); host_copy_release stops the helpers (pcp_destroy)
+// (pcp_hostcopy.hip); host_copy_release stops the helpers (~pcp_ctx)
 void host_copy(pcp_ctx *ctx, void *dst, const void *src, size_t bytes);
 void host_copy_release(pcp_ctx *ctx);
 

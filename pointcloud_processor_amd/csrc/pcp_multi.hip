@@ -241,14 +241,13 @@ int pcp_multi_create(int n_dev, const int *devices, pcp_multi **out) {
 void pcp_multi_destroy(pcp_multi *m) {
     if (!m) return;
     for (ncclComm_t c : m->comm) (void)ncclCommDestroy(c);
-    for (int r = 0; r < m->n; ++r) {
-        if (!m->ctx[r]) continue;
-        (void)hipSetDevice(m->ctx[r]->device);
-        m->keys[r].release();
-        if (r == 0) m->tmp.release();
+    // a rank's key vector goes with its device current, then its context; rank 0 last, so that
+    // `delete m` frees tmp (and the pinned landing) on rank 0's device
+    for (int r = m->n - 1; r >= 0; --r) {
+        if (m->ctx[r]) (void)hipSetDevice(m->ctx[r]->device);
+        m->keys.pop_back();
+        pcp_destroy(m->ctx[r]);
     }
-    m->host.release();
-    for (pcp_ctx *c : m->ctx) pcp_destroy(c);
     delete m;
 }
 

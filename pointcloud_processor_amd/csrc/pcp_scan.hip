@@ -315,7 +315,7 @@ int resolve_enqueue(pcp_ctx *ctx, const ScanPlan &s, const pcp_fan_params *fan, 
     }
     if (int rc = exclusive_scan_u32(ctx, cnt, wbase, nW, blk + s.tmp_off)) return rc;
     ResolveArgs a{};
-    if (ctx->terrain.present) a.g = ctx->terrain.view();
+    if (ctx->terrain.present) a.g = ctx->terrain.view(ctx->knob);
     const double *tab = ctx->fan_tab.as<const double>();
     a.ca = tab;
     a.sa = tab + fan->n_az;

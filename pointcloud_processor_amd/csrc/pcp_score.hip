@@ -888,7 +888,7 @@ k_cand_compact(const double *__restrict__ lat, int L, double *__restrict__ out, 
 static VisEnv make_env(pcp_ctx *ctx, const pcp_vl_params *p, const double *steps_d, int K) {
     VisEnv E{};
     E.terrain_present = ctx->terrain.present ? 1 : 0;
-    if (E.terrain_present) E.terrain = ctx->terrain.view();
+    if (E.terrain_present) E.terrain = ctx->terrain.view(ctx->knob);
     E.aux_present = (ctx->aux.present && ctx->aux_cloud_n > 0) ? 1 : 0;
     if (E.aux_present) E.aux = ctx->aux.view();
     E.max_distance = p->max_distance;
@@ -932,7 +932,7 @@ static CandArgs cand_args(pcp_ctx *ctx, const double bb[6], const pcp_vl_params 
                           const double zx[5], int gs) {
     CandArgs a{};
     a.ground_enabled = (ctx->terrain_cloud_n > 0 && ctx->terrain.present) ? 1 : 0;
-    if (a.ground_enabled) a.g = ctx->terrain.view();
+    if (a.ground_enabled) a.g = ctx->terrain.view(ctx->knob);
     a.gs = gs;
     const double exminx = bb[0] - p->search_radius, exmaxx = bb[1] + p->search_radius;
     const double exminy = bb[2] - p->search_radius, exmaxy = bb[3] + p->search_radius;
@@ -1037,13 +1037,13 @@ static void launch_score_cells(hipStream_t st, pcp_ctx *ctx, const VisEnv &E, in
                                double *score_z, const uint32_t *P_dev, const uint32_t *C_dev) {
     const unsigned cb = (unsigned)((C + kT - 1) / kT);
     const dim3 g(cb, (unsigned)(P + 1));
-    const uint64_t wide_rays = ctx->score_wide_rays >= 0 ? (uint64_t)ctx->score_wide_rays
+    const uint64_t wide_rays = ctx->knob.score_wide_rays >= 0 ? (uint64_t)ctx->knob.score_wide_rays
                                                          : (uint64_t)kWideMaxRays;
-    const bool wide = (uint64_t)(P + 1) * (uint64_t)C <= wide_rays && ctx->score_wide;
+    const bool wide = (uint64_t)(P + 1) * (uint64_t)C <= wide_rays && ctx->knob.score_wide;
     // the lanes per ray of the kernel that IS launched size its grid: PCP_SCORE_WIDE_G (2 / 4 /
     // 8 / 16, validated by pcp_create) with the step table in LDS, the default width past it
     // (the only instantiation there)
-    const int Gq = ctx->score_wide_g;
+    const int Gq = ctx->knob.score_wide_g;
     const int G = (E.K <= kStepLds && (Gq == 2 || Gq == 4 || Gq == 8)) ? Gq : kWideG;
     const dim3 gw((unsigned)(((uint64_t)C * G + kT - 1) / kT), (unsigned)(P + 1));
     const double *cx = ctx->cells_xyz.as<const double>();
@@ -1249,7 +1249,8 @@ int pcp_score_poses(pcp_ctx *ctx, const double *poses5, uint64_t n, const double
         return set_err(ctx, PCP_E_INVALID, "pcp_score_poses: null argument");
     if (n > 65535) return set_err(ctx, PCP_E_INVALID, "pcp_score_poses: at most 65535 poses per call");
     ScoreEnq o;
-    if (int rc = score_enqueue(ctx, poses5, n, zx, p, o, cell_flags, true, ctx->zc_in)) return rc;
+    if (int rc = score_enqueue(ctx, poses5, n, zx, p, o, cell_flags, true, ctx->knob.zc_in))
+        return rc;
     if (int rc = score_tail_sync(ctx, o)) return rc;
     prof_resolve(ctx);
     score_tail_report(ctx, o, (uint32_t)o.P, o.C, cell_flags, total_score, covered, rep);
@@ -1362,14 +1363,14 @@ int pcp_generate_and_score(pcp_ctx *ctx, const double bb[6], const pcp_vl_params
     *n_out = 0;
     const int gs = (int)std::ceil(std::sqrt((double)p->num_candidates));
     const int64_t L = gs > 0 ? (int64_t)gs * gs : 0;
-    if (pend && (L == 0 || L > 65535 || !ctx->zc_in || !PCP_ROW_SUM_LANES)) {
+    if (pend && (L == 0 || L > 65535 || !ctx->knob.zc_in || !PCP_ROW_SUM_LANES)) {
         // the two-call path needs the count on the host: settle the setup (fresh flags, :259)
         if (int rc = area_finish(ctx)) return rc;
         if (ctx->n_cells) std::memset(cell_flags, 0, ctx->n_cells);
         return pcp_generate_and_score(ctx, bb, p, zx, poses5, cap, n_out, cell_flags, total_score,
                                       covered, rep);
     }
-    if (L == 0 || L > 65535 || !ctx->zc_in) {   // the two calls (one synchronisation each)
+    if (L == 0 || L > 65535 || !ctx->knob.zc_in) {   // the two calls (one synchronisation each)
         uint64_t n = 0;
         if (int rc = pcp_generate_candidates(ctx, bb, p, zx, poses5, cap, &n)) return rc;
         *n_out = n;

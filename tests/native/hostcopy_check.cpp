@@ -19,7 +19,7 @@ int main() {
             if (std::memcmp(b.data(), a.data() + (rep % 7), n) != 0 || b[n] != 0) { std::printf("FAIL %zu\n", n); return 1; }
         }
     for (int t : {0, 3}) {
-        ctx->copy_threads = t;
+        ctx->knob.copy_threads = t;
         auto t0 = std::chrono::steady_clock::now();
         for (int rep = 0; rep < 500; ++rep) pcp::host_copy(ctx, b.data(), a.data(), 960512);
         double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count() / 500;
