@@ -836,6 +836,43 @@ int pcp_step_table(double end, double *steps, uint64_t cap, uint64_t *n);
  * run as one look-back pass (PCP_SCAN_ONEPASS, default 1), others as three launches. */
 int pcp_debug_exclusive_scan(pcp_ctx *ctx, const uint32_t *in, uint64_t n, uint32_t *out);
 
+/* Test infrastructure: the device's own arithmetic, element by element (one thread per element),
+ * through the same device functions the production kernels call (tests/test_device_math_gpu.py).
+ * a, b and out are host arrays of n elements of the op's types; b is read only by the ops that
+ * name it and aux is written only by PCP_MATH_SCORE_SIN_PART (both may be NULL elsewhere).
+ * n == 0 succeeds; a NULL ctx / a / out, a NULL b or aux where the op uses it, and an unknown op
+ * give PCP_E_INVALID.
+ *   double -> double (pcp_crmath.h; the scoring and the candidate generator):
+ *     SCORE_SIN_PART  evaluateCellScore's sin(pi / 2 - acos(a)) as eval_cell computes it;
+ *                     aux[i] = 1 when the fast phase decided, 2 when the exact phase did
+ *     ACOS_RAW        ocml's acos(a), the composite's first result
+ *     ATAN2_RAW       ocml's atan2(a, b), the candidate angles' first result
+ *     ATAN2_CR        pcp_cr_atan2_fix(a, b, atan2(a, b)), the candidate generator's expression
+ *   float -> float (pcp_libm.h; the PCA normals): ATAN2F (a, b), SINF, COSF, DIVF a / b, SQRTF
+ *   bare double operations: F64_DIV a / b, F64_SQRT, F64_TO_F32 (out: float), F64_FMA
+ *     fma(a[i], b[2 i], b[2 i + 1]) (b: 2 n doubles), F64_NEXTAFTER nextafter(a, b),
+ *     F64_NEARBYINT
+ *   NORMAL            a: n float covariances of 9 (row-major 3 x 3), b: n query points of 3,
+ *                     out: n float normals of 3 -- computeTerrainNormals' eigen33 and two flips */
+#define PCP_MATH_SCORE_SIN_PART 1
+#define PCP_MATH_ACOS_RAW 2
+#define PCP_MATH_ATAN2_RAW 3
+#define PCP_MATH_ATAN2_CR 4
+#define PCP_MATH_ATAN2F 10
+#define PCP_MATH_SINF 11
+#define PCP_MATH_COSF 12
+#define PCP_MATH_DIVF 13
+#define PCP_MATH_SQRTF 14
+#define PCP_MATH_F64_DIV 20
+#define PCP_MATH_F64_SQRT 21
+#define PCP_MATH_F64_TO_F32 22
+#define PCP_MATH_F64_FMA 23
+#define PCP_MATH_F64_NEXTAFTER 24
+#define PCP_MATH_F64_NEARBYINT 25
+#define PCP_MATH_NORMAL 30
+int pcp_debug_math(pcp_ctx *ctx, int op, const void *a, const void *b, uint64_t n, void *out,
+                   int32_t *aux);
+
 /* Test infrastructure: the terrain's fine-window copy read back exactly as
  * it lies on the device, with every value its build kernels received as a parameter.  Two calls,
  * as elsewhere: with frec, wpts and pts all NULL it fills *geo only (the byte sizes among it);

@@ -172,6 +172,11 @@ void orc_fan_tables(int32_t n_az, int32_t n_el, double el_min, double el_max,
 void orc_area_normals(const float *pts, int64_t n, int64_t stride_floats, double radius,
                       float *normals3);
 
+/* The normal of computeTerrainNormals from a given covariance (test infrastructure): pcl::eigen33's
+ * smallest eigenvector of each of the n float covariances (cov9: row-major 3 x 3), flipped
+ * towards the viewpoint (0,0,0) as seen from the query point q3, then to normal_z >= 0. */
+void orc_normal_from_cov(const float *cov9, const float *q3, int64_t n, float *normals3);
+
 /* generateExcavationGrid3D (:236-287) with isPointNearExcavation (radius 1.5 * resolution)
  * and computeCellSurfaceNormal (:301-340) from area_normals3 (NULL: default (0,0,1)).
  * Cells in the reference's loop order (rows i over y, columns j over x, layers k).  Returns

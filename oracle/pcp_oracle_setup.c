@@ -137,6 +137,26 @@ static void eigen33_min(const float cov[3][3], float ev[3]) {
     for (int a = 0; a < 3; ++a) ev[a] = v[a] / s;
 }
 
+/* flipNormalTowardsViewpoint with the viewpoint (0,0,0), then computeTerrainNormals' normal_z >= 0 */
+static void flip_normal(const float q[3], float ev[3]) {
+    const float ct = (0.0f - q[0]) * ev[0] + (0.0f - q[1]) * ev[1] + (0.0f - q[2]) * ev[2];
+    if (ct < 0.0f)
+        for (int a = 0; a < 3; ++a) ev[a] = -ev[a];
+    if (ev[2] < 0.0f)
+        for (int a = 0; a < 3; ++a) ev[a] = -ev[a];
+}
+
+void orc_normal_from_cov(const float *cov9, const float *q3, int64_t n, float *normals3) {
+    for (int64_t i = 0; i < n; ++i) {
+        float cov[3][3], ev[3];
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) cov[r][c] = cov9[9 * i + 3 * r + c];
+        eigen33_min(cov, ev);
+        flip_normal(q3 + 3 * i, ev);
+        for (int a = 0; a < 3; ++a) normals3[3 * i + a] = ev[a];
+    }
+}
+
 void orc_area_normals(const float *pts, int64_t n, int64_t stride_floats, double radius,
                       float *normals3) {
     nb_t *nb = (nb_t *)malloc(sizeof(nb_t) * (size_t)(n > 0 ? n : 1));
@@ -177,13 +197,7 @@ void orc_area_normals(const float *pts, int64_t n, int64_t stride_floats, double
         cov[2][1] = cov[1][2];
         float ev[3];
         eigen33_min(cov, ev);
-        /* flipNormalTowardsViewpoint, viewpoint (0,0,0) */
-        const float ct = (0.0f - q[0]) * ev[0] + (0.0f - q[1]) * ev[1] + (0.0f - q[2]) * ev[2];
-        if (ct < 0.0f)
-            for (int a = 0; a < 3; ++a) ev[a] = -ev[a];
-        /* computeTerrainNormals: normal_z >= 0 */
-        if (ev[2] < 0.0f)
-            for (int a = 0; a < 3; ++a) ev[a] = -ev[a];
+        flip_normal(q, ev);
         o[0] = ev[0];
         o[1] = ev[1];
         o[2] = ev[2];

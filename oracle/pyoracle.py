@@ -71,6 +71,7 @@ _SIGS = [
                                   C.c_double, C.c_double, _P, _P, _P, _P]),
     ("orc_fan_tables", None, [C.c_int32, C.c_int32, C.c_double, C.c_double, _P, _P, _P, _P]),
     ("orc_area_normals", None, [_P, C.c_int64, C.c_int64, C.c_double, _P]),
+    ("orc_normal_from_cov", None, [_P, _P, C.c_int64, _P]),
     ("orc_terrain_height", C.c_double, [_P, C.c_int64, C.c_int64, C.c_double, C.c_double,
                                         C.c_double]),
     ("orc_drivable_area", None, [_P, C.c_int64, C.c_int64, _P, _P, C.c_double, C.c_double,
@@ -352,6 +353,17 @@ def area_normals(pts, radius=1.5):
     a = _f32(pts)
     out = np.empty((a.shape[0], 3), np.float32)
     lib().orc_area_normals(_p(a), a.shape[0], a.shape[1], float(radius), _p(out))
+    return out
+
+
+def normal_from_cov(cov, q):
+    """computeTerrainNormals' normal of each (n, 9) float32 covariance (row-major 3 x 3) seen
+    from the query points q (n, 3): eigen33's smallest eigenvector and the two flips -> (n, 3)."""
+    c = np.ascontiguousarray(cov, np.float32).reshape(-1, 9)
+    qq = np.ascontiguousarray(q, np.float32).reshape(-1, 3)
+    assert c.shape[0] == qq.shape[0]
+    out = np.empty((c.shape[0], 3), np.float32)
+    lib().orc_normal_from_cov(_p(c), _p(qq), c.shape[0], _p(out))
     return out
 
 

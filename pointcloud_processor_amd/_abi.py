@@ -24,6 +24,13 @@ PCP_E_NOMEM = -5
 
 MAX_STEPS = 4096   # PCP_MAX_STEPS of include/pcp_abi.h: the longest step table a query marches
 
+# pcp_debug_math's ops (PCP_MATH_* of include/pcp_abi.h)
+MATH_SCORE_SIN_PART, MATH_ACOS_RAW, MATH_ATAN2_RAW, MATH_ATAN2_CR = 1, 2, 3, 4
+MATH_ATAN2F, MATH_SINF, MATH_COSF, MATH_DIVF, MATH_SQRTF = 10, 11, 12, 13, 14
+(MATH_F64_DIV, MATH_F64_SQRT, MATH_F64_TO_F32, MATH_F64_FMA, MATH_F64_NEXTAFTER,
+ MATH_F64_NEARBYINT) = 20, 21, 22, 23, 24, 25
+MATH_NORMAL = 30
+
 PCP_MEM_DEVICE_IN = 1
 PCP_MEM_DEVICE_OUT = 2
 
@@ -263,6 +270,7 @@ _SIGS = [
     ("pcp_simulate_scan_mounted_burst", C.c_int, [_P, _P, C.c_uint64, C.POINTER(FanParams), _P,
                                                   C.c_int, _P]),
     ("pcp_debug_exclusive_scan", C.c_int, [_P, _P, C.c_uint64, _P]),
+    ("pcp_debug_math", C.c_int, [_P, C.c_int, _P, _P, C.c_uint64, _P, _P]),
     ("pcp_debug_fine_copy", C.c_int, [_P, C.POINTER(FineGeo), _P, C.c_uint64, _P, C.c_uint64, _P,
                                       C.c_uint64]),
     ("pcp_debug_fine_pivot", C.c_int, [_P, C.POINTER(FinePivotGeo), _P, C.c_uint64]),
@@ -944,6 +952,30 @@ class Context:
         self._check(self.lib.pcp_debug_exclusive_scan(self.h, _ptr(a), a.size, _ptr(out)),
                     "pcp_debug_exclusive_scan")
         return out
+
+    def debug_math(self, op: int, a: np.ndarray, b: np.ndarray | None = None):
+        """pcp_debug_math: op (MATH_*) element-wise on the device through the production device
+        functions.  float64 ops take float64 arrays, the float libm ops and MATH_NORMAL (a: (n, 9)
+        covariances, b: (n, 3) query points -> (n, 3)) float32; MATH_F64_FMA takes b (n, 2).
+        Returns out, or (out, phase int32) for MATH_SCORE_SIN_PART."""
+        f32 = op in (MATH_ATAN2F, MATH_SINF, MATH_COSF, MATH_DIVF, MATH_SQRTF, MATH_NORMAL)
+        dt = np.float32 if f32 else np.float64
+        a = np.ascontiguousarray(a, dt)
+        n = a.shape[0]
+        if b is not None:
+            b = np.ascontiguousarray(b, dt)
+            if b.shape[0] != n:
+                raise ValueError("debug_math: a and b differ in length")
+        if op == MATH_NORMAL and (a.shape != (n, 9) or b is None or b.shape != (n, 3)):
+            raise ValueError("debug_math: MATH_NORMAL takes a (n, 9) and b (n, 3)")
+        if op == MATH_F64_FMA and (b is None or b.shape != (n, 2)):
+            raise ValueError("debug_math: MATH_F64_FMA takes b (n, 2)")
+        out = np.zeros((n, 3) if op == MATH_NORMAL else n,
+                       np.float32 if f32 or op == MATH_F64_TO_F32 else np.float64)
+        aux = np.zeros(n, np.int32) if op == MATH_SCORE_SIN_PART else None
+        self._check(self.lib.pcp_debug_math(self.h, op, _ptr(a), _ptr(b), n, _ptr(out), _ptr(aux)),
+                    "pcp_debug_math")
+        return (out, aux) if aux is not None else out
 
     def debug_fine_copy(self):
         """pcp_debug_fine_copy: the terrain's fine-window copy as built -> (geo dict, frec uint8,

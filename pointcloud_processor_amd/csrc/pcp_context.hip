@@ -629,6 +629,60 @@ extern "C" int pcp_debug_exclusive_scan(pcp_ctx *ctx, const uint32_t *in, uint64
     return PCP_OK;
 }
 
+// the device's own arithmetic on host arrays (diagnostic entry point, pcp_abi.h: the probe
+// kernels live with the device functions they call, tests/test_device_math_gpu.py)
+extern "C" int pcp_debug_math(pcp_ctx *ctx, int op, const void *a, const void *b, uint64_t n,
+                              void *out, int32_t *aux) {
+    using namespace pcp;
+    // bytes per element of a, b (0: not read) and out; whether aux is written; the float source
+    size_t sa = 8, sb = 0, so = 8;
+    bool use_aux = false, f32 = false;
+    switch (op) {
+    case PCP_MATH_SCORE_SIN_PART: use_aux = true; break;
+    case PCP_MATH_ACOS_RAW:
+    case PCP_MATH_F64_SQRT:
+    case PCP_MATH_F64_NEARBYINT: break;
+    case PCP_MATH_ATAN2_RAW:
+    case PCP_MATH_ATAN2_CR:
+    case PCP_MATH_F64_DIV:
+    case PCP_MATH_F64_NEXTAFTER: sb = 8; break;
+    case PCP_MATH_F64_TO_F32: so = 4; break;
+    case PCP_MATH_F64_FMA: sb = 16; break;
+    case PCP_MATH_ATAN2F:
+    case PCP_MATH_DIVF: f32 = true; sa = sb = so = 4; break;
+    case PCP_MATH_SINF:
+    case PCP_MATH_COSF:
+    case PCP_MATH_SQRTF: f32 = true; sa = so = 4; break;
+    case PCP_MATH_NORMAL: f32 = true; sa = 36; sb = so = 12; break;
+    default: return ctx ? set_err(ctx, PCP_E_INVALID, "pcp_debug_math: unknown op %d", op)
+                        : PCP_E_INVALID;
+    }
+    if (!ctx) return PCP_E_INVALID;
+    if (n == 0) return PCP_OK;
+    if (!a || !out || (sb && !b) || (use_aux && !aux))
+        return set_err(ctx, PCP_E_INVALID, "pcp_debug_math: null array");
+    if (n > (1ull << 24)) return set_err(ctx, PCP_E_INVALID, "pcp_debug_math: n above 2^24");
+    PCP_HIP(ctx, hipSetDevice(ctx->device));
+    DevBuf da, db, dout, daux;   // (an early return frees them)
+    PCP_HIP(ctx, da.ensure(n * sa));
+    PCP_HIP(ctx, db.ensure(n * (sb ? sb : 1)));
+    PCP_HIP(ctx, dout.ensure(n * so));
+    PCP_HIP(ctx, daux.ensure(n * sizeof(int32_t)));
+    PCP_HIP(ctx, hipMemcpyAsync(da.p, a, n * sa, hipMemcpyHostToDevice, ctx->stream));
+    if (sb) PCP_HIP(ctx, hipMemcpyAsync(db.p, b, n * sb, hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = f32 ? debug_math_f32(ctx, op, da.as<const float>(), db.as<const float>(), n,
+                                      dout.as<float>())
+                     : debug_math_f64(ctx, op, da.as<const double>(), db.as<const double>(), n,
+                                      dout.p, daux.as<int32_t>()))
+        return rc;
+    PCP_HIP(ctx, hipMemcpyAsync(out, dout.p, n * so, hipMemcpyDeviceToHost, ctx->stream));
+    if (use_aux)
+        PCP_HIP(ctx, hipMemcpyAsync(aux, daux.p, n * sizeof(int32_t), hipMemcpyDeviceToHost,
+                                    ctx->stream));
+    PCP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return PCP_OK;
+}
+
 namespace pcp {
 // exclusive_scan_u32 of two arrays (out2 / zero2 as there, no preset); two one-tile scans
 // (a message-sized cloud's pair of grids) are one launch

@@ -1,10 +1,14 @@
-/* pcp_crmath.h -- correctly rounded double atan2 from a faithful first result, for the device
- * (ocml's atan2 is within an ulp; glibc's, which the reference and the oracle call, rounds
- * correctly in all but rare cases -- tools/libm_cr_check.py).  C and HIP (host + device) from
- * one text: the CPU suite checks it against the running glibc (tests/test_crmath.py).
+/* pcp_crmath.h -- correctly rounded double atan2 from a nearby first result, for the device
+ * (ocml's atan2; glibc's, which the reference and the oracle call, rounds correctly in all but
+ * rare cases -- tools/libm_cr_check.py).  C and HIP (host + device) from one text: the CPU suite
+ * checks it against the running glibc (tests/test_crmath.py) and against an exact reference
+ * with no allowance (tests/test_crmath_exact.py), the GPU suite checks the device build against
+ * the same reference (tests/test_device_math_gpu.py).
  *
- * pcp_cr_atan2_fix(y, x, r): r is atan2(y, x) to within one ulp.  The true angle t lies between
- * r's neighbours; it is compared with the two midpoints m = r -+ ulp / 2 through the sign of
+ * pcp_cr_atan2_fix(y, x, r): r is atan2(y, x) to within a few ulps (ocml's: up to 1.45 of the
+ * true angle, within one of the correctly rounded one).  The true angle t is compared with the
+ * two midpoints m = r -+ ulp / 2 of r and its neighbours, and with the next midpoint on while t
+ * lies beyond one (up to PCP_CR_ATAN2_STEPS doubles from r), through the sign of
  *     sin(t - m) = (y cos m - x sin m) / |(x, y)|
  * with cos m and sin m in double-double (Cody-Waite reduction by pi / 2 in three parts, Taylor
  * series to t^31 for |t| <= pi / 4), so the sign is decided unless t lies within ~2^-100 of a
@@ -160,30 +164,46 @@ PCP_CR int pcp_cr_side(double y, double x, pcp_dd m) {
     return (v > 0.0) - (v < 0.0);
 }
 
+/* ocml's atan2 is up to 1.45 ulps from the true angle (measured, tests/test_device_math_gpu.py),
+ * and one pair of midpoint tests is right only up to 1.5: the tests walk on from the neighbour
+ * they point to, up to PCP_CR_ATAN2_STEPS doubles away, all from the one sin / cos at r */
+#define PCP_CR_ATAN2_STEPS 4
 PCP_CR double pcp_cr_atan2_fix(double y, double x, double r) {
     if (!(isfinite(y) && isfinite(x) && isfinite(r)) || y == 0.0 || x == 0.0 || r == 0.0)
         return r;
     /* angles near the underflow range (|y / x| < 2^-900): the double-double terms underflow */
     if (fabs(r) < 0x1p-900) return r;
-    const double lo = nextafter(r, -INFINITY), hi = nextafter(r, INFINITY);
-    /* sin / cos at r once; at the midpoints m = r + h (h = half the exact gap to a neighbour)
-     * sin m = S + h C - h^2 / 2 S, cos m = C - h S - h^2 / 2 C (the h^3 terms are ~2^-160) */
+    /* the angle does not change under a common power of two: the larger of |y|, |x| to [1, 2), so
+     * that the products below keep their low words (those of a y near the subnormal range
+     * underflowed: tests/test_crmath_exact.py) and cannot overflow.  Exact but for a y or x that
+     * leaves the normal range, which then lies 2^-1000 below the other and decides nothing. */
+    int ex;
+    (void)frexp(fmax(fabs(y), fabs(x)), &ex);
+    y = ldexp(y, 1 - ex);
+    x = ldexp(x, 1 - ex);
+    /* sin / cos at r once; at a midpoint m = r + h (h a few half ulps, exact)
+     * sin m = S + h C - h^2 / 2 S, cos m = C - h S - h^2 / 2 C (the h^3 terms are ~2^-150) */
     pcp_dd S, C;
     pcp_dd_sincos(pcp_dd_make(r, 0.0), &S, &C);
     const pcp_dd yC = pcp_dd_mul_d(C, y), xS = pcp_dd_mul_d(S, x);
     const pcp_dd yS = pcp_dd_mul_d(S, y), xC = pcp_dd_mul_d(C, x);
     const pcp_dd e0 = pcp_dd_add(yC, pcp_dd_neg(xS));   /* y cos r - x sin r */
     const pcp_dd e1 = pcp_dd_add(yS, xC);               /* d/dh of -(y cos m - x sin m) */
-    for (int side = 0; side < 2; ++side) {
-        const double h = 0.5 * ((side ? hi : lo) - r);
-        /* y cos m - x sin m = e0 - h e1 - h^2 / 2 e0 */
-        pcp_dd e = pcp_dd_add(e0, pcp_dd_neg(pcp_dd_mul_d(e1, h)));
-        e = pcp_dd_add(e, pcp_dd_make(-0.5 * h * h * e0.hi, 0.0));
-        const double v = e.hi != 0.0 ? e.hi : e.lo;
-        if (side == 0 && v < 0.0) return lo;
-        if (side == 1 && v > 0.0) return hi;
-    }
-    return r;
+    /* downwards while the angle lies below the midpoint under cur; if it never did, upwards
+     * while it lies above the midpoint over cur */
+    double cur = r;
+    for (int up = 0; up < 2 && cur == r; ++up)
+        for (int step = 0; step < PCP_CR_ATAN2_STEPS; ++step) {
+            const double nb = nextafter(cur, up ? INFINITY : -INFINITY);
+            const double h = 0.5 * (nb - r) + 0.5 * (cur - r);   /* (cur + nb) / 2 - r */
+            /* y cos m - x sin m = e0 - h e1 - h^2 / 2 e0 */
+            pcp_dd e = pcp_dd_add(e0, pcp_dd_neg(pcp_dd_mul_d(e1, h)));
+            e = pcp_dd_add(e, pcp_dd_make(-0.5 * h * h * e0.hi, 0.0));
+            const double v = e.hi != 0.0 ? e.hi : e.lo;
+            if (up ? !(v > 0.0) : !(v < 0.0)) break;
+            cur = nb;
+        }
+    return cur;
 }
 
 /* acos(d) for 0 < d < 1 from a faithful first result r: acos is decreasing, so the true angle

@@ -1568,3 +1568,42 @@ int pcp_diag_nb_stamps(pcp_ctx *ctx, int which, unsigned long long *out, size_t 
 #endif
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------
+// pcp_debug_math's float ops: one thread per element through pcp_libm.h's functions as
+// computeRoots / eigen33_min call them, and normal_from_cov itself on a given covariance
+// ---------------------------------------------------------------------------------------
+namespace pcp {
+
+__global__ void __launch_bounds__(256)
+k_debug_math_f32(int op, const float *__restrict__ a, const float *__restrict__ b, uint64_t n,
+                 float *__restrict__ out) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    switch (op) {
+    case PCP_MATH_ATAN2F: out[i] = pcp_atan2f(a[i], b[i]); break;
+    case PCP_MATH_SINF: out[i] = pcp_sinf(a[i]); break;
+    case PCP_MATH_COSF: out[i] = pcp_cosf(a[i]); break;
+    case PCP_MATH_DIVF: out[i] = pcp_lm_div(a[i], b[i]); break;
+    case PCP_MATH_SQRTF: out[i] = pcp_lm_sqrt(a[i]); break;
+    case PCP_MATH_NORMAL: {
+        float cov[3][3];
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) cov[r][c] = a[9 * i + 3 * r + c];
+        float nrm[3];
+        normal_from_cov(cov, b[3 * i], b[3 * i + 1], b[3 * i + 2], nrm);
+        for (int c = 0; c < 3; ++c) out[3 * i + c] = nrm[c];
+        break;
+    }
+    default: break;
+    }
+}
+
+int debug_math_f32(pcp_ctx *ctx, int op, const float *a, const float *b, uint64_t n, float *out) {
+    hipLaunchKernelGGL(k_debug_math_f32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                       ctx->stream, op, a, b, n, out);
+    PCP_CHECK_LAUNCH(ctx);
+    return PCP_OK;
+}
+
+}  // namespace pcp

@@ -479,6 +479,13 @@ int exclusive_scan_u32_pair(pcp_ctx *ctx, const uint32_t *in_a, uint32_t *out_a,
                             uint32_t *out2_a, const uint32_t *in_b, uint32_t *out_b, uint64_t n_b,
                             uint32_t *out2_b, void *tmp, bool zero2);
 
+// pcp_debug_math's element-wise probes, enqueued on ctx->stream by the source that owns the
+// probed device functions: the double ops (pcp_score.hip) and the float libm / normal ops
+// (pcp_excav.hip).  Device pointers, n > 0 and a known op are the caller's to ensure.
+int debug_math_f64(pcp_ctx *ctx, int op, const double *a, const double *b, uint64_t n, void *out,
+                   int32_t *aux);
+int debug_math_f32(pcp_ctx *ctx, int op, const float *a, const float *b, uint64_t n, float *out);
+
 // fan query up to the per-pose sums, enqueued on ctx->stream (pcp_fan.hip): device results
 // in flight on return, the caller synchronizes.  n > 0.
 struct FanEnq {

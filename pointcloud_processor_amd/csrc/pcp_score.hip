@@ -830,8 +830,9 @@ __global__ void __launch_bounds__(kCandT) k_candidates(CandArgs a) {
         out[0] = 0.0;
         return;
     }
-    // glibc's atan2 (the reference's) rounds correctly but for rare near-ties; ocml's is within
-    // an ulp: pcp_cr_atan2_fix rounds it correctly (pcp_crmath.h, tests/test_crmath.py)
+    // glibc's atan2 (the reference's) rounds correctly but for rare near-ties; ocml's is up to
+    // 1.45 ulps off: pcp_cr_atan2_fix rounds it correctly (pcp_crmath.h, tests/test_crmath.py,
+    // tests/test_device_math_gpu.py)
     const double elev = pcp_cr_atan2_fix(-dz, hd, atan2(-dz, hd));
     if (elev >= kMinElevation && elev <= kMaxElevation) {
         out[0] = 1.0;
@@ -1419,3 +1420,48 @@ int pcp_generate_and_score(pcp_ctx *ctx, const double bb[6], const pcp_vl_params
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------
+// pcp_debug_math's double ops: one thread per element through the functions above -- the
+// scoring's composite as eval_cell calls it, ocml's first results, the candidate generator's
+// angle expression -- and the bare double operations the exactness arguments rest on
+// ---------------------------------------------------------------------------------------
+namespace pcp {
+
+__global__ void __launch_bounds__(256)
+k_debug_math_f64(int op, const double *__restrict__ a, const double *__restrict__ b, uint64_t n,
+                 void *__restrict__ out, int32_t *__restrict__ aux) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double x = a[i];
+    double *o = static_cast<double *>(out);
+    switch (op) {
+    case PCP_MATH_SCORE_SIN_PART: {
+        o[i] = score_sin_part(x);
+        int ph = 0;   // the phase: the same call with the phase asked for
+        (void)pcp_score_sin_part(x, acos(x), &ph);
+        aux[i] = ph;
+        break;
+    }
+    case PCP_MATH_ACOS_RAW: o[i] = acos(x); break;
+    case PCP_MATH_ATAN2_RAW: o[i] = atan2(x, b[i]); break;
+    case PCP_MATH_ATAN2_CR: o[i] = pcp_cr_atan2_fix(x, b[i], atan2(x, b[i])); break;
+    case PCP_MATH_F64_DIV: o[i] = x / b[i]; break;
+    case PCP_MATH_F64_SQRT: o[i] = sqrt(x); break;
+    case PCP_MATH_F64_TO_F32: static_cast<float *>(out)[i] = (float)x; break;
+    case PCP_MATH_F64_FMA: o[i] = fma(x, b[2 * i], b[2 * i + 1]); break;
+    case PCP_MATH_F64_NEXTAFTER: o[i] = nextafter(x, b[i]); break;
+    case PCP_MATH_F64_NEARBYINT: o[i] = nearbyint(x); break;
+    default: break;
+    }
+}
+
+int debug_math_f64(pcp_ctx *ctx, int op, const double *a, const double *b, uint64_t n, void *out,
+                   int32_t *aux) {
+    hipLaunchKernelGGL(k_debug_math_f64, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                       ctx->stream, op, a, b, n, out, aux);
+    PCP_CHECK_LAUNCH(ctx);
+    return PCP_OK;
+}
+
+}  // namespace pcp

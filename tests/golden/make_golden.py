@@ -7,6 +7,9 @@ tests/test_oracle.py cross-checks the restatement with independent numpy/scipy c
 Inputs are stored in the fixtures, so the GPU parity tests consume exactly these bytes.
 
     python tests/golden/make_golden.py
+
+cr_hard_cases.npz is not made here (it needs no oracle, and a 2^24-argument long-double screen):
+    python tools/gen/cr_hard_cases.py
 """
 import math
 import sys

@@ -1,0 +1,458 @@
+"""The device's own arithmetic, element by element (pcp_debug_math: the same device functions
+the production kernels call, compiled by hipcc for gfx950), against
+  * the exact reference tests/cr_ref.py -- the scoring's sin(pi / 2 - acos(d)) and the candidate
+    generator's atan2: bit-equal, zero mismatches, zero undecided;
+  * the exact reference again for ocml's raw acos / atan2: the true value lies between the raw
+    result's neighbours, the precondition of pcp_crmath.h's fixes;
+  * the gcc build of pcp_libm.h (which tests/test_libm.py ties to glibc) -- float atan2f / sinf /
+    cosf, divide and square root;
+  * numpy and exact rationals -- the bare double operations the exactness arguments rest on;
+  * the oracle's exported eigen33 / normal_from_cov on constructed covariances.
+
+Measured on an MI355X (ROCm 7.2), printed by each run:
+  * composite and candidate atan2: 0 mismatches, 0 undecided (53,258 d; 30,728 pairs);
+  * ocml acos: worst 0.68 ulps of the true value, 6.5 % of the raw results not the correctly
+    rounded double (28 % of the hard cases);
+  * ocml atan2: worst 1.45 ulps of the true angle (metre-scale pairs; 1.27 at ratios 2^+-40),
+    23 % not correctly rounded -- not within one ulp of the true angle, as the header had
+    assumed, though every raw result is within one ulp of the correctly rounded double;
+  * the exact phase: 2,092 of the 4,096 hard cases on the device and on the host build alike;
+    3 of 32,768 uniform d on the device, 9 of 98,304 on the host build (9.2e-5 both);
+  * float libm, divide, square root, the bare double operations and the normals: 0 mismatches.
+"""
+import math
+from fractions import Fraction
+
+import numpy as np
+import pytest
+
+import cr_ref
+import devmath
+from pointcloud_processor_amd import _abi
+
+pytestmark = pytest.mark.gpu
+
+N = 1 << 14
+FLT_EPS = float(np.finfo(np.float32).eps)
+FLT_MIN = float(np.finfo(np.float32).tiny)
+
+
+@pytest.fixture(scope="module")
+def host(tmp_path_factory):
+    return devmath.HostMath(tmp_path_factory.mktemp("devmath_gpu"))
+
+
+@pytest.fixture(scope="module")
+def hard():
+    return devmath.hard_cases()
+
+
+def composite_inputs(hard):
+    """d of the composite: uniform (0, 1), (2^-20, 0.01), (0.99, 1), the edges, the hard cases."""
+    f = devmath.spa_families(N)
+    p = 2.0 ** -20
+    edges = np.array([0.0, 1.0, p, np.nextafter(p, 0), np.nextafter(p, 1), np.nextafter(1.0, 0),
+                      5e-324, 2.0 ** -1030, 0.5, np.nextafter(0.0, 1) * 3])
+    return {"uniform": f["uniform"], "small": f["small"], "near_one": f["near_one"],
+            "edges": edges, "hard": np.concatenate([hard["acos_d"], hard["spa_d"]])}
+
+
+def atan2_inputs(hard):
+    """(y, x) of the candidate generator's angles: metre-scale pairs in +-60 (all quadrants),
+    ratios 2^+-40, a level sensor's |dz| << hd, the hard cases."""
+    f = devmath.atan2_families(N)
+    g = np.random.default_rng(0x1E7E1)
+    n = N // 4
+    level = (g.uniform(-1e-7, 1e-7, n) * np.exp2(g.integers(-20, 1, n)),
+             g.uniform(0.1, 60.0, n))
+    quad = (np.array([3.0, 3.0, -3.0, -3.0, 1e-9, -1e-9, 60.0, -60.0]),
+            np.array([4.0, -4.0, 4.0, -4.0, -7.0, -7.0, 1e-9, -1e-9]))
+    return {"metres": f["metres"], "ratios": (f["ratios"][0][:N // 2], f["ratios"][1][:N // 2]),
+            "level": level, "quadrants": quad, "hard": (hard["atan2_y"], hard["atan2_x"])}
+
+
+def _first_results(name, raw, exact, fixed, args, strict):
+    """ocml's raw results against the exact reference -> (worst |raw - true| in ulps, share not
+    correctly rounded).  Asserts |raw - exact| <= 1 ulp: raw is the correctly rounded double or
+    one of its neighbours; strict: also that the true value lies between raw's own neighbours.
+    Only the raw values that are not the correctly rounded one need the fixed-point value again
+    (the others are within half an ulp)."""
+    off = np.nonzero(~devmath.bit_equal(raw, exact))[0]
+    near = devmath.bit_equal(raw, devmath.moved(exact, 1)) | devmath.bit_equal(raw, devmath.moved(exact, -1))
+    worst = 0.5 if off.size < raw.size else 0.0
+    for i in off:
+        v, prec = fixed(*(float(a[i]) for a in args))
+        u = cr_ref.ulps_off(float(raw[i]), v, prec)
+        worst = max(worst, u)
+        assert near[i] and (not strict or cr_ref.brackets(float(raw[i]), v, prec)), \
+            f"{name}: raw {float(raw[i]).hex()} of {[float(a[i]).hex() for a in args]} is " \
+            f"{u:.3f} ulps from the true value, exact {float(exact[i]).hex()}"
+    return worst, off.size / raw.size
+
+
+def test_score_composite_bit_equal_exact(gpu, hard):
+    """score_sin_part(d) as eval_cell calls it == cr_ref.cr_score_sin_part(d), every d."""
+    for name, d in composite_inputs(hard).items():
+        exact, und = devmath.exact_score_sin_part(d)
+        assert und == 0, f"{name}: {und} undecided"
+        got, ph = gpu.debug_math(_abi.MATH_SCORE_SIN_PART, d)
+        bad = ~devmath.bit_equal(got, exact)
+        print(f"composite {name}: {int(bad.sum())} of {d.size} differ, phase 2: "
+              f"{int((ph == 2).sum())}")
+        assert set(np.unique(ph)) <= {1, 2}
+        assert not bad.any(), (name, d[bad][:4], got[bad][:4], exact[bad][:4])
+
+
+def test_candidate_atan2_bit_equal_exact(gpu, hard):
+    """pcp_cr_atan2_fix(y, x, atan2(y, x)) == cr_ref.cr_atan2(y, x); with a zero argument the
+    fix returns ocml's value, which must be the C99 one (numpy's)."""
+    for name, (y, x) in atan2_inputs(hard).items():
+        exact, und = devmath.exact_atan2(y, x)
+        assert und == 0, f"{name}: {und} undecided"
+        got = gpu.debug_math(_abi.MATH_ATAN2_CR, y, x)
+        bad = ~devmath.bit_equal(got, exact)
+        print(f"atan2 {name}: {int(bad.sum())} of {y.size} differ")
+        assert not bad.any(), (name, y[bad][:4], x[bad][:4], got[bad][:4], exact[bad][:4])
+    y = np.array([0.0, -0.0, 0.0, -0.0, 2.5, -2.5, 2.5, -2.5, 0.0, -0.0, 0.0, -0.0])
+    x = np.array([3.0, 3.0, -3.0, -3.0, 0.0, 0.0, -0.0, -0.0, 0.0, 0.0, -0.0, -0.0])
+    for op in (_abi.MATH_ATAN2_CR, _abi.MATH_ATAN2_RAW):
+        assert devmath.bit_equal(gpu.debug_math(op, y, x), np.arctan2(y, x)).all()
+    assert devmath.bit_equal(np.arctan2(y, x),
+                             np.array([cr_ref.cr_atan2(*t) for t in zip(y, x)])).all()
+
+
+def test_ocml_acos_is_faithful(gpu, hard):
+    """ocml's acos(d), the first result of the scoring's composite: the true value lies between
+    the raw result's two neighbours (|raw - exact| <= 1 ulp), the precondition of
+    pcp_cr_acos_fix and of phase 1, for every d of the composite test.  Measured on gfx950 /
+    ROCm 7.2: worst 0.68 ulps of the true value; 6.5 % of the raw results are not the correctly
+    rounded double (28 % of the hard cases)."""
+    worst, share, n = 0.0, 0.0, 0
+    for name, d in composite_inputs(hard).items():
+        d = d[(d > 0.0) & (d < 1.0)]
+        exact, _ = devmath.exact_acos(d)
+        raw = gpu.debug_math(_abi.MATH_ACOS_RAW, d)
+        w, s = _first_results("acos " + name, raw, exact, cr_ref.acos_fixed, (d,), strict=True)
+        print(f"ocml acos {name}: worst {w:.4f} ulps, not correctly rounded {s:.4f}")
+        worst, share, n = max(worst, w), share + s * d.size, n + d.size
+    print(f"ocml acos: worst {worst:.4f} ulps, not correctly rounded {share / n:.4f}")
+    # acos(0) and acos(1), which the composite passes through unchanged
+    assert devmath.bit_equal(gpu.debug_math(_abi.MATH_ACOS_RAW, np.array([0.0, 1.0])),
+                             np.array([math.pi / 2, 0.0])).all()
+
+
+def test_ocml_atan2_is_within_an_ulp_of_exact(gpu, hard):
+    """ocml's atan2(y, x), the first result of the candidate angles: |raw - exact| <= 1 ulp, exact
+    the correctly rounded double -- one round of pcp_cr_atan2_fix's midpoint tests (two with the
+    confirming one) then gives it, and the fix follows a first result up to 4.5 ulps off
+    (tests/test_crmath_exact.py).  ocml's atan2 is NOT within one ulp of the true angle:
+    measured on gfx950 / ROCm 7.2, worst 1.45 ulps over the metre-scale pairs (for one,
+    atan2(0x1.08096fe0a3972p+5, 0x1.04e77f54bdc4cp+5) is 1.062 ulps above it) and 23 % of the raw
+    results not correctly rounded, which is why the fix repeats its tests: a single round is
+    right only up to 1.5 ulps.  The worst and the share are printed per family."""
+    worst, share, n = 0.0, 0.0, 0
+    for name, (y, x) in atan2_inputs(hard).items():
+        exact, _ = devmath.exact_atan2(y, x)
+        raw = gpu.debug_math(_abi.MATH_ATAN2_RAW, y, x)
+        w, s = _first_results("atan2 " + name, raw, exact, cr_ref.atan2_fixed, (y, x),
+                              strict=False)
+        print(f"ocml atan2 {name}: worst {w:.4f} ulps, not correctly rounded {s:.4f}")
+        worst, share, n = max(worst, w), share + s * y.size, n + y.size
+    print(f"ocml atan2: worst {worst:.4f} ulps, not correctly rounded {share / n:.4f}")
+
+
+def test_phase_two_runs_on_the_device(gpu, host, hard):
+    """The exact phase is reached on the device: the hard cases send at least as many values
+    through it as the host build does from the same first results (ocml's, read back), and on
+    uniform d its share stays below twice the host build's own share (first results at -1, 0
+    and +1 ulp of the exact value: different first results take different paths)."""
+    d = np.concatenate([hard["acos_d"], hard["spa_d"]])
+    _, ph_dev = gpu.debug_math(_abi.MATH_SCORE_SIN_PART, d)
+    _, ph_host = host.score_sin_part(d, gpu.debug_math(_abi.MATH_ACOS_RAW, d))
+    n_dev, n_host = int((ph_dev == 2).sum()), int((ph_host == 2).sum())
+    print(f"hard cases through phase 2: device {n_dev}, host {n_host} of {d.size}")
+    assert n_host > d.size // 4 and n_dev >= n_host
+    d = devmath.spa_families(1 << 15)["uniform"]
+    th, _ = devmath.exact_acos(d)
+    n_host = sum(int((host.score_sin_part(d, devmath.moved(th, k))[1] == 2).sum())
+                 for k in (-1, 0, 1))
+    _, ph_dev = gpu.debug_math(_abi.MATH_SCORE_SIN_PART, d)
+    n_dev = int((ph_dev == 2).sum())
+    print(f"uniform d through phase 2: device {n_dev} of {d.size}, host {n_host} of {3 * d.size}")
+    assert n_dev / d.size < 2 * n_host / (3 * d.size)
+
+
+# ---- float libm (pcp_libm.h): the device build against the gcc build --------------------------
+def _f32_bits(lo, hi, stride):
+    return np.arange(np.float32(lo).view(np.uint32), np.float32(hi).view(np.uint32) + 1, stride,
+                     dtype=np.uint32).view(np.float32)
+
+
+def _same_f32(a, b):
+    """Bit-equal, or both NaN (a NaN's sign and payload are the processor's, not the text's)."""
+    return devmath.bit_equal(a, b) | (np.isnan(a) & np.isnan(b))
+
+
+def test_float_libm_bit_equal_host_build(gpu, host):
+    """pcp_sinf / pcp_cosf over every 257th float of [0, 1.1] (4.1 M floats: a few ms on either
+    side), pcp_atan2f over computeRoots' magnitudes and arbitrary bit patterns, pcp_lm_div and
+    pcp_lm_sqrt with subnormal results, subnormal arguments and exact ties of the conversion."""
+    t = _f32_bits(0.0, 1.1, 257)
+    assert t.size > 4_000_000
+    assert _same_f32(gpu.debug_math(_abi.MATH_SINF, t), host.sinf(t)).all()
+    assert _same_f32(gpu.debug_math(_abi.MATH_COSF, t), host.cosf(t)).all()
+    g = np.random.default_rng(0xF32)
+    n = 1 << 15
+    # sqrt(-q), half_b as computeRoots forms them (tests/libm/libm_check.c's magnitudes)
+    y = np.ldexp(g.integers(0, 1 << 24, n).astype(np.float32) / np.float32(1 << 24),
+                 g.integers(-36, 12, n)).astype(np.float32)
+    x = np.ldexp(g.integers(0, 1 << 24, n).astype(np.float32) / np.float32(1 << 24)
+                 - np.float32(0.5), g.integers(-36, 12, n)).astype(np.float32)
+    yb = g.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32).view(np.float32)
+    xb = g.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32).view(np.float32)
+    for yy, xx in ((y, x), (yb, xb), (y, np.ones_like(y)), (np.zeros_like(x), x)):
+        with np.errstate(all="ignore"):
+            assert _same_f32(gpu.debug_math(_abi.MATH_ATAN2F, yy, xx), host.atan2f(yy, xx)).all()
+    # divide: any bit patterns; subnormal quotients; exact ties of the double quotient between
+    # two subnormal floats (an odd significand just above FLT_MIN over 2, 4, 8)
+    odd = (np.float32(FLT_MIN).view(np.uint32) + 2 * g.integers(0, 1 << 20, n).astype(np.uint32)
+           + np.uint32(1)).view(np.float32)
+    pairs = [(yb, xb),
+             (g.uniform(1.0, 2.0, n).astype(np.float32) * np.float32(2.0 ** -100),
+              g.uniform(1.0, 2.0, n).astype(np.float32) * np.float32(2.0 ** 40)),
+             (odd, np.float32(2.0) ** g.integers(1, 4, n).astype(np.float32)),
+             (y, np.maximum(np.abs(x), np.float32(FLT_MIN)))]
+    for a, b in pairs:
+        with np.errstate(all="ignore"):
+            want = host.divf(a, b)
+            assert _same_f32(gpu.debug_math(_abi.MATH_DIVF, a, b), want).all()
+    sub = (pairs[1][0] / pairs[1][1], host.divf(odd, pairs[2][1]))
+    assert (np.abs(sub[0]) < FLT_MIN).all() and (np.abs(sub[1]) < FLT_MIN).all()
+    # square root: any bit patterns (negative -> NaN), subnormal arguments, perfect squares
+    roots = [yb, np.arange(0, 1 << 15, dtype=np.uint32).view(np.float32),
+             (g.integers(0, 4096, n).astype(np.float32)) ** 2, np.abs(y)]
+    for a in roots:
+        with np.errstate(all="ignore"):
+            assert _same_f32(gpu.debug_math(_abi.MATH_SQRTF, a), host.sqrtf(a)).all()
+
+
+# ---- the bare double operations --------------------------------------------------------------
+def _f64_bits(g, n):
+    v = g.integers(0, 1 << 64, 2 * n, dtype=np.uint64).view(np.float64)
+    return v[np.isfinite(v)][:n]
+
+
+def test_bare_f64_operations(gpu):
+    """a / b, sqrt, (float), fma, nextafter and nearbyint on the device == numpy (IEEE, correctly
+    rounded on the host) and, for fma, the exact rational rounded once.  Subnormals, values near
+    overflow and exact halfway cases of the conversion included."""
+    g = np.random.default_rng(0xF64)
+    n = 1 << 15
+    a, b = _f64_bits(g, n), _f64_bits(g, n)
+    big = g.uniform(1.0, 2.0, n) * 2.0 ** 1023
+    tiny = g.uniform(1.0, 2.0, n) * 2.0 ** -1022
+    sub = g.integers(1, 1 << 52, n).astype(np.uint64).view(np.float64)
+    metres = g.uniform(-60.0, 60.0, n)
+    with np.errstate(all="ignore"):
+        for p, q in ((a, b), (big, g.uniform(0.5, 2.0, n)), (tiny, g.uniform(1.0, 2.0 ** 30, n)),
+                     (sub, g.uniform(0.5, 4.0, n)), (metres, g.uniform(-60.0, 60.0, n)),
+                     (np.ones(n), g.uniform(0.5, 70.0, n))):
+            assert devmath.bit_equal(gpu.debug_math(_abi.MATH_F64_DIV, p, q), np.divide(p, q)).all()
+        for p in (np.abs(a), big, tiny, sub, metres ** 2, g.integers(0, 1 << 26, n).astype(float) ** 2):
+            assert devmath.bit_equal(gpu.debug_math(_abi.MATH_F64_SQRT, p), np.sqrt(p)).all()
+        # (float): halfway between adjacent floats (normal and subnormal: ties to even), one
+        # double ulp to either side of it, around FLT_MAX's overflow threshold, below the
+        # smallest subnormal's half
+        f = np.concatenate([g.integers(0, 0x7F7FFFFF, n // 2, dtype=np.int64),
+                            g.integers(0, 0x00800000, n // 2, dtype=np.int64)]
+                           ).astype(np.uint32).view(np.float32)
+        mid = (f.astype(np.float64) + np.nextafter(f, np.float32(np.inf)).astype(np.float64)) / 2
+        fmax = float(np.finfo(np.float32).max)
+        edge = np.array([fmax, fmax * (1 + 2.0 ** -25), np.nextafter(fmax * (1 + 2.0 ** -25), 0),
+                         np.nextafter(fmax * (1 + 2.0 ** -25), np.inf), 2.0 ** -150,
+                         np.nextafter(2.0 ** -150, 1), np.nextafter(2.0 ** -150, 0), 2.0 ** -149,
+                         0.0, -0.0, np.inf, -np.inf, 1e300, 5e-324])
+        for p in (mid, np.nextafter(mid, np.inf), np.nextafter(mid, -np.inf), -mid, a, metres,
+                  edge, -edge):
+            assert devmath.bit_equal(gpu.debug_math(_abi.MATH_F64_TO_F32, p),
+                                     p.astype(np.float32)).all()
+        # nextafter both ways from zeros, subnormals, powers of two, the largest finite double
+        p = np.concatenate([a, sub[:256], 2.0 ** g.integers(-1022, 1023, 256).astype(float),
+                            [0.0, -0.0, 5e-324, -5e-324, np.finfo(float).max,
+                             -np.finfo(float).max, 1.0, -1.0, 2.0 ** -1022]])
+        for q in (np.full(p.size, np.inf), np.full(p.size, -np.inf), p, np.zeros(p.size)):
+            assert devmath.bit_equal(gpu.debug_math(_abi.MATH_F64_NEXTAFTER, p, q),
+                                     np.nextafter(p, q)).all()
+        # nearbyint: halves (ties to even), both signs, -0 results, past 2^52
+        k = g.integers(-(1 << 20), 1 << 20, n).astype(float)
+        for p in (k + 0.5, k + 0.25, metres * 9.0, g.uniform(-0.5, 0.5, n), a,
+                  np.array([0.5, -0.5, 1.5, 2.5, -0.0, 2.0 ** 52 + 1, 2.0 ** 53, -2.0 ** 52 - 1,
+                            0.49999999999999994, 4503599627370495.5])):
+            assert devmath.bit_equal(gpu.debug_math(_abi.MATH_F64_NEARBYINT, p), np.rint(p)).all()
+    # fma against the exact rational: two_prod's error term fma(a, b, -(a b)), random moderate
+    # operands, subnormal results, results next to overflow
+    m = 2048
+    fa = np.concatenate([g.uniform(-60.0, 60.0, m), g.uniform(1.0, 2.0, m) * 2.0 ** -600,
+                         g.uniform(1.0, 2.0, m) * 2.0 ** 511, _f64_bits(g, m)])
+    fb = np.concatenate([g.uniform(-60.0, 60.0, m), g.uniform(1.0, 2.0, m) * 2.0 ** -470,
+                         g.uniform(1.0, 1.4, m) * 2.0 ** 511, 1.0 / _f64_bits(g, m)])
+    with np.errstate(all="ignore"):
+        fc = np.concatenate([-(fa[:m] * fb[:m]), g.uniform(-1.0, 1.0, m) * 2.0 ** -1070,
+                             -g.uniform(1.0, 2.0, m) * 2.0 ** 1000, g.uniform(-4.0, 4.0, m)])
+    with np.errstate(all="ignore"):
+        ok = np.isfinite(fb) & np.isfinite(fc) & (np.abs(fa * fb) < 2.0 ** 1023)
+    fa, fb, fc = fa[ok], fb[ok], fc[ok]
+    want = np.array([float(Fraction(p) * Fraction(q) + Fraction(r)) for p, q, r in
+                     zip(fa.tolist(), fb.tolist(), fc.tolist())])
+    got = gpu.debug_math(_abi.MATH_F64_FMA, fa, np.stack([fb, fc], 1))
+    assert (want[:m] != 0).mean() > 0.9 and (np.abs(want[m:2 * m]) < 2.0 ** -1022).all()
+    assert (got == want).all() and devmath.bit_equal(got, want)[want != 0].all()
+
+
+# ---- normals ----------------------------------------------------------------------------------
+def _rot(g):
+    q, _ = np.linalg.qr(g.normal(size=(3, 3)))
+    return q
+
+
+def _sym32(m):
+    m = np.asarray(m, np.float64)
+    m = ((m + m.T) / 2).astype(np.float32)
+    return m.reshape(9)
+
+
+def _c0_scaled(c):
+    """det of cov / max |entry| in float32 (computeRoots' c0, to the rounding of its sums)."""
+    m = c.reshape(3, 3).astype(np.float32)
+    m = m / np.abs(m).max()
+    return float(np.linalg.det(m.astype(np.float64)))
+
+
+def normal_cases():
+    g = np.random.default_rng(0xC0F)
+    covs, tags = [], []
+
+    def add(tag, m):
+        covs.append(_sym32(m))
+        tags.append(tag)
+
+    for s in np.logspace(-12, 6, 37):                      # random SPD at scales 1e-12 .. 1e6
+        for _ in range(8):
+            r = _rot(g)
+            add("spd", s * (r * g.uniform(0.05, 1.0, 3)) @ r.T)
+    for _ in range(64):                                    # rank 2, rank 1, zero
+        r = _rot(g)
+        l2, l1 = g.uniform(0.1, 2.0, 2)
+        add("rank2", (r * np.array([0.0, l1, l2])) @ r.T)
+        add("rank1", (r * np.array([0.0, 0.0, l2])) @ r.T)
+        add("rank2_axis", np.diag(np.roll([0.0, l1, l2], g.integers(3))))
+    add("zero", np.zeros((3, 3)))
+    for f in np.exp2(np.linspace(-3.0, 3.0, 193)):         # |c0| on both sides of FLT_EPSILON
+        r = _rot(g)
+        add("c0", (r * np.array([f * FLT_EPS, 1.0, 1.0])) @ r.T)
+        add("c0_axis", np.diag([1.0, f * FLT_EPS, 1.0]))
+    for _ in range(64):                                    # two and three equal eigenvalues
+        r, s = _rot(g), 10.0 ** g.uniform(-3, 3)
+        add("eq2_low", s * (r * np.array([1.0, 1.0, 3.0])) @ r.T)
+        add("eq2_high", s * (r * np.array([1.0, 3.0, 3.0])) @ r.T)
+        add("eq3", s * np.eye(3))
+        add("eq2_axis", s * np.diag(np.roll([1.0, 1.0, 3.0], g.integers(3))))
+    for _ in range(128):                                   # cross products of equal length:
+        p, q, s, t = g.uniform(-1.0, 1.0, 4)               # covariances symmetric under a swap
+        base = np.array([[2.0 + p, q, q], [q, 2.0 + s, t], [q, t, 2.0 + s]])   # of two axes
+        for perm in ([0, 1, 2], [1, 0, 2], [2, 1, 0]):
+            add("tie", base[np.ix_(perm, perm)])
+    add("tie_ones", np.ones((3, 3)) + np.eye(3))
+    for _ in range(64):                                    # every entry at or below FLT_MIN
+        r = _rot(g)
+        add("tiny", FLT_MIN * (r * g.uniform(0.05, 1.0, 3)) @ r.T * 0.57)
+        add("tiny_axis", np.diag(np.roll([FLT_MIN, FLT_MIN / 2, FLT_MIN / 4], g.integers(3))))
+    add("flt_min", np.full((3, 3), FLT_MIN))
+    for i in range(3):                                     # a NaN entry, an infinite entry
+        for j in range(i, 3):
+            for bad in (np.nan, np.inf, -np.inf):
+                m = np.diag([1.0, 2.0, 3.0])
+                m[i, j] = m[j, i] = bad
+                add("nonfinite", m)
+    return np.stack(covs), np.array(tags)
+
+
+def axis_cases():
+    """Diagonal covariances, one strictly smallest entry, every axis permutation and scale."""
+    g = np.random.default_rng(0xA15)
+    covs, axes = [], []
+    for s in (1e-12, 1e-6, 1e-3, 1.0, 37.0, 1e6):
+        for _ in range(16):
+            lo = g.uniform(0.01, 0.5)
+            for hi in ((g.uniform(0.6, 1.0), g.uniform(0.6, 1.0)), (0.75, 0.75)):
+                for ax in range(3):
+                    dvals = np.insert(np.array(hi), ax, lo) * s
+                    covs.append(_sym32(np.diag(dvals)))
+                    axes.append(ax)
+    return np.stack(covs), np.array(axes)
+
+
+def test_normals_bit_equal_oracle(gpu, oracle):
+    """normal_from_cov on the device == the oracle's exported function, covariance by
+    covariance; the branches of computeRoots / eigen33 are reached by construction."""
+    covs, tags = normal_cases()
+    c0 = np.array([_c0_scaled(c) for c in covs[(tags == "c0") | (tags == "c0_axis")]])
+    assert (np.abs(c0) < 0.9 * FLT_EPS).any() and (np.abs(c0) > 1.1 * FLT_EPS).any()
+    assert (np.abs(covs[np.isin(tags, ["tiny", "tiny_axis", "flt_min"])]) <= FLT_MIN).all()
+    g = np.random.default_rng(0x9)
+    qs = [np.zeros((covs.shape[0], 3), np.float32),
+          g.uniform(-20.0, 20.0, (covs.shape[0], 3)).astype(np.float32)]
+    for q in qs:
+        want = oracle.normal_from_cov(covs, q)
+        got = gpu.debug_math(_abi.MATH_NORMAL, covs, q)
+        same = _same_f32(got, want).all(1)
+        for t in np.unique(tags):
+            print(f"normals {t}: {int((~same[tags == t]).sum())} of {int((tags == t).sum())} "
+                  f"differ, {int(np.isnan(want[tags == t]).any(1).sum())} NaN")
+        assert same.all(), (tags[~same][:8], covs[~same][:2], got[~same][:2], want[~same][:2])
+    finite = np.isfinite(want).all(1)
+    assert finite[np.isin(tags, ["spd", "rank2", "c0", "eq2_high", "tie"])].all()
+    assert np.allclose(np.linalg.norm(want[finite].astype(np.float64), axis=1), 1.0, atol=1e-5)
+
+
+def test_normals_axis_and_flips(gpu, oracle):
+    """Diagonal covariances with one strictly smallest entry give exactly the unit axis, on the
+    oracle and on the device; the two flips (towards the viewpoint (0, 0, 0) as seen from the
+    query point, then normal_z >= 0) follow numpy's float32 evaluation of the same rule."""
+    covs, axes = axis_cases()
+    n = covs.shape[0]
+    g = np.random.default_rng(0xF11)
+    zero = np.zeros((n, 3), np.float32)
+    q = g.uniform(-20.0, 20.0, (n, 3)).astype(np.float32)
+    q[::5] = 0.0
+    q[1::5, 0] = 0.0
+    for fn in (oracle.normal_from_cov, lambda c, p: gpu.debug_math(_abi.MATH_NORMAL, c, p)):
+        base = fn(covs, zero)          # ct = 0: no first flip; the second leaves -0.0 alone
+        assert (np.abs(base) == np.eye(3, dtype=np.float32)[axes]).all()
+        got = fn(covs, q)
+        ct = ((np.float32(0) - q[:, 0]) * base[:, 0] + (np.float32(0) - q[:, 1]) * base[:, 1]) \
+            + (np.float32(0) - q[:, 2]) * base[:, 2]
+        want = np.where((ct < 0)[:, None], -base, base)
+        want = np.where((want[:, 2] < 0)[:, None], -want, want)
+        assert devmath.bit_equal(got, want).all()
+        assert (got[axes == 2][:, 2] == 1.0).all()            # a vertical normal points up
+        h = (axes != 2) & (ct != 0)
+        assert (np.einsum("ij,ij->i", got[h], -q[h]) > 0).all()   # a horizontal one faces (0,0,0)
+
+
+def test_debug_math_argument_errors(gpu):
+    lib = _abi.load_library()
+    a = np.ones(4)
+    out = np.zeros(4)
+    assert lib.pcp_debug_math(gpu.h, _abi.MATH_ACOS_RAW, None, None, 0, None, None) == _abi.PCP_OK
+    assert lib.pcp_debug_math(gpu.h, 999, _abi._ptr(a), None, 4, _abi._ptr(out), None) \
+        == _abi.PCP_E_INVALID
+    assert lib.pcp_debug_math(None, _abi.MATH_ACOS_RAW, _abi._ptr(a), None, 4, _abi._ptr(out),
+                              None) == _abi.PCP_E_INVALID
+    for args in ((None, None, 4, _abi._ptr(out), None), (_abi._ptr(a), None, 4, None, None)):
+        assert lib.pcp_debug_math(gpu.h, _abi.MATH_ACOS_RAW, *args) == _abi.PCP_E_INVALID
+    assert lib.pcp_debug_math(gpu.h, _abi.MATH_F64_DIV, _abi._ptr(a), None, 4, _abi._ptr(out),
+                              None) == _abi.PCP_E_INVALID
+    assert lib.pcp_debug_math(gpu.h, _abi.MATH_SCORE_SIN_PART, _abi._ptr(a), None, 4,
+                              _abi._ptr(out), None) == _abi.PCP_E_INVALID
+    assert np.array_equal(gpu.debug_math(_abi.MATH_F64_SQRT, np.array([4.0, 9.0])), [2.0, 3.0])
