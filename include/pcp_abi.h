@@ -576,6 +576,79 @@ int pcp_place_refine_burst(pcp_ctx *ctx, const double *poses5, uint64_t n, const
                            const pcp_vl_params *p, const pcp_refine_params *rp, int reps,
                            double *ms_per_eval);
 
+/* Greedy placement of mobile sensors with a limited field of view: where to stand and which way
+ * to look.  Every pose is searched with every aim of a table; a sensor sees a cell when the cell
+ * lies inside its horizontal sector (h_fov about the pose's yaw plus the aim's offset) and inside
+ * its elevation band (v_fov about the aim's pitch).  S[p][c] and Z[c] are the values
+ * pcp_score_matrix returns for the same arguments with every pose's pitch replaced by 0.0
+ * (zx120_pose5 as given): range, visibility and score, nothing else.  max(a, b), osum(v), the
+ * separation expression and the first-maximum rule are pcp_place_sensors'.
+ *   Host tables (cos, sin, tan: the host C library's double functions): cyp = cos(yaw_p), syp =
+ *      sin(yaw_p), yaw_p = poses5[5 p + 4]; ca = cos(aims[2 a]), sa = sin(aims[2 a]); ch =
+ *      cos(h_fov * 0.5); lo_a = aims[2 a + 1] - v_fov * 0.5, hi_a = aims[2 a + 1] + v_fov * 0.5;
+ *      tlo_a = lo_a <= -M_PI_2 ? -inf : tan(lo_a), thi_a = hi_a >= M_PI_2 ? +inf : tan(hi_a).
+ *   Per (p, a, c), in double, every product, sum and sqrt rounded on its own: dx = cx - px, dy =
+ *      cy - py, dz = cz - pz; hyp = sqrt(dx * dx + dy * dy); Cy = cyp * ca - syp * sa, Sy = syp *
+ *      ca + cyp * sa; fwd = dx * Cy + dy * Sy; H = (h_fov >= 2 pi) || (fwd >= ch * hyp); V =
+ *      !(dz < tlo_a * hyp) && !(dz > thi_a * hyp) (negated, so -+inf * 0 = NaN counts as inside:
+ *      a cell straight below is in view exactly when the lower bound reaches -90 degrees);
+ *      W[p][a][c] = (H && V) ? S[p][c] : +0.0.
+ *   1. base = Z, owner[c] = Z[c] > 0 ? PCP_OWNER_ZX120 : PCP_OWNER_NONE; then W[fixed_pose[i]]
+ *      [fixed_aim[i]] folded in by max in list order, fixed sensor i owning the cells it raises
+ *      (ties keep the earlier owner).  *base_total = osum(base), *base_covered = #{base > 0}.
+ *   2. A pose is alive unless it is fixed or, with min_separation > 0, closer than it to a fixed
+ *      pose.
+ *   3. Round r = 0 .. k_max - 1: t[p][a] = osum(max(base, W[p][a])) for the alive p, -inf for the
+ *      others; round_totals[r] holds the whole [n][n_aims] table.
+ *   4. (b, ab) = the first maximum in row-major order (pose ascending, then aim; strict '>' from
+ *      -inf).
+ *   5. Stop when no pose is alive, or unless t[b][ab] > T (T = *base_total, then the last
+ *      total_after).
+ *   6. selected[r] = b, selected_aim[r] = ab, total_after[r] = T = t[b][ab], covered_after[r] its
+ *      count of positive elements; every cell with base[c] < W[b][ab][c] gets owner n_fixed + r,
+ *      base = max(base, W[b][ab]); pose b leaves the search, and with min_separation > 0 so does
+ *      every pose closer to it than that.
+ *   7. cell_score = base, *n_selected = rounds recorded; entries and tables from there on are not
+ *      written.
+ * PCP_E_INVALID before any launch, nothing written: k_max outside 1 .. PCP_PLACE_MAX, n_aims
+ * outside 1 .. PCP_AIM_MAX, n_fixed outside 0 .. PCP_PLACE_MAX, reserved != 0, h_fov not finite or
+ * <= 0, v_fov outside (0, pi], a non-finite aim or an aim pitch outside [-pi / 2, pi / 2], n >
+ * PCP_PAIR_MAX_POSES, n * n_aims > PCP_AIM_MAX_ROWS, a fixed pose >= n or listed twice, a fixed aim
+ * outside the table, a step table past PCP_MAX_STEPS, a null required pointer (everything not
+ * marked nullable), a null context.  n == 0 or no cells: PCP_OK, *n_selected = 0, the base totals
+ * as defined (0 without cells).  One synchronisation; deterministic (two calls give identical
+ * bytes); the caller's GridCell flags are neither read nor written; the call's scratch is its own,
+ * so the other queries on the context are unchanged by it. */
+#define PCP_AIM_MAX       64      /* aims per call */
+#define PCP_AIM_MAX_ROWS  65536   /* n * n_aims */
+typedef struct pcp_aim_params {
+    int32_t k_max;          /* sensors to place, 1 .. PCP_PLACE_MAX */
+    int32_t n_aims;         /* 1 .. PCP_AIM_MAX */
+    int32_t n_fixed;        /* aimed sensors already placed, 0 .. PCP_PLACE_MAX */
+    int32_t reserved;       /* 0 */
+    double  h_fov, v_fov;   /* full angles, radians: h_fov > 0 (>= 2 pi: no horizontal test), 0 < v_fov <= pi */
+    double  min_separation; /* metres in XY; <= 0: none */
+    int64_t fixed_pose[PCP_PLACE_MAX];   /* indices into poses5, first n_fixed used */
+    int32_t fixed_aim[PCP_PLACE_MAX];    /* indices into aims, first n_fixed used */
+} pcp_aim_params;
+int pcp_place_aimed(pcp_ctx *ctx, const double *poses5, uint64_t n, const double zx120_pose5[5],
+                    const pcp_vl_params *p, const pcp_aim_params *ap,
+                    const double *aims,        /* [n_aims][2]: yaw offset, pitch (radians) */
+                    int64_t *selected, int32_t *selected_aim,        /* [k_max] */
+                    double *total_after, int32_t *covered_after,     /* [k_max] */
+                    double *round_totals,      /* nullable [k_max][n][n_aims] */
+                    double *cell_score, int32_t *cell_owner,         /* nullable [n_cells] */
+                    double *base_total, int32_t *base_covered, int32_t *n_selected);
+
+/* Kernel timing of pcp_place_aimed (the timing tool only): the query's setup (the scoring, the
+ * tables, the base) once, then `reps` repetitions of round 0's launch -- every row's total, the
+ * last block's selection, nothing committed -- between two stream events; *ms_per_round = the
+ * interval / reps.  n >= 1, cells present. */
+int pcp_place_aimed_burst(pcp_ctx *ctx, const double *poses5, uint64_t n,
+                          const double zx120_pose5[5], const pcp_vl_params *p,
+                          const pcp_aim_params *ap, const double *aims, int reps,
+                          double *ms_per_round);
+
 /* Dense ray fan (BASELINE configs[1]): per pose, n_az x n_el rays, ray (i, j) with local
  * direction (cos e_j cos a_i, cos e_j sin a_i, sin e_j), a_i = 2*pi*i/n_az,
  * e_j = el_min + (el_max-el_min)*(j+0.5)/n_el, rotated by the pose yaw, marched with

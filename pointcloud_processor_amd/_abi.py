@@ -115,6 +115,18 @@ class RefineParams(C.Structure):
                 ("start", C.c_int64 * PLACE_MAX)]
 
 
+AIM_MAX = 64           # PCP_AIM_MAX: aims one pcp_place_aimed call searches per pose
+AIM_MAX_ROWS = 65536   # PCP_AIM_MAX_ROWS: (pose, aim) rows one call searches at most
+
+
+class AimParams(C.Structure):
+    """pcp_aim_params."""
+    _fields_ = [("k_max", C.c_int32), ("n_aims", C.c_int32), ("n_fixed", C.c_int32),
+                ("reserved", C.c_int32), ("h_fov", C.c_double), ("v_fov", C.c_double),
+                ("min_separation", C.c_double), ("fixed_pose", C.c_int64 * PLACE_MAX),
+                ("fixed_aim", C.c_int32 * PLACE_MAX)]
+
+
 SCAN_MAX_POSES = 64   # PCP_SCAN_MAX_POSES: poses one pcp_simulate_scan call casts (mask bits)
 
 
@@ -254,6 +266,12 @@ _SIGS = [
     ("pcp_place_refine_burst", C.c_int, [_P, _P, C.c_uint64, _P, C.POINTER(VlParams),
                                          C.POINTER(RefineParams), C.c_int,
                                          C.POINTER(C.c_double)]),
+    ("pcp_place_aimed", C.c_int, [_P, _P, C.c_uint64, _P, C.POINTER(VlParams),
+                                  C.POINTER(AimParams), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                  _P]),
+    ("pcp_place_aimed_burst", C.c_int, [_P, _P, C.c_uint64, _P, C.POINTER(VlParams),
+                                        C.POINTER(AimParams), _P, C.c_int,
+                                        C.POINTER(C.c_double)]),
     ("pcp_simulate_scan", C.c_int, [_P, _P, C.c_uint64, C.POINTER(FanParams), _P, C.c_uint64,
                                     C.POINTER(C.c_uint64), _P, _P, _P, _P, _P, C.c_uint64,
                                     C.POINTER(C.c_uint64), _P, C.POINTER(C.c_uint64)]),
@@ -1135,6 +1153,76 @@ class Context:
         self._check(self.lib.pcp_place_pair_burst(self.h, _ptr(poses), poses.shape[0], _ptr(zx),
                                                   C.byref(params), C.byref(pp), int(reps),
                                                   C.byref(ms)), "pcp_place_pair_burst")
+        return ms.value
+
+    @staticmethod
+    def _aim_params(k_max, n_aims, h_fov, v_fov, fixed, min_separation, reserved,
+                    n_fixed=None) -> AimParams:
+        fixed = [(int(p), int(a)) for p, a in fixed]
+        ap = AimParams(int(k_max), int(n_aims), len(fixed) if n_fixed is None else int(n_fixed),
+                       int(reserved), float(h_fov), float(v_fov), float(min_separation))
+        for i, (p, a) in enumerate(fixed[:PLACE_MAX]):
+            ap.fixed_pose[i] = p
+            ap.fixed_aim[i] = a
+        return ap
+
+    def place_aimed(self, poses5, zx120_pose5, params: VlParams, aims, h_fov: float,
+                    v_fov: float, k_max: int, fixed=(), min_separation: float = 0.0,
+                    want_round_totals: bool = False, want_cells: bool = False,
+                    reserved: int = 0) -> dict:
+        """pcp_place_aimed: up to k_max sensors with a field of view of h_fov x v_fov (full
+        angles, radians) placed greedily, every pose searched with every aim of `aims` [A, 2] (yaw
+        offset, pitch) beside zx120 and the `fixed` (pose, aim) pairs.  -> dict: n_selected,
+        selected / selected_aim / total_after / covered_after [n_selected], base_total,
+        base_covered, and on request round_totals [n_selected, P, A] (-inf at poses out of the
+        search), cell_score / cell_owner [n_cells]."""
+        poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 5)
+        zx = np.ascontiguousarray(zx120_pose5, np.float64)
+        aims = np.ascontiguousarray(aims, np.float64).reshape(-1, 2)
+        P, A = poses.shape[0], aims.shape[0]
+        ap = self._aim_params(k_max, A, h_fov, v_fov, fixed, min_separation, reserved)
+        kk = max(min(int(k_max), PLACE_MAX), 1)
+        sel = np.full(kk, -1, np.int64)
+        sa = np.full(kk, -1, np.int32)
+        tot = np.zeros(kk, np.float64)
+        cov = np.zeros(kk, np.int32)
+        fits = P <= PAIR_MAX_POSES and P * A <= AIM_MAX_ROWS   # (a refused call writes nothing)
+        rt = np.zeros((kk, max(P, 1), max(A, 1)), np.float64) \
+            if want_round_totals and fits else None
+        C_ = self.cells_count() if want_cells else 0
+        cs = np.zeros(max(C_, 1), np.float64) if want_cells else None
+        co = np.zeros(max(C_, 1), np.int32) if want_cells else None
+        bt, bc, ns = C.c_double(), C.c_int32(), C.c_int32()
+        self._check(self.lib.pcp_place_aimed(
+            self.h, _ptr(poses) if P else None, P, _ptr(zx), C.byref(params), C.byref(ap),
+            _ptr(aims) if A else None, _ptr(sel), _ptr(sa), _ptr(tot), _ptr(cov), _ptr(rt),
+            _ptr(cs), _ptr(co), C.byref(bt), C.byref(bc), C.byref(ns)), "pcp_place_aimed")
+        n = ns.value
+        out = {"n_selected": n, "selected": sel[:n].copy(), "selected_aim": sa[:n].copy(),
+               "total_after": tot[:n].copy(), "covered_after": cov[:n].copy(),
+               "base_total": bt.value, "base_covered": bc.value}
+        if want_round_totals:
+            out["round_totals"] = rt[:n, :P, :A].copy()
+        if want_cells:
+            out["cell_score"] = cs[:C_].copy()
+            out["cell_owner"] = co[:C_].copy()
+        return out
+
+    def place_aimed_burst(self, poses5, zx120_pose5, params: VlParams, aims, h_fov: float,
+                          v_fov: float, fixed=(), min_separation: float = 0.0,
+                          reps: int = 20) -> float:
+        """pcp_place_aimed_burst -> ms per round of the aimed placement (round 0's launch: every
+        (pose, aim) row's total and the last block's selection; the scoring, the tables and the
+        base once before the interval)."""
+        poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 5)
+        zx = np.ascontiguousarray(zx120_pose5, np.float64)
+        aims = np.ascontiguousarray(aims, np.float64).reshape(-1, 2)
+        ap = self._aim_params(1, aims.shape[0], h_fov, v_fov, fixed, min_separation, 0)
+        ms = C.c_double(0.0)
+        self._check(self.lib.pcp_place_aimed_burst(self.h, _ptr(poses), poses.shape[0], _ptr(zx),
+                                                   C.byref(params), C.byref(ap), _ptr(aims),
+                                                   int(reps), C.byref(ms)),
+                    "pcp_place_aimed_burst")
         return ms.value
 
     def place_triple(self, poses5, zx120_pose5, params: VlParams, fixed=(),

@@ -14,6 +14,11 @@
 //   pcp_nodes_cli place_refine  (place's arguments) [N_LOCKED [MAX_MOVES]]: KMAX sensors placed
 //                         greedily, then refined by single-sensor exchanges; OUT_SELECTED: the
 //                         refined set; OUT_TOTALS: start, final, then the total after each move
+//   pcp_nodes_cli place_aimed  (place's arguments) H_FOV V_FOV AIMS.f64 [FIXED]: KMAX sensors of
+//                         H_FOV x V_FOV radians placed greedily, every candidate searched with
+//                         every aim of AIMS.f64 ([A][2] doubles: yaw offset, pitch) beside the
+//                         aimed sensors already placed (FIXED: candidate,aim,candidate,aim,..);
+//                         OUT_SELECTED: (candidate, aim) pairs; OUT_TOTALS: the total after each
 //   pcp_nodes_cli scan    TERRAIN.f32 TN POSES(5 per sensor) NAZ NEL MAXD OUT_SCANS.bin
 //   pcp_nodes_cli scan_mounted TERRAIN.f32 TN POSES(6 per sensor: x,y,z,roll,pitch,yaw) NAZ NEL
 //                         MAXD ELTABLE|- OUT_SCANS.bin ... (scan's outputs; ELTABLE: NEL radians)
@@ -199,7 +204,7 @@ static int cmd_vlidar(Device &dev, char **a, int argc) {
 // one tick of the virtual-LiDAR node (vlidar's inputs), then KMAX mobile sensors placed greedily
 // among its candidates: the selected candidates, the totals after each and the placement's table
 static int cmd_place(Device &dev, char **a, bool exact_pair = false, bool refine = false,
-                     int argc = 16, bool exact_triple = false) {
+                     int argc = 16, bool exact_triple = false, bool aimed = false) {
     const auto t = read_file(a[0]), ax = read_file(a[2]), c = read_file(a[4]),
                nr = read_file(a[5]);
     const size_t tn = std::strtoull(a[1], nullptr, 10), an = std::strtoull(a[3], nullptr, 10),
@@ -324,6 +329,46 @@ static int cmd_place(Device &dev, char **a, bool exact_pair = false, bool refine
                     tick.candidates.size(), r.selected.size(), r.n_locked, r.moves.size(),
                     r.converged ? 1 : 0, sel.c_str(), moves.c_str(), r.start_covered, r.covered,
                     r.total_cells);
+        return 0;
+    }
+    if (aimed) {
+        // place_aimed: limited-field-of-view sensors, every candidate with every aim of the table
+        MobileLidarPlacement::AimedParams ap;
+        ap.h_fov = std::strtod(a[16], nullptr);
+        ap.v_fov = std::strtod(a[17], nullptr);
+        const auto raw = read_file(a[18]);
+        ap.aims.resize(raw.size() / 16);
+        for (size_t i = 0; i < ap.aims.size(); ++i) {
+            std::memcpy(&ap.aims[i].yaw_offset, raw.data() + 16 * i, 8);
+            std::memcpy(&ap.aims[i].pitch, raw.data() + 16 * i + 8, 8);
+        }
+        if (placement.place_aimed(dev, SimplifiedDualLidarOptimizer::Result{}, p, ap).ran) return 3;
+        std::vector<MobileLidarPlacement::FixedAimed> fixed;
+        if (argc > 19) {
+            const auto f = tuple(a[19]);
+            for (size_t i = 0; i + 1 < f.size(); i += 2)
+                fixed.push_back({(int64_t)f[i], (int32_t)f[i + 1]});
+        }
+        const auto r = placement.place_aimed(dev, tick, p, ap, fixed);
+        if (!r.ran) {
+            std::fprintf(stderr, "place_aimed: %s\n", placement.lastError().c_str());
+            return 1;
+        }
+        std::vector<int64_t> sel;
+        std::vector<double> tot;
+        for (const auto &q : r.rounds) {
+            sel.push_back(q.candidate);
+            sel.push_back(q.aim);
+            tot.push_back(q.total);
+        }
+        write_file(a[13], sel.data(), sel.size() * 8);
+        write_file(a[14], tot.data(), tot.size() * 8);
+        write_file(a[15], r.log.data(), r.log.size());
+        std::printf("{\"n_candidates\": %zu, \"n_aims\": %zu, \"n_fixed\": %d, "
+                    "\"n_selected\": %zu, \"base_total\": %.17g, \"base_covered\": %d, "
+                    "\"total_cells\": %d}\n",
+                    tick.candidates.size(), ap.aims.size(), r.n_fixed, r.rounds.size(),
+                    r.base_total, r.base_covered, r.total_cells);
         return 0;
     }
     if (placement.place(dev, SimplifiedDualLidarOptimizer::Result{}, p).ran) return 3;   // no tick
@@ -781,7 +826,7 @@ int main(int argc, char **argv) {
         if (!hp || std::atoi(hp) != 0) setenv("HSA_ENABLE_INTERRUPT", "0", 0);
     }
     if (argc < 2) {
-        std::fprintf(stderr, "usage: pcp_nodes_cli filter|merge|vlidar|place|place_pair|place_triple|place_refine|scan|scan_mounted|area|drivable|replay ...\n");
+        std::fprintf(stderr, "usage: pcp_nodes_cli filter|merge|vlidar|place|place_pair|place_triple|place_refine|place_aimed|scan|scan_mounted|area|drivable|replay ...\n");
         return 2;
     }
     const std::string cmd = argv[1];
@@ -792,6 +837,7 @@ int main(int argc, char **argv) {
                      : cmd == "place_pair" ? 16
                      : cmd == "place_triple" ? 16
                      : cmd == "place_refine" ? 16
+                     : cmd == "place_aimed" ? 19
                      : cmd == "scan"   ? 10
                      : cmd == "scan_mounted" ? 11
                      : cmd == "area"   ? 10
@@ -814,6 +860,9 @@ int main(int argc, char **argv) {
                              /*exact_triple=*/true);
         if (cmd == "place_refine")
             return cmd_place(dev, argv + 2, /*exact_pair=*/false, /*refine=*/true, argc - 2);
+        if (cmd == "place_aimed")
+            return cmd_place(dev, argv + 2, /*exact_pair=*/false, /*refine=*/false, argc - 2,
+                             /*exact_triple=*/false, /*aimed=*/true);
         if (cmd == "scan") return cmd_scan(dev, argv + 2);
         if (cmd == "scan_mounted") return cmd_scan(dev, argv + 2, /*mounted=*/true);
         if (cmd == "area") return cmd_area(dev, argv + 2);

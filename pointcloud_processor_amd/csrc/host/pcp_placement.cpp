@@ -415,4 +415,107 @@ MobileLidarPlacement::RefineResult MobileLidarPlacement::refine(
     return r;
 }
 
+std::string placement_aimed_log(const MobileLidarPlacement::AimedResult &r) {
+    std::string log;
+    const int tc = r.total_cells;
+    auto pct = [tc](int v) { return tc > 0 ? (double)v / tc * 100.0 : 0.0; };
+    const double deg = 180.0 / 3.14159265358979323846;
+    const char *rule = "========================================";
+    const char *thin = "----------------------------------------";
+    appendf(log, "%s", rule);
+    appendf(log, "Aimed LiDAR Placement (ZX120 + %d Fixed + %zu Mobile)", r.n_fixed,
+            r.placed.size());
+    appendf(log, "Field of view: %.1f x %.1f deg", r.h_fov * deg, r.v_fov * deg);
+    appendf(log, "%s", rule);
+    appendf(log, "Total Score (ZX120%s): %.2f", r.n_fixed ? " + fixed" : " only", r.base_total);
+    appendf(log, "  Covered cells: %d of %d (%.1f%%)", r.base_covered, tc, pct(r.base_covered));
+    for (size_t i = 0; i < r.rounds.size(); ++i) {
+        const auto &q = r.rounds[i];
+        const auto &p = r.placed[i];
+        appendf(log, "%s", thin);
+        appendf(log, "Mobile LiDAR %zu Position: (%.2f, %.2f, %.2f)  [candidate %lld, aim %d]",
+                i + 1, p.x, p.y, p.z, (long long)q.candidate, (int)q.aim);
+        appendf(log, "  Heading: yaw %.1f deg, pitch %.1f deg", p.yaw * deg, p.pitch * deg);
+        appendf(log, "  Total Score: %.2f (gain %.2f)", q.total, q.gain);
+        appendf(log, "  Covered cells: %d of %d (%.1f%%)", q.covered, tc, pct(q.covered));
+    }
+    appendf(log, "%s", rule);
+    return log;
+}
+
+MobileLidarPlacement::AimedResult MobileLidarPlacement::place_aimed(
+    Device &dev, const SimplifiedDualLidarOptimizer::Result &tick,
+    const SimplifiedDualLidarOptimizer::Params &vl, const AimedParams &ap,
+    const std::vector<FixedAimed> &fixed) {
+    AimedResult r;
+    err_.clear();
+    if (!tick.ran) return r;
+    if (fixed.size() > PCP_PLACE_MAX || ap.aims.size() > PCP_AIM_MAX) {
+        err_ = "place_aimed: more than PCP_PLACE_MAX fixed sensors or PCP_AIM_MAX aims";
+        return r;
+    }
+    const double zx[5] = {tick.zx120.x, tick.zx120.y, tick.zx120.z, tick.zx120.pitch,
+                          tick.zx120.yaw};
+    const pcp_vl_params p{vl.grid_resolution, vl.sensor_height, vl.search_radius, vl.max_distance,
+                          vl.num_candidates,  vl.vertical_layers};
+    pcp_aim_params pp{};
+    pp.k_max = p_.num_mobile_lidars;
+    pp.n_aims = (int32_t)ap.aims.size();
+    pp.n_fixed = (int32_t)fixed.size();
+    pp.h_fov = ap.h_fov;
+    pp.v_fov = ap.v_fov;
+    pp.min_separation = p_.min_separation;
+    for (size_t i = 0; i < fixed.size(); ++i) {
+        pp.fixed_pose[i] = fixed[i].candidate;
+        pp.fixed_aim[i] = fixed[i].aim;
+    }
+    std::vector<double> aims(2 * ap.aims.size());
+    for (size_t a = 0; a < ap.aims.size(); ++a) {
+        aims[2 * a] = ap.aims[a].yaw_offset;
+        aims[2 * a + 1] = ap.aims[a].pitch;
+    }
+    const size_t n = tick.candidates.size();
+    std::vector<double> poses(5 * n);
+    for (size_t i = 0; i < n; ++i) {
+        const auto &c = tick.candidates[i];
+        poses[5 * i] = c.x;
+        poses[5 * i + 1] = c.y;
+        poses[5 * i + 2] = c.z;
+        poses[5 * i + 3] = c.pitch;
+        poses[5 * i + 4] = c.yaw;
+    }
+    int64_t sel[PCP_PLACE_MAX];
+    int32_t sel_aim[PCP_PLACE_MAX], cov[PCP_PLACE_MAX], ns = 0;
+    double tot[PCP_PLACE_MAX];
+    if (pcp_place_aimed(dev.ctx(), poses.data(), n, zx, &p, &pp, aims.data(), sel, sel_aim, tot, cov,
+                        nullptr, nullptr, nullptr, &r.base_total, &r.base_covered,
+                        &ns) != PCP_OK) {
+        err_ = dev.error();
+        return r;
+    }
+    r.ran = true;
+    r.total_cells = tick.report.total_cells;
+    r.n_fixed = pp.n_fixed;
+    r.h_fov = ap.h_fov;
+    r.v_fov = ap.v_fov;
+    double before = r.base_total;
+    for (int32_t i = 0; i < ns; ++i) {
+        AimedRound q;
+        q.candidate = sel[i];
+        q.aim = sel_aim[i];
+        q.total = tot[i];
+        q.gain = tot[i] - before;
+        q.covered = cov[i];
+        q.coverage_ratio = r.total_cells > 0 ? (double)cov[i] / r.total_cells : 0.0;
+        before = tot[i];
+        r.rounds.push_back(q);
+        r.placed.push_back(tick.candidates[(size_t)sel[i]]);
+        r.placed.back().yaw += ap.aims[(size_t)sel_aim[i]].yaw_offset;
+        r.placed.back().pitch = ap.aims[(size_t)sel_aim[i]].pitch;
+        r.placed.back().total_score = tot[i];
+    }
+    r.log = placement_aimed_log(r);
+    return r;
+}
+
 }  // namespace pcp

@@ -131,6 +131,46 @@ class MobileLidarPlacement {
                         const SimplifiedDualLidarOptimizer::Params &vl,
                         const std::vector<int64_t> &start, int n_locked = 0,
                         int max_moves = PCP_REFINE_MAX_MOVES);
+
+    // Sensors with a limited field of view (pcp_place_aimed): every candidate of the tick is
+    // searched with every aim of a table, greedily as place(), beside zx120 and the `fixed`
+    // aimed sensors.  The answer says where to stand and which way to look.
+    struct Aim {
+        double yaw_offset = 0;         // radians, added to the candidate's yaw
+        double pitch = 0;              // radians, -pi / 2 .. pi / 2
+    };
+    struct AimedParams {
+        double h_fov = 0, v_fov = 0;   // full angles, radians (h_fov >= 2 pi: no horizontal test)
+        std::vector<Aim> aims;         // 1 .. PCP_AIM_MAX
+    };
+    struct FixedAimed {
+        int64_t candidate = -1;
+        int32_t aim = -1;
+    };
+    struct AimedRound {
+        int64_t candidate = -1;        // index into the tick's candidates
+        int32_t aim = -1;              // index into AimedParams::aims
+        double total = 0, gain = 0;    // as Round's
+        int32_t covered = 0;
+        double coverage_ratio = 0;
+    };
+    struct AimedResult {
+        bool ran = false;              // false: the tick did not run, or the call failed
+        std::vector<SimplifiedDualLidarOptimizer::LidarPosition> placed;   // in placement order:
+                                       // yaw = the candidate's + the aim's offset, pitch = the
+                                       // aim's, total_score = AimedRound::total
+        std::vector<AimedRound> rounds;
+        double base_total = 0;         // zx120 and the fixed sensors alone
+        int32_t base_covered = 0;
+        int32_t n_fixed = 0;
+        int32_t total_cells = 0;
+        double h_fov = 0, v_fov = 0;
+        std::string log;
+    };
+    // num_mobile_lidars and min_separation are params()'s
+    AimedResult place_aimed(Device &dev, const SimplifiedDualLidarOptimizer::Result &tick,
+                            const SimplifiedDualLidarOptimizer::Params &vl, const AimedParams &ap,
+                            const std::vector<FixedAimed> &fixed = {});
     const std::string &lastError() const { return err_; }
 
    private:
@@ -152,5 +192,8 @@ std::string placement_triple_log(const MobileLidarPlacement::TripleResult &r,
 // the refinement's table in the same format: the start set, every move (slot, from and to with
 // their positions, the gain), and either "1-exchange optimal" or "stopped after N moves"
 std::string placement_refine_log(const MobileLidarPlacement::RefineResult &r);
+// the aimed placement's table in the same format: the field of view, the base, and per sensor its
+// position, heading and pitch with the candidate and the aim they come from
+std::string placement_aimed_log(const MobileLidarPlacement::AimedResult &r);
 
 }  // namespace pcp

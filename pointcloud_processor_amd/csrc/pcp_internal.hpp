@@ -331,6 +331,11 @@ struct pcp_ctx : pcp::CtxStreams {
     // one download; its pair phase runs in pair_d / pair_m, which no call reads across calls
     pcp::DevBuf triple_d;
     pcp::PinnedBuf triple_host;
+    // pcp_place_aimed (pcp_aim.hip): its state, base / owner, the rounds' [P][A] totals and covered
+    // counts and the alive mask (aim_d), the predicate's tables (aim_m), and the pinned staging of
+    // the tables' upload and landing of its one download (its own, as the placement's)
+    pcp::DevBuf aim_d, aim_m;
+    pcp::PinnedBuf aim_host;
     // pcp_simulate_scan (pcp_scan.hip): wave bases, offsets, records, dense images, point mask and
     // counts, and the pinned landing of its downloads (its own: the fan's buffers stay as
     // pcp_raycast_fan leaves and expects them)
