@@ -17,12 +17,12 @@ _COMMON = ["pcp_internal.hpp", "pcp_knobs.hpp", "Makefile", "../../include/pcp_a
 WORKLOAD_SOURCES = {
     "fan": ["pcp_fan.hip", "pcp_march.hpp", "pcp_fine.hip", "pcp_index.hip", "pcp_stencil.hpp",
             "pcp_grid.hpp", "pcp_fan_band.hpp", "pcp_fan_clear.hpp", "pcp_fan_clip.hpp",
-            "pcp_fan_pivot.hpp", "pcp_fan_row.hpp"] + _COMMON,
+            "pcp_fan_pivot.hpp", "pcp_fan_row.hpp", "pcp_walk_pair.hpp"] + _COMMON,
     "filter": ["pcp_filter.hip", "pcp_rigid.hpp"] + _COMMON,
     # reference mode (k_score_cells: the same march over the same terrain copy)
     "cells": ["pcp_score.hip", "pcp_march.hpp", "pcp_fine.hip", "pcp_index.hip", "pcp_stencil.hpp",
               "pcp_grid.hpp", "pcp_fan_band.hpp", "pcp_fan_clear.hpp", "pcp_fan_clip.hpp",
-              "pcp_fan_pivot.hpp", "pcp_fan_row.hpp"] + _COMMON,
+              "pcp_fan_pivot.hpp", "pcp_fan_row.hpp", "pcp_walk_pair.hpp"] + _COMMON,
 }
 
 

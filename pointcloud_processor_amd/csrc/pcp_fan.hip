@@ -5,7 +5,7 @@
 // Numerics: compiled with -ffp-contract=off (no FMA) so every double/float operation
 // rounds exactly as the reference's SSE2 build.  The radius predicate restates FLANN's
 // L2_Simple<float> (x, y, z accumulated in order, strict '<' against float(r*r)).
-// Build knobs of this file: PCP_FAN_NO_ROW, PCP_FAN_NO_SP.
+// Build knobs of this file: PCP_FAN_NO_ROW, PCP_FAN_NO_SP, PCP_FAN_NO_PRO1.
 #pragma clang fp contract(off)
 
 #include <algorithm>
@@ -103,8 +103,52 @@ __device__ __forceinline__ void fan_body(const FanArgs &a, uint32_t p0, uint32_t
     // pose's values and its live rings are then LDS broadcasts, not a round trip through
     // vector memory at the top of every pose
     __shared__ double s_steps[SL ? kStepLds : 1];
-    __shared__ double s_pose[SL ? PR * NPW : 1];
-    if (SL) {
+    // (whole trips of BS lanes: the staging below stores every lane's value unguarded)
+    __shared__ double s_pose[SL ? (PR * NPW + BS - 1) / BS * BS : 1];
+#ifdef PCP_FAN_NO_PRO1   // A/B build only: each staging loop and each table load waits by itself
+    constexpr bool PRO1 = false;
+#else
+    constexpr bool PRO1 = SL;
+#endif
+    if (PRO1) {
+        // every address of the prologue is known at the wave's start: the step table's entries,
+        // the rows and the four direction-table values are all loaded before the first wait --
+        // one round trip through vector memory, not one per staging trip and table
+        constexpr int NS = kStepLds / BS, NR = (PR * NPW + BS - 1) / BS;
+        static_assert(kStepLds % BS == 0, "whole trips over the step table");
+        double sv[NS], rv[NR], cej = 0.0, cai = 0.0, sai = 0.0, sej = 0.0;
+#pragma unroll
+        for (int t = 0; t < NS; ++t) {
+            const int q = (int)threadIdx.x + t * BS;
+            sv[t] = q < a.K ? a.steps[q] : 0.0;
+        }
+#pragma unroll
+        for (int t = 0; t < NR; ++t) {
+            const int q = (int)threadIdx.x + t * BS;
+            rv[t] = q < PR * NPW ? a.pose[PR * (size_t)p0 + q] : 0.0;
+        }
+        if (active && a.present) {
+            const uint32_t j = UE ? (rblock * BS + (threadIdx.x & ~63u)) / (uint32_t)a.n_az
+                                  : ray / (uint32_t)a.n_az;
+            const uint32_t i = ray - j * (uint32_t)a.n_az;
+            cej = a.ce[j];
+            cai = a.ca[i];
+            sai = a.sa[i];
+            sej = a.se[j];
+        }
+        // (both arrays hold whole trips: an entry past K or past the rows is a zero nobody
+        // reads, and the stores need no guard -- one block, one wait)
+#pragma unroll
+        for (int t = 0; t < NS; ++t) s_steps[threadIdx.x + t * BS] = sv[t];
+#pragma unroll
+        for (int t = 0; t < NR; ++t) s_pose[threadIdx.x + t * BS] = rv[t];
+        __syncthreads();
+        if (active && a.present) {
+            lx = cej * cai;
+            ly = cej * sai;
+            lz = sej;
+        }
+    } else if (SL) {
         for (int q = threadIdx.x; q < a.K; q += BS) s_steps[q] = a.steps[q];
         for (int q = threadIdx.x; q < PR * NPW; q += BS) s_pose[q] = a.pose[PR * (size_t)p0 + q];
         __syncthreads();
@@ -115,7 +159,7 @@ __device__ __forceinline__ void fan_body(const FanArgs &a, uint32_t p0, uint32_t
     if (UE)
         ju = (uint32_t)__builtin_amdgcn_readfirstlane(
             (int)((rblock * BS + (threadIdx.x & ~63u)) / (uint32_t)a.n_az));
-    if (active && a.present) {
+    if (!PRO1 && active && a.present) {
         // UE (n_az % 64 == 0): the wave's ring is uniform, a scalar division of its first ray
         const uint32_t j = UE ? (rblock * BS + (threadIdx.x & ~63u)) / (uint32_t)a.n_az
                               : ray / (uint32_t)a.n_az;

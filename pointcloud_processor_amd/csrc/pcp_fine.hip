@@ -28,6 +28,7 @@
 #include "pcp_fan_pivot.hpp"
 #include "pcp_grid.hpp"
 #include "pcp_internal.hpp"
+#include "pcp_walk_pair.hpp"
 
 namespace pcp {
 
@@ -500,9 +501,13 @@ int build_fine(pcp_ctx *ctx, GridIndex &g) {
     // the pivot table goes with the split records; its 12-byte records are addressed with
     // 32-bit byte offsets (a plane past 2^28 cells keeps the copy and goes without)
     const bool pivots = tile == 2 && plan.npiv < (1ull << 28);
-    // packed: the float4 entries are built in scratch, then packed into wpts
+    // packed: the float4 entries are built in scratch, then packed into wpts.  The packed array
+    // keeps kWalkPairSlack bytes behind its last entry (the last window's sentinel): the paired
+    // walk loads one entry behind the one it tests, 12 bytes of slack per extra entry loaded
+    // (pcp_walk_pair.hpp)
     if ((pack && ctx->scratch[7].ensure(nent * sizeof(float4)) != hipSuccess) ||
-        g.wpts.ensure(pack ? nent * 12 + 16 : nent * sizeof(float4)) != hipSuccess ||
+        g.wpts.ensure(pack ? nent * kWalkEntryBytes + kWalkPairSlack
+                           : nent * sizeof(float4)) != hipSuccess ||
         g.frec.ensure(rec_bytes) != hipSuccess ||
         (pivots && g.fpiv.ensure(plan.npiv * kPivotBytes + 16) != hipSuccess)) {
         (void)hipGetLastError();

@@ -3,7 +3,7 @@
 // __forceinline__ device functions only, so each source compiles its own kernels around them.
 // Both sources include it under #pragma clang fp contract(off) (no FMA, see their headers).
 // Build knobs of the march: PCP_CELL_PROBES, PCP_BLK_STEP, PCP_NO_VGPR_PIN, PCP_WALK_CENSUS,
-// PCP_CLAMP_INT.
+// PCP_CLAMP_INT, PCP_FAN_NO_PAIR, PCP_WALK_CENSUS_PAIR.
 #pragma once
 
 #include <cfloat>
@@ -13,6 +13,7 @@
 #include "pcp_fan_row.hpp"
 #include "pcp_internal.hpp"
 #include "pcp_stencil.hpp"
+#include "pcp_walk_pair.hpp"
 
 namespace pcp {
 
@@ -120,6 +121,14 @@ __device__ __forceinline__ T vgpr_pin(T x) {
     return x;
 }
 
+// entries per trip of the packed walk under march's SP (PCP_FAN_NO_PAIR: an A/B build that keeps
+// the one-entry walk everywhere)
+#ifdef PCP_FAN_NO_PAIR
+template <bool SP> constexpr int kWalkSp = 1;
+#else
+template <bool SP> constexpr int kWalkSp = SP ? 2 : 1;
+#endif
+
 // a z-descending run pts[k0 .. e): the walk of one block (or one fine window)
 template <bool STATS>
 __device__ __forceinline__ bool scan_run(const float4 *pts, uint32_t k0, uint32_t e, float qx,
@@ -141,22 +150,47 @@ __device__ __forceinline__ bool scan_run(const float4 *pts, uint32_t k0, uint32_
 }
 
 // the packed (12-byte) entries' walk: the same test on x, y, z at k * 12
-template <bool STATS>
+// WS 2 (the production fan kernels, march's SP): two entries per trip, pcp_walk_pair.hpp -- the
+// same answer and the same tests from half the dependent round trips through vector memory.
+// Both entries' loads are in flight before the first wait: left to itself the compiler sinks
+// the second entry's load behind the first entry's test, so its floats are pinned right after
+// the loads.
+template <bool STATS, int WS = 1>
 __device__ __forceinline__ bool scan_window3(const float *pts, uint32_t k, float qx, float qy,
                                              float qz, float r2, float rexit, uint32_t *cnt) {
     bool within, stop;
+    if (WS == 2) {
+        do {
+            const float *f = walk_entry(pts, k);
+            const float ax = f[0], ay = f[1], az = f[2];
+            float bx = f[3], by = f[4], bz = f[5];
+            asm volatile("" : "+v"(bx), "+v"(by), "+v"(bz));
+            k += 2;
+            uint32_t t;
+            stop = walk_pair_step(ax, ay, az, bx, by, bz, qx, qy, qz, r2, rexit, within, t);
+            if (STATS) cnt[2] += t;
+        } while (!stop);
+        return within;
+    }
+    const uint32_t k0 = k;
+    (void)k0;
     do {
         const float *f = reinterpret_cast<const float *>(reinterpret_cast<const char *>(pts) +
                                                          ((k << 3) + (k << 2)));
         const P3 p = P3{f[0], f[1], f[2]};
         ++k;
         if (STATS) cnt[2] += 1;
-#ifdef PCP_WALK_CENSUS
+#if defined(PCP_WALK_CENSUS) && !defined(PCP_WALK_CENSUS_PAIR)
         if (STATS && p.z - qz >= rexit) cnt[3] += 1;   // an entry r above q: a later start skips it
 #endif
         within = flann_within(qx, qy, qz, p, r2);
         stop = within | (qz - p.z >= rexit);
     } while (!stop);
+#if defined(PCP_WALK_CENSUS) && defined(PCP_WALK_CENSUS_PAIR)
+    // (make census EXTRA=-DPCP_WALK_CENSUS_PAIR) a walk of an odd number of tests: the paired
+    // walk's last trip loads an entry it does not test
+    if (STATS && ((k - k0) & 1u)) cnt[3] += 1;
+#endif
     return within;
 }
 
@@ -411,8 +445,9 @@ __device__ __forceinline__ int march(const GridView &g, double px, double py, do
                     }
                 }
                 const bool packed = SP || g.wpack;
-                if (packed ? scan_window3<STATS>(reinterpret_cast<const float *>(g.wpts), w0, qx,
-                                                 qy, qz, r2, rexit, cnt)
+                if (packed ? scan_window3<STATS, kWalkSp<SP>>(
+                                 reinterpret_cast<const float *>(g.wpts), w0, qx, qy, qz, r2, rexit,
+                                 cnt)
                            : scan_window<STATS>(g.wpts, w0, qx, qy, qz, r2, rexit, cnt))
                     return k;
             }
