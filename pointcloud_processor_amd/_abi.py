@@ -392,6 +392,16 @@ def _ptr(a: np.ndarray | None):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _poses5(x) -> np.ndarray:
+    """poses5 as the ABI reads it: C-contiguous float64 [P, 5]."""
+    return np.ascontiguousarray(x, np.float64).reshape(-1, 5)
+
+
+def _zx5(x) -> np.ndarray:
+    """zx120_pose5 as the ABI reads it: C-contiguous float64."""
+    return np.ascontiguousarray(x, np.float64)
+
+
 def cloud_view(arr: np.ndarray, point_step: int | None = None, offs=(0, 4, 8)) -> CloudView:
     """CloudView over a C-contiguous array whose rows are point records.
 
@@ -821,7 +831,7 @@ class Context:
 
     def generate_candidates(self, grid_bbox, params: VlParams, zx120_pose5, cap=None):
         bb = np.ascontiguousarray(grid_bbox, np.float64)
-        zx = np.ascontiguousarray(zx120_pose5, np.float64)
+        zx = _zx5(zx120_pose5)
         gs = int(np.ceil(np.sqrt(float(params.num_candidates))))
         cap = cap or max(gs * gs, 1)
         out = np.empty((cap, 5), np.float64)
@@ -834,9 +844,9 @@ class Context:
     def score_poses(self, poses5: np.ndarray, zx120_pose5, params: VlParams,
                     cell_flags: np.ndarray):
         """runOptimization scoring; cell_flags (uint8, n_cells) is updated in place."""
-        poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 5)
+        poses = _poses5(poses5)
         P = poses.shape[0]
-        zx = np.ascontiguousarray(zx120_pose5, np.float64)
+        zx = _zx5(zx120_pose5)
         assert cell_flags.dtype == np.uint8 and cell_flags.flags.c_contiguous
         tot = np.empty(max(P, 1), np.float64)
         cov = np.empty(max(P, 1), np.int32)
@@ -851,7 +861,7 @@ class Context:
         """runOptimization's device part in one call (pcp_generate_and_score): returns
         (poses [n, 5], totals, covered, report); cell_flags updated in place."""
         bb = np.ascontiguousarray(grid_bbox, np.float64)
-        zx = np.ascontiguousarray(zx120_pose5, np.float64)
+        zx = _zx5(zx120_pose5)
         assert cell_flags.dtype == np.uint8 and cell_flags.flags.c_contiguous
         gs = int(np.ceil(np.sqrt(float(params.num_candidates))))
         cap = max(gs * gs, 1)
@@ -1044,8 +1054,8 @@ class Context:
     def score_matrix(self, poses5, zx120_pose5, params: VlParams):
         """pcp_score_matrix -> (score_mobile [P, C], score_zx120 [C]): evaluateCellScore per
         (pose, cell) as k_score_cells computes it (the per-cell parity bar)."""
-        poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 5)
-        zx = np.ascontiguousarray(zx120_pose5, np.float64)
+        poses = _poses5(poses5)
+        zx = _zx5(zx120_pose5)
         C_ = self.cells_count()
         P = poses.shape[0]
         sm = np.zeros((max(P, 1), max(C_, 1)), np.float64)
@@ -1053,6 +1063,33 @@ class Context:
         self._check(self.lib.pcp_score_matrix(self.h, _ptr(poses), P, _ptr(zx), C.byref(params),
                                               _ptr(sm), _ptr(sz)), "pcp_score_matrix")
         return sm[:P, :C_].copy(), sz[:C_].copy()
+
+    def _cell_buffers(self, want_cells: bool):
+        """(n_cells, cell_score, cell_owner) for a placement call: its buffers when wanted."""
+        if not want_cells:
+            return 0, None, None
+        n = self.cells_count()
+        return n, np.zeros(max(n, 1), np.float64), np.zeros(max(n, 1), np.int32)
+
+    @staticmethod
+    def _cells_out(out: dict, cells) -> dict:
+        """out with the call's cell_score / cell_owner [n_cells], where _cell_buffers made them."""
+        n, cs, co = cells
+        if cs is not None:
+            out["cell_score"] = cs[:n].copy()
+            out["cell_owner"] = co[:n].copy()
+        return out
+
+    def _place_burst(self, symbol: str, poses5, zx120_pose5, params: VlParams, call_params,
+                     reps: int, *extra) -> float:
+        """A placement call's timing entry point -> its ms per repetition; extra: what the call
+        takes between its parameters and reps."""
+        poses, zx = _poses5(poses5), _zx5(zx120_pose5)
+        ms = C.c_double(0.0)
+        self._check(getattr(self.lib, symbol)(self.h, _ptr(poses), poses.shape[0], _ptr(zx),
+                                              C.byref(params), C.byref(call_params), *extra,
+                                              int(reps), C.byref(ms)), symbol)
+        return ms.value
 
     def place_sensors(self, poses5, zx120_pose5, params: VlParams, k_max: int,
                       min_separation: float = 0.0, want_round_totals: bool = False,
@@ -1062,8 +1099,8 @@ class Context:
         ordered total while it adds anything).  -> dict: n_selected, selected / total_after /
         covered_after [n_selected], zx120_total, zx120_covered, and on request round_totals
         [n_selected, P] (-inf at poses out of the search), cell_score / cell_owner [n_cells]."""
-        poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 5)
-        zx = np.ascontiguousarray(zx120_pose5, np.float64)
+        poses = _poses5(poses5)
+        zx = _zx5(zx120_pose5)
         P = poses.shape[0]
         pp = PlaceParams(int(k_max), int(reserved), float(min_separation))
         kk = max(min(int(k_max), PLACE_MAX), 1)
@@ -1071,9 +1108,7 @@ class Context:
         tot = np.zeros(kk, np.float64)
         cov = np.zeros(kk, np.int32)
         rt = np.zeros((kk, max(P, 1)), np.float64) if want_round_totals else None
-        C_ = self.cells_count() if want_cells else 0
-        cs = np.zeros(max(C_, 1), np.float64) if want_cells else None
-        co = np.zeros(max(C_, 1), np.int32) if want_cells else None
+        cells = _, cs, co = self._cell_buffers(want_cells)
         zt, zc, ns = C.c_double(), C.c_int32(), C.c_int32()
         self._check(self.lib.pcp_place_sensors(self.h, _ptr(poses) if P else None, P, _ptr(zx),
                                                C.byref(params), C.byref(pp), _ptr(sel), _ptr(tot),
@@ -1086,10 +1121,7 @@ class Context:
                "zx120_covered": zc.value}
         if want_round_totals:
             out["round_totals"] = rt[:n, :P].copy()
-        if want_cells:
-            out["cell_score"] = cs[:C_].copy()
-            out["cell_owner"] = co[:C_].copy()
-        return out
+        return self._cells_out(out, cells)
 
     @staticmethod
     def _pair_params(fixed, min_separation, reserved, n_fixed=None) -> PairParams:
@@ -1111,8 +1143,8 @@ class Context:
         best_single, single_total, single_covered, base_total, base_covered, and on request
         pair_totals [P, P] (-inf off the admissible upper triangle), single_totals [P],
         cell_score / cell_owner [n_cells] of the answer."""
-        poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 5)
-        zx = np.ascontiguousarray(zx120_pose5, np.float64)
+        poses = _poses5(poses5)
+        zx = _zx5(zx120_pose5)
         P = poses.shape[0]
         pp = self._pair_params(fixed, min_separation, reserved)
         bp = np.full(2, -1, np.int64)
@@ -1122,9 +1154,7 @@ class Context:
         dense = P <= PAIR_MAX_POSES   # (a refused call writes nothing: no table for it)
         tab = np.zeros((max(P, 1), max(P, 1)), np.float64) if want_pair_totals and dense else None
         sg = np.zeros(max(P, 1), np.float64) if want_single_totals else None
-        C_ = self.cells_count() if want_cells else 0
-        cs = np.zeros(max(C_, 1), np.float64) if want_cells else None
-        co = np.zeros(max(C_, 1), np.int32) if want_cells else None
+        cells = _, cs, co = self._cell_buffers(want_cells)
         self._check(self.lib.pcp_place_pair(
             self.h, _ptr(poses) if P else None, P, _ptr(zx), C.byref(params), C.byref(pp),
             _ptr(bp), C.byref(pt), C.byref(pc), C.byref(bs), C.byref(st), C.byref(sc),
@@ -1137,23 +1167,14 @@ class Context:
             out["pair_totals"] = tab[:P, :P].copy()
         if want_single_totals:
             out["single_totals"] = sg[:P].copy()
-        if want_cells:
-            out["cell_score"] = cs[:C_].copy()
-            out["cell_owner"] = co[:C_].copy()
-        return out
+        return self._cells_out(out, cells)
 
     def place_pair_burst(self, poses5, zx120_pose5, params: VlParams, fixed=(),
                          min_separation: float = 0.0, reps: int = 20) -> float:
         """pcp_place_pair_burst -> ms per repetition of the pair phase (preparation, pair tiles,
         selection; the scoring once before the interval)."""
-        poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 5)
-        zx = np.ascontiguousarray(zx120_pose5, np.float64)
-        pp = self._pair_params(fixed, min_separation, 0)
-        ms = C.c_double(0.0)
-        self._check(self.lib.pcp_place_pair_burst(self.h, _ptr(poses), poses.shape[0], _ptr(zx),
-                                                  C.byref(params), C.byref(pp), int(reps),
-                                                  C.byref(ms)), "pcp_place_pair_burst")
-        return ms.value
+        return self._place_burst("pcp_place_pair_burst", poses5, zx120_pose5, params,
+                                 self._pair_params(fixed, min_separation, 0), reps)
 
     @staticmethod
     def _aim_params(k_max, n_aims, h_fov, v_fov, fixed, min_separation, reserved,
@@ -1176,8 +1197,8 @@ class Context:
         selected / selected_aim / total_after / covered_after [n_selected], base_total,
         base_covered, and on request round_totals [n_selected, P, A] (-inf at poses out of the
         search), cell_score / cell_owner [n_cells]."""
-        poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 5)
-        zx = np.ascontiguousarray(zx120_pose5, np.float64)
+        poses = _poses5(poses5)
+        zx = _zx5(zx120_pose5)
         aims = np.ascontiguousarray(aims, np.float64).reshape(-1, 2)
         P, A = poses.shape[0], aims.shape[0]
         ap = self._aim_params(k_max, A, h_fov, v_fov, fixed, min_separation, reserved)
@@ -1189,9 +1210,7 @@ class Context:
         fits = P <= PAIR_MAX_POSES and P * A <= AIM_MAX_ROWS   # (a refused call writes nothing)
         rt = np.zeros((kk, max(P, 1), max(A, 1)), np.float64) \
             if want_round_totals and fits else None
-        C_ = self.cells_count() if want_cells else 0
-        cs = np.zeros(max(C_, 1), np.float64) if want_cells else None
-        co = np.zeros(max(C_, 1), np.int32) if want_cells else None
+        cells = _, cs, co = self._cell_buffers(want_cells)
         bt, bc, ns = C.c_double(), C.c_int32(), C.c_int32()
         self._check(self.lib.pcp_place_aimed(
             self.h, _ptr(poses) if P else None, P, _ptr(zx), C.byref(params), C.byref(ap),
@@ -1203,10 +1222,7 @@ class Context:
                "base_total": bt.value, "base_covered": bc.value}
         if want_round_totals:
             out["round_totals"] = rt[:n, :P, :A].copy()
-        if want_cells:
-            out["cell_score"] = cs[:C_].copy()
-            out["cell_owner"] = co[:C_].copy()
-        return out
+        return self._cells_out(out, cells)
 
     def place_aimed_burst(self, poses5, zx120_pose5, params: VlParams, aims, h_fov: float,
                           v_fov: float, fixed=(), min_separation: float = 0.0,
@@ -1214,16 +1230,10 @@ class Context:
         """pcp_place_aimed_burst -> ms per round of the aimed placement (round 0's launch: every
         (pose, aim) row's total and the last block's selection; the scoring, the tables and the
         base once before the interval)."""
-        poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 5)
-        zx = np.ascontiguousarray(zx120_pose5, np.float64)
         aims = np.ascontiguousarray(aims, np.float64).reshape(-1, 2)
         ap = self._aim_params(1, aims.shape[0], h_fov, v_fov, fixed, min_separation, 0)
-        ms = C.c_double(0.0)
-        self._check(self.lib.pcp_place_aimed_burst(self.h, _ptr(poses), poses.shape[0], _ptr(zx),
-                                                   C.byref(params), C.byref(ap), _ptr(aims),
-                                                   int(reps), C.byref(ms)),
-                    "pcp_place_aimed_burst")
-        return ms.value
+        return self._place_burst("pcp_place_aimed_burst", poses5, zx120_pose5, params, ap, reps,
+                                 _ptr(aims))
 
     def place_triple(self, poses5, zx120_pose5, params: VlParams, fixed=(),
                      min_separation: float = 0.0, want_first: bool = False,
@@ -1238,8 +1248,8 @@ class Context:
         first_partners [P, 2] (the best (b, c) of every first sensor a), triple_totals [P, P, P]
         (-inf off the admissible a < b < c; P <= TRIPLE_TABLE_MAX_POSES), cell_score /
         cell_owner [n_cells] of the answer."""
-        poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 5)
-        zx = np.ascontiguousarray(zx120_pose5, np.float64)
+        poses = _poses5(poses5)
+        zx = _zx5(zx120_pose5)
         P = poses.shape[0]
         pp = self._pair_params(fixed, min_separation, reserved)
         bt3, bp = np.full(3, -1, np.int64), np.full(2, -1, np.int64)
@@ -1252,9 +1262,7 @@ class Context:
         # (past the table's limit the call is refused: one entry stands for the argument)
         nt = max(P, 1) if P <= TRIPLE_TABLE_MAX_POSES else 1
         tab = np.zeros((nt, nt, nt), np.float64) if want_triple_totals else None
-        C_ = self.cells_count() if want_cells else 0
-        cs = np.zeros(max(C_, 1), np.float64) if want_cells else None
-        co = np.zeros(max(C_, 1), np.int32) if want_cells else None
+        cells = _, cs, co = self._cell_buffers(want_cells)
         self._check(self.lib.pcp_place_triple(
             self.h, _ptr(poses) if P else None, P, _ptr(zx), C.byref(params), C.byref(pp),
             _ptr(bt3), C.byref(tt), C.byref(tc), _ptr(bp), C.byref(pt), C.byref(pc),
@@ -1269,24 +1277,15 @@ class Context:
             out["first_partners"] = fp[:P].copy()
         if want_triple_totals:
             out["triple_totals"] = tab[:P, :P, :P].copy()
-        if want_cells:
-            out["cell_score"] = cs[:C_].copy()
-            out["cell_owner"] = co[:C_].copy()
-        return out
+        return self._cells_out(out, cells)
 
     def place_triple_burst(self, poses5, zx120_pose5, params: VlParams, fixed=(),
                            min_separation: float = 0.0, reps: int = 20) -> float:
         """pcp_place_triple_burst -> ms per repetition of the triple phase (the pair phase it
         builds on, the triple tiles, the rows' maxima and the selection; the scoring once before
         the interval)."""
-        poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 5)
-        zx = np.ascontiguousarray(zx120_pose5, np.float64)
-        pp = self._pair_params(fixed, min_separation, 0)
-        ms = C.c_double(0.0)
-        self._check(self.lib.pcp_place_triple_burst(self.h, _ptr(poses), poses.shape[0], _ptr(zx),
-                                                    C.byref(params), C.byref(pp), int(reps),
-                                                    C.byref(ms)), "pcp_place_triple_burst")
-        return ms.value
+        return self._place_burst("pcp_place_triple_burst", poses5, zx120_pose5, params,
+                                 self._pair_params(fixed, min_separation, 0), reps)
 
     @staticmethod
     def _refine_params(start, n_locked, max_moves, min_separation, reserved,
@@ -1309,8 +1308,8 @@ class Context:
         out first), move_slot / move_from / move_to / move_total / move_covered [n_moves], and on
         request swap_totals [n_moves + 1, k, P] (-inf at inadmissible moves), cell_score /
         cell_owner [n_cells] of the refined set."""
-        poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 5)
-        zx = np.ascontiguousarray(zx120_pose5, np.float64)
+        poses = _poses5(poses5)
+        zx = _zx5(zx120_pose5)
         P = poses.shape[0]
         rp = self._refine_params(start, n_locked, max_moves, min_separation, reserved)
         k = max(min(rp.k, PLACE_MAX), 1)
@@ -1326,9 +1325,7 @@ class Context:
         dense = P <= PAIR_MAX_POSES   # (a refused call writes nothing: no table for it)
         tab = (np.zeros((mm + 1, k, max(P, 1)), np.float64)
                if want_swap_totals and dense else None)
-        C_ = self.cells_count() if want_cells else 0
-        cs = np.zeros(max(C_, 1), np.float64) if want_cells else None
-        co = np.zeros(max(C_, 1), np.int32) if want_cells else None
+        cells = _, cs, co = self._cell_buffers(want_cells)
         self._check(self.lib.pcp_place_refine(
             self.h, _ptr(poses), P, _ptr(zx), C.byref(params), C.byref(rp), _ptr(sel),
             C.byref(tot), C.byref(cov), C.byref(st), C.byref(sc), _ptr(m_slot), _ptr(m_from),
@@ -1343,23 +1340,14 @@ class Context:
         if want_swap_totals:
             # (without cells nothing is evaluated: no table)
             out["swap_totals"] = tab[:n + 1 if self.cells_count() else 0, :, :P].copy()
-        if want_cells:
-            out["cell_score"] = cs[:C_].copy()
-            out["cell_owner"] = co[:C_].copy()
-        return out
+        return self._cells_out(out, cells)
 
     def place_refine_burst(self, poses5, zx120_pose5, params: VlParams, start, n_locked: int = 0,
                            min_separation: float = 0.0, reps: int = 20) -> float:
         """pcp_place_refine_burst -> ms per evaluation of the start set (preparation and
         evaluation launches; the scoring and the setup once before the interval)."""
-        poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 5)
-        zx = np.ascontiguousarray(zx120_pose5, np.float64)
-        rp = self._refine_params(start, n_locked, 0, min_separation, 0)
-        ms = C.c_double(0.0)
-        self._check(self.lib.pcp_place_refine_burst(self.h, _ptr(poses), poses.shape[0], _ptr(zx),
-                                                    C.byref(params), C.byref(rp), int(reps),
-                                                    C.byref(ms)), "pcp_place_refine_burst")
-        return ms.value
+        return self._place_burst("pcp_place_refine_burst", poses5, zx120_pose5, params,
+                                 self._refine_params(start, n_locked, 0, min_separation, 0), reps)
 
     def simulate_scan(self, poses5, fan: FanParams, want_dense: bool = False,
                       want_mask: bool = True, returns_cap: int | None = None,
@@ -1483,7 +1471,7 @@ class Context:
 
     def simulate_scan_burst(self, poses5, fan: FanParams, reps: int = 20):
         """pcp_simulate_scan_burst -> (fan kernel ms per launch, resolve phase ms per repetition)."""
-        poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 5)
+        poses = _poses5(poses5)
         ms = np.zeros(2, np.float64)
         self._check(self.lib.pcp_simulate_scan_burst(self.h, _ptr(poses), poses.shape[0],
                                                      C.byref(fan), reps, _ptr(ms)),
@@ -1493,8 +1481,8 @@ class Context:
     def score_poses_stats(self, poses5, zx120_pose5, params: VlParams) -> dict:
         """pcp_score_poses_stats: the gather lane-loads of the query's visibility rays
         (diagnostic twin of k_score_cells; the caller's flags are not touched)."""
-        poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 5)
-        zx = np.ascontiguousarray(zx120_pose5, np.float64)
+        poses = _poses5(poses5)
+        zx = _zx5(zx120_pose5)
         st = np.zeros(4, np.uint64)
         self._check(self.lib.pcp_score_poses_stats(self.h, _ptr(poses), poses.shape[0], _ptr(zx),
                                                    C.byref(params), _ptr(st)),
@@ -1505,8 +1493,8 @@ class Context:
     def score_poses_burst(self, poses5, zx120_pose5, params: VlParams, reps: int = 20) -> float:
         """pcp_score_poses_burst: the query's production k_score_cells launch `reps` times
         back-to-back between two events -> ms per launch."""
-        poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 5)
-        zx = np.ascontiguousarray(zx120_pose5, np.float64)
+        poses = _poses5(poses5)
+        zx = _zx5(zx120_pose5)
         ms = C.c_double()
         self._check(self.lib.pcp_score_poses_burst(self.h, _ptr(poses), poses.shape[0], _ptr(zx),
                                                    C.byref(params), reps, C.byref(ms)),
@@ -1539,7 +1527,7 @@ class Context:
         return ms.value if timed else None
 
     def raycast_fan(self, poses5: np.ndarray, fan: FanParams, want_first_hit=False):
-        poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 5)
+        poses = _poses5(poses5)
         P = poses.shape[0]
         blocked = np.zeros(max(P, 1), np.uint32)
         units = np.zeros(max(P, 1), np.uint64)
@@ -1608,7 +1596,7 @@ class Multi:
                     "pcp_multi_set_cells")
 
     def raycast_fan(self, poses5: np.ndarray, fan: FanParams):
-        poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 5)
+        poses = _poses5(poses5)
         P = poses.shape[0]
         blocked = np.zeros(max(P, 1), np.uint32)
         units = np.zeros(max(P, 1), np.uint64)
@@ -1620,9 +1608,9 @@ class Multi:
 
     def score_poses(self, poses5: np.ndarray, zx120_pose5, params: VlParams,
                     cell_flags: np.ndarray):
-        poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 5)
+        poses = _poses5(poses5)
         P = poses.shape[0]
-        zx = np.ascontiguousarray(zx120_pose5, np.float64)
+        zx = _zx5(zx120_pose5)
         assert cell_flags.dtype == np.uint8 and cell_flags.flags.c_contiguous
         tot = np.empty(max(P, 1), np.float64)
         cov = np.empty(max(P, 1), np.int32)
@@ -1640,7 +1628,7 @@ def _fan_stats(self, poses5, fan):
     actually loaded (a candidate settled by its window's pivot loads none, DESIGN.md §5 Skip 6);
     point_tests = every exact point test, the pivot tests included; their sum is the launch's
     gather count.  directory_loads is 0 over a fine copy."""
-    poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 5)
+    poses = _poses5(poses5)
     st = np.zeros(4, np.uint64)
     self._check(self.lib.pcp_raycast_fan_stats(self.h, _ptr(poses), poses.shape[0], C.byref(fan),
                                                _ptr(st)), "pcp_raycast_fan_stats")
@@ -1653,7 +1641,7 @@ Context.raycast_fan_stats = _fan_stats
 
 def _fan_stamps(self, poses5, fan):
     """Per-wave shader-clock stamps (diagnostic build): (P, waves, 4) uint64."""
-    poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 5)
+    poses = _poses5(poses5)
     waves = (fan.n_az * fan.n_el + 63) // 64
     st = np.zeros((poses.shape[0], waves, 4), np.uint64)
     self._check(self.lib.pcp_raycast_fan_stamps(self.h, _ptr(poses), poses.shape[0],
@@ -1667,7 +1655,7 @@ Context.raycast_fan_stamps = _fan_stamps
 
 def _fan_burst(self, poses5, fan, reps=20):
     """Average launch time (ms) of the production fan kernel over `reps` back-to-back launches."""
-    poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 5)
+    poses = _poses5(poses5)
     ms = C.c_double()
     self._check(self.lib.pcp_raycast_fan_burst(self.h, _ptr(poses), poses.shape[0], C.byref(fan),
                                                reps, C.byref(ms)), "pcp_raycast_fan_burst")

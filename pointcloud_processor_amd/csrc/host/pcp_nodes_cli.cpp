@@ -201,26 +201,32 @@ static int cmd_vlidar(Device &dev, char **a, int argc) {
     return 0;
 }
 
-// one tick of the virtual-LiDAR node (vlidar's inputs), then KMAX mobile sensors placed greedily
-// among its candidates: the selected candidates, the totals after each and the placement's table
-static int cmd_place(Device &dev, char **a, bool exact_pair = false, bool refine = false,
-                     int argc = 16, bool exact_triple = false, bool aimed = false) {
+// ---- the placement commands: a tick of the virtual-LiDAR node, a search among its candidates ----
+struct PlaceFront {
+    SimplifiedDualLidarOptimizer::Params p;
+    SimplifiedDualLidarOptimizer::Result tick;
+    MobileLidarPlacement placement;   // with KMAX and MINSEP
+    int failed(const char *cmd) const {   // a search that did not run
+        std::fprintf(stderr, "%s: %s\n", cmd, placement.lastError().c_str());
+        return 1;
+    }
+};
+static const SimplifiedDualLidarOptimizer::Result kNoTick{};   // (every call must refuse it: 3)
+
+// the shared arguments (vlidar's inputs, KMAX, MINSEP) and the tick; 0, or the failure's status
+static int place_front(Device &dev, char **a, PlaceFront &f) {
     const auto t = read_file(a[0]), ax = read_file(a[2]), c = read_file(a[4]),
                nr = read_file(a[5]);
     const size_t tn = std::strtoull(a[1], nullptr, 10), an = std::strtoull(a[3], nullptr, 10),
                  cn = std::strtoull(a[6], nullptr, 10);
     const auto bbox = tuple(a[7]), zxt = tuple(a[8]);
-    SimplifiedDualLidarOptimizer::Params p;
-    p.num_candidates = std::atoi(a[9]);
-    p.max_distance = std::strtod(a[10], nullptr);
-    MobileLidarPlacement::Params pp;
-    pp.num_mobile_lidars = std::atoi(a[11]);
-    pp.min_separation = std::strtod(a[12], nullptr);
-    SimplifiedDualLidarOptimizer node(dev, p);
+    f.p.num_candidates = std::atoi(a[9]);
+    f.p.max_distance = std::strtod(a[10], nullptr);
+    f.placement.params().num_mobile_lidars = std::atoi(a[11]);
+    f.placement.params().min_separation = std::strtod(a[12], nullptr);
+    SimplifiedDualLidarOptimizer node(dev, f.p);
     Transform zx;
-    zx.t[0] = zxt[0];
-    zx.t[1] = zxt[1];
-    zx.t[2] = zxt[2];
+    for (int i = 0; i < 3; ++i) zx.t[i] = zxt[i];
     node.terrainCallback(cloud_from(t, tn, 32, "map"));
     node.zx120PointsCallback(cloud_from(ax, an, 32, "velodyne_link"));
     std::vector<double> xyz(cn * 3);
@@ -228,168 +234,160 @@ static int cmd_place(Device &dev, char **a, bool exact_pair = false, bool refine
     std::memcpy(xyz.data(), c.data(), xyz.size() * 8);
     std::memcpy(nrm.data(), nr.data(), nrm.size() * 4);
     node.setExcavationGrid(xyz, nrm, bbox.data());
-    const auto tick = node.runOptimization(&zx);
-    if (!tick.ran) {
+    f.tick = node.runOptimization(&zx);
+    if (!f.tick.ran) {
         std::fprintf(stderr, "place: %s\n", node.lastError().c_str());
         return 1;
     }
-    MobileLidarPlacement placement(pp);
-    if (exact_pair) {
-        // place_pair: the exact best pair beside the greedy placement's first two (KMAX sensors
-        // placed greedily for the comparison); the chosen candidates, {base, single, pair}
-        // totals and the pair table
-        if (placement.place_pair(dev, SimplifiedDualLidarOptimizer::Result{}, p).ran) return 3;
-        const auto greedy = placement.place(dev, tick, p);
-        const auto r = placement.place_pair(dev, tick, p, {}, greedy.ran ? &greedy : nullptr);
-        if (!r.ran) {
-            std::fprintf(stderr, "place_pair: %s\n", placement.lastError().c_str());
-            return 1;
-        }
-        std::vector<int64_t> sel;
-        if (r.n_selected == 2) sel = {r.pair[0], r.pair[1]};
-        if (r.n_selected == 1) sel = {r.single};
-        const double tot[3] = {r.base_total, r.single_total, r.pair_total};
-        write_file(a[13], sel.data(), sel.size() * 8);
-        write_file(a[14], tot, sizeof(tot));
-        write_file(a[15], r.log.data(), r.log.size());
-        std::printf("{\"n_candidates\": %zu, \"n_selected\": %d, \"best_pair\": [%lld, %lld], "
-                    "\"pair_covered\": %d, \"best_single\": %lld, \"single_covered\": %d, "
-                    "\"base_covered\": %d, \"total_cells\": %d}\n",
-                    tick.candidates.size(), r.n_selected, (long long)r.pair[0],
-                    (long long)r.pair[1], r.pair_covered, (long long)r.single, r.single_covered,
-                    r.base_covered, r.total_cells);
-        return 0;
-    }
-    if (exact_triple) {
-        // place_triple: the exact best triple beside the greedy placement's first three (KMAX
-        // sensors placed greedily for the comparison); the chosen candidates, {base, single, pair,
-        // triple} totals and the triple table
-        if (placement.place_triple(dev, SimplifiedDualLidarOptimizer::Result{}, p).ran) return 3;
-        const auto greedy = placement.place(dev, tick, p);
-        const auto r = placement.place_triple(dev, tick, p, {}, greedy.ran ? &greedy : nullptr);
-        if (!r.ran) {
-            std::fprintf(stderr, "place_triple: %s\n", placement.lastError().c_str());
-            return 1;
-        }
-        std::vector<int64_t> sel;
-        if (r.n_selected == 3) sel = {r.triple[0], r.triple[1], r.triple[2]};
-        if (r.n_selected == 2) sel = {r.pair[0], r.pair[1]};
-        if (r.n_selected == 1) sel = {r.single};
-        const double tot[4] = {r.base_total, r.single_total, r.pair_total, r.triple_total};
-        write_file(a[13], sel.data(), sel.size() * 8);
-        write_file(a[14], tot, sizeof(tot));
-        write_file(a[15], r.log.data(), r.log.size());
-        std::printf("{\"n_candidates\": %zu, \"n_selected\": %d, \"best_triple\": [%lld, %lld, "
-                    "%lld], \"triple_covered\": %d, \"best_pair\": [%lld, %lld], "
-                    "\"pair_covered\": %d, \"best_single\": %lld, \"single_covered\": %d, "
-                    "\"base_covered\": %d, \"total_cells\": %d}\n",
-                    tick.candidates.size(), r.n_selected, (long long)r.triple[0],
-                    (long long)r.triple[1], (long long)r.triple[2], r.triple_covered,
-                    (long long)r.pair[0], (long long)r.pair[1], r.pair_covered, (long long)r.single,
-                    r.single_covered, r.base_covered, r.total_cells);
-        return 0;
-    }
-    if (refine) {
-        // place_refine: the greedy placement, then single-sensor exchanges from it; the refined
-        // set, {start, final, after each move} totals and the refinement's table
-        if (placement.refine(dev, SimplifiedDualLidarOptimizer::Result{}, p, {0}).ran) return 3;
-        const auto greedy = placement.place(dev, tick, p);
-        if (!greedy.ran || greedy.rounds.empty()) {
-            std::fprintf(stderr, "place_refine: %s\n",
-                         greedy.ran ? "greedy placed nothing" : placement.lastError().c_str());
-            return 1;
-        }
-        std::vector<int64_t> start;
-        for (const auto &q : greedy.rounds) start.push_back(q.candidate);
-        const int n_locked = argc > 16 ? std::atoi(a[16]) : 0;
-        const int max_moves = argc > 17 ? std::atoi(a[17]) : PCP_REFINE_MAX_MOVES;
-        const auto r = placement.refine(dev, tick, p, start, n_locked, max_moves);
-        if (!r.ran) {
-            std::fprintf(stderr, "place_refine: %s\n", placement.lastError().c_str());
-            return 1;
-        }
-        std::vector<double> tot = {r.start_total, r.total};
-        std::string moves;
-        for (const auto &m : r.moves) {
-            tot.push_back(m.total);
-            char buf[96];
-            std::snprintf(buf, sizeof(buf), "%s[%d, %lld, %lld]", moves.empty() ? "" : ", ",
-                          m.slot, (long long)m.from, (long long)m.to);
-            moves += buf;
-        }
-        std::string sel;
-        for (size_t i = 0; i < r.selected.size(); ++i)
-            sel += (i ? ", " : "") + std::to_string((long long)r.selected[i]);
-        write_file(a[13], r.selected.data(), r.selected.size() * 8);
-        write_file(a[14], tot.data(), tot.size() * 8);
-        write_file(a[15], r.log.data(), r.log.size());
-        std::printf("{\"n_candidates\": %zu, \"k\": %zu, \"n_locked\": %d, \"n_moves\": %zu, "
-                    "\"converged\": %d, \"selected\": [%s], \"moves\": [%s], "
-                    "\"start_covered\": %d, \"covered\": %d, \"total_cells\": %d}\n",
-                    tick.candidates.size(), r.selected.size(), r.n_locked, r.moves.size(),
-                    r.converged ? 1 : 0, sel.c_str(), moves.c_str(), r.start_covered, r.covered,
-                    r.total_cells);
-        return 0;
-    }
-    if (aimed) {
-        // place_aimed: limited-field-of-view sensors, every candidate with every aim of the table
-        MobileLidarPlacement::AimedParams ap;
-        ap.h_fov = std::strtod(a[16], nullptr);
-        ap.v_fov = std::strtod(a[17], nullptr);
-        const auto raw = read_file(a[18]);
-        ap.aims.resize(raw.size() / 16);
-        for (size_t i = 0; i < ap.aims.size(); ++i) {
-            std::memcpy(&ap.aims[i].yaw_offset, raw.data() + 16 * i, 8);
-            std::memcpy(&ap.aims[i].pitch, raw.data() + 16 * i + 8, 8);
-        }
-        if (placement.place_aimed(dev, SimplifiedDualLidarOptimizer::Result{}, p, ap).ran) return 3;
-        std::vector<MobileLidarPlacement::FixedAimed> fixed;
-        if (argc > 19) {
-            const auto f = tuple(a[19]);
-            for (size_t i = 0; i + 1 < f.size(); i += 2)
-                fixed.push_back({(int64_t)f[i], (int32_t)f[i + 1]});
-        }
-        const auto r = placement.place_aimed(dev, tick, p, ap, fixed);
-        if (!r.ran) {
-            std::fprintf(stderr, "place_aimed: %s\n", placement.lastError().c_str());
-            return 1;
-        }
-        std::vector<int64_t> sel;
-        std::vector<double> tot;
-        for (const auto &q : r.rounds) {
-            sel.push_back(q.candidate);
-            sel.push_back(q.aim);
-            tot.push_back(q.total);
-        }
-        write_file(a[13], sel.data(), sel.size() * 8);
-        write_file(a[14], tot.data(), tot.size() * 8);
-        write_file(a[15], r.log.data(), r.log.size());
-        std::printf("{\"n_candidates\": %zu, \"n_aims\": %zu, \"n_fixed\": %d, "
-                    "\"n_selected\": %zu, \"base_total\": %.17g, \"base_covered\": %d, "
-                    "\"total_cells\": %d}\n",
-                    tick.candidates.size(), ap.aims.size(), r.n_fixed, r.rounds.size(),
-                    r.base_total, r.base_covered, r.total_cells);
-        return 0;
-    }
-    if (placement.place(dev, SimplifiedDualLidarOptimizer::Result{}, p).ran) return 3;   // no tick
-    const auto r = placement.place(dev, tick, p);
-    if (!r.ran) {
-        std::fprintf(stderr, "place: %s\n", placement.lastError().c_str());
-        return 1;
-    }
-    std::vector<int64_t> sel;
-    std::vector<double> tot;
-    for (const auto &q : r.rounds) {
-        sel.push_back(q.candidate);
-        tot.push_back(q.total);
-    }
+    return 0;
+}
+
+// OUT_SELECTED, OUT_TOTALS, OUT_REPORT
+static void write_placement(char **a, const std::vector<int64_t> &sel,
+                            const std::vector<double> &tot, const std::string &log) {
     write_file(a[13], sel.data(), sel.size() * 8);
     write_file(a[14], tot.data(), tot.size() * 8);
-    write_file(a[15], r.log.data(), r.log.size());
+    write_file(a[15], log.data(), log.size());
+}
+
+// an exact search's answer as candidate indices (triple: null for the pair search)
+static std::vector<int64_t> exact_selection(const MobileLidarPlacement::PairResult &r,
+                                            const int64_t *triple = nullptr) {
+    if (r.n_selected == 3 && triple) return {triple[0], triple[1], triple[2]};
+    if (r.n_selected == 2) return {r.pair[0], r.pair[1]};
+    if (r.n_selected == 1) return {r.single};
+    return {};
+}
+
+// place: KMAX mobile sensors placed greedily; the selected candidates and the totals after each
+static int cmd_place(Device &dev, char **a, int) {
+    PlaceFront f;
+    if (const int rc = place_front(dev, a, f)) return rc;
+    if (f.placement.place(dev, kNoTick, f.p).ran) return 3;
+    const auto r = f.placement.place(dev, f.tick, f.p);
+    if (!r.ran) return f.failed("place");
+    std::vector<int64_t> sel;
+    std::vector<double> tot;
+    for (const auto &q : r.rounds) sel.push_back(q.candidate);
+    for (const auto &q : r.rounds) tot.push_back(q.total);
+    write_placement(a, sel, tot, r.log);
     std::printf("{\"n_candidates\": %zu, \"n_selected\": %zu, \"zx120_total\": %.17g, "
                 "\"zx120_covered\": %d, \"total_cells\": %d}\n",
-                tick.candidates.size(), r.rounds.size(), r.zx120_total, r.zx120_covered,
+                f.tick.candidates.size(), r.rounds.size(), r.zx120_total, r.zx120_covered,
                 r.total_cells);
+    return 0;
+}
+
+// place_pair: the exact best pair, compared with the first two of KMAX sensors placed greedily
+static int cmd_place_pair(Device &dev, char **a, int) {
+    PlaceFront f;
+    if (const int rc = place_front(dev, a, f)) return rc;
+    if (f.placement.place_pair(dev, kNoTick, f.p).ran) return 3;
+    const auto greedy = f.placement.place(dev, f.tick, f.p);
+    const auto r = f.placement.place_pair(dev, f.tick, f.p, {}, greedy.ran ? &greedy : nullptr);
+    if (!r.ran) return f.failed("place_pair");
+    write_placement(a, exact_selection(r), {r.base_total, r.single_total, r.pair_total}, r.log);
+    std::printf("{\"n_candidates\": %zu, \"n_selected\": %d, \"best_pair\": [%lld, %lld], "
+                "\"pair_covered\": %d, \"best_single\": %lld, \"single_covered\": %d, "
+                "\"base_covered\": %d, \"total_cells\": %d}\n",
+                f.tick.candidates.size(), r.n_selected, (long long)r.pair[0], (long long)r.pair[1],
+                r.pair_covered, (long long)r.single, r.single_covered, r.base_covered,
+                r.total_cells);
+    return 0;
+}
+
+// place_triple: the exact best triple, compared with the first three of KMAX placed greedily
+static int cmd_place_triple(Device &dev, char **a, int) {
+    PlaceFront f;
+    if (const int rc = place_front(dev, a, f)) return rc;
+    if (f.placement.place_triple(dev, kNoTick, f.p).ran) return 3;
+    const auto greedy = f.placement.place(dev, f.tick, f.p);
+    const auto r = f.placement.place_triple(dev, f.tick, f.p, {}, greedy.ran ? &greedy : nullptr);
+    if (!r.ran) return f.failed("place_triple");
+    write_placement(a, exact_selection(r, r.triple),
+                    {r.base_total, r.single_total, r.pair_total, r.triple_total}, r.log);
+    std::printf("{\"n_candidates\": %zu, \"n_selected\": %d, \"best_triple\": [%lld, %lld, "
+                "%lld], \"triple_covered\": %d, \"best_pair\": [%lld, %lld], "
+                "\"pair_covered\": %d, \"best_single\": %lld, \"single_covered\": %d, "
+                "\"base_covered\": %d, \"total_cells\": %d}\n",
+                f.tick.candidates.size(), r.n_selected, (long long)r.triple[0],
+                (long long)r.triple[1], (long long)r.triple[2], r.triple_covered,
+                (long long)r.pair[0], (long long)r.pair[1], r.pair_covered, (long long)r.single,
+                r.single_covered, r.base_covered, r.total_cells);
+    return 0;
+}
+
+// place_refine: the greedy placement, then single-sensor exchanges from it
+static int cmd_place_refine(Device &dev, char **a, int argc) {
+    PlaceFront f;
+    if (const int rc = place_front(dev, a, f)) return rc;
+    if (f.placement.refine(dev, kNoTick, f.p, {0}).ran) return 3;
+    const auto greedy = f.placement.place(dev, f.tick, f.p);
+    if (!greedy.ran) return f.failed("place_refine");
+    if (greedy.rounds.empty()) {
+        std::fprintf(stderr, "place_refine: greedy placed nothing\n");
+        return 1;
+    }
+    std::vector<int64_t> start;
+    for (const auto &q : greedy.rounds) start.push_back(q.candidate);
+    const int n_locked = argc > 16 ? std::atoi(a[16]) : 0;
+    const int max_moves = argc > 17 ? std::atoi(a[17]) : PCP_REFINE_MAX_MOVES;
+    const auto r = f.placement.refine(dev, f.tick, f.p, start, n_locked, max_moves);
+    if (!r.ran) return f.failed("place_refine");
+    std::vector<double> tot = {r.start_total, r.total};
+    std::string moves;
+    for (const auto &m : r.moves) {
+        tot.push_back(m.total);
+        char buf[96];
+        std::snprintf(buf, sizeof(buf), "%s[%d, %lld, %lld]", moves.empty() ? "" : ", ", m.slot,
+                      (long long)m.from, (long long)m.to);
+        moves += buf;
+    }
+    std::string sel;
+    for (size_t i = 0; i < r.selected.size(); ++i)
+        sel += (i ? ", " : "") + std::to_string((long long)r.selected[i]);
+    write_placement(a, r.selected, tot, r.log);
+    std::printf("{\"n_candidates\": %zu, \"k\": %zu, \"n_locked\": %d, \"n_moves\": %zu, "
+                "\"converged\": %d, \"selected\": [%s], \"moves\": [%s], "
+                "\"start_covered\": %d, \"covered\": %d, \"total_cells\": %d}\n",
+                f.tick.candidates.size(), r.selected.size(), r.n_locked, r.moves.size(),
+                r.converged ? 1 : 0, sel.c_str(), moves.c_str(), r.start_covered, r.covered,
+                r.total_cells);
+    return 0;
+}
+
+// place_aimed: limited-field-of-view sensors, every candidate with every aim of the table
+static int cmd_place_aimed(Device &dev, char **a, int argc) {
+    PlaceFront f;
+    if (const int rc = place_front(dev, a, f)) return rc;
+    MobileLidarPlacement::AimedParams ap;
+    ap.h_fov = std::strtod(a[16], nullptr);
+    ap.v_fov = std::strtod(a[17], nullptr);
+    const auto raw = read_file(a[18]);
+    ap.aims.resize(raw.size() / 16);
+    for (size_t i = 0; i < ap.aims.size(); ++i) {
+        std::memcpy(&ap.aims[i].yaw_offset, raw.data() + 16 * i, 8);
+        std::memcpy(&ap.aims[i].pitch, raw.data() + 16 * i + 8, 8);
+    }
+    if (f.placement.place_aimed(dev, kNoTick, f.p, ap).ran) return 3;
+    std::vector<MobileLidarPlacement::FixedAimed> fixed;
+    if (argc > 19) {
+        const auto fx = tuple(a[19]);
+        for (size_t i = 0; i + 1 < fx.size(); i += 2)
+            fixed.push_back({(int64_t)fx[i], (int32_t)fx[i + 1]});
+    }
+    const auto r = f.placement.place_aimed(dev, f.tick, f.p, ap, fixed);
+    if (!r.ran) return f.failed("place_aimed");
+    std::vector<int64_t> sel;
+    std::vector<double> tot;
+    for (const auto &q : r.rounds) sel.insert(sel.end(), {q.candidate, (int64_t)q.aim});
+    for (const auto &q : r.rounds) tot.push_back(q.total);
+    write_placement(a, sel, tot, r.log);
+    std::printf("{\"n_candidates\": %zu, \"n_aims\": %zu, \"n_fixed\": %d, "
+                "\"n_selected\": %zu, \"base_total\": %.17g, \"base_covered\": %d, "
+                "\"total_cells\": %d}\n",
+                f.tick.candidates.size(), ap.aims.size(), r.n_fixed, r.rounds.size(),
+                r.base_total, r.base_covered, r.total_cells);
     return 0;
 }
 
@@ -829,45 +827,37 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "usage: pcp_nodes_cli filter|merge|vlidar|place|place_pair|place_triple|place_refine|place_aimed|scan|scan_mounted|area|drivable|replay ...\n");
         return 2;
     }
+    // name, arguments required after it, the command (a: the arguments, argc: how many)
+    struct Command {
+        const char *name;
+        int need;
+        int (*run)(Device &dev, char **a, int argc);
+    };
+    static const Command commands[] = {
+        {"filter", 8, [](Device &d, char **a, int) { return cmd_filter(d, a); }},
+        {"merge", 7, [](Device &d, char **a, int) { return cmd_merge(d, a); }},
+        {"vlidar", 14, cmd_vlidar},
+        {"place", 16, cmd_place},
+        {"place_pair", 16, cmd_place_pair},
+        {"place_triple", 16, cmd_place_triple},
+        {"place_refine", 16, cmd_place_refine},
+        {"place_aimed", 19, cmd_place_aimed},
+        {"scan", 10, [](Device &d, char **a, int) { return cmd_scan(d, a); }},
+        {"scan_mounted", 11, [](Device &d, char **a, int) { return cmd_scan(d, a, /*mounted=*/true); }},
+        {"area", 10, [](Device &d, char **a, int) { return cmd_area(d, a); }},
+        {"drivable", 7, [](Device &d, char **a, int) { return cmd_drivable(d, a); }},
+        {"replay", 8, [](Device &d, char **a, int) { return cmd_replay(d, a); }},
+    };
     const std::string cmd = argv[1];
-    const int need = cmd == "filter"   ? 8
-                     : cmd == "merge"  ? 7
-                     : cmd == "vlidar" ? 14
-                     : cmd == "place"  ? 16
-                     : cmd == "place_pair" ? 16
-                     : cmd == "place_triple" ? 16
-                     : cmd == "place_refine" ? 16
-                     : cmd == "place_aimed" ? 19
-                     : cmd == "scan"   ? 10
-                     : cmd == "scan_mounted" ? 11
-                     : cmd == "area"   ? 10
-                     : cmd == "drivable" ? 7
-                     : cmd == "replay" ? 8
-                                       : -1;
-    if (need < 0 || argc - 2 < need) {
+    const Command *c = std::find_if(std::begin(commands), std::end(commands),
+                                    [&cmd](const Command &k) { return cmd == k.name; });
+    if (c == std::end(commands) || argc - 2 < c->need) {
         std::fprintf(stderr, "bad arguments for %s\n", cmd.c_str());
         return 2;
     }
     try {
         Device dev(0);
-        if (cmd == "filter") return cmd_filter(dev, argv + 2);
-        if (cmd == "merge") return cmd_merge(dev, argv + 2);
-        if (cmd == "vlidar") return cmd_vlidar(dev, argv + 2, argc - 2);
-        if (cmd == "place") return cmd_place(dev, argv + 2);
-        if (cmd == "place_pair") return cmd_place(dev, argv + 2, /*exact_pair=*/true);
-        if (cmd == "place_triple")
-            return cmd_place(dev, argv + 2, /*exact_pair=*/false, /*refine=*/false, 16,
-                             /*exact_triple=*/true);
-        if (cmd == "place_refine")
-            return cmd_place(dev, argv + 2, /*exact_pair=*/false, /*refine=*/true, argc - 2);
-        if (cmd == "place_aimed")
-            return cmd_place(dev, argv + 2, /*exact_pair=*/false, /*refine=*/false, argc - 2,
-                             /*exact_triple=*/false, /*aimed=*/true);
-        if (cmd == "scan") return cmd_scan(dev, argv + 2);
-        if (cmd == "scan_mounted") return cmd_scan(dev, argv + 2, /*mounted=*/true);
-        if (cmd == "area") return cmd_area(dev, argv + 2);
-        if (cmd == "drivable") return cmd_drivable(dev, argv + 2);
-        return cmd_replay(dev, argv + 2);
+        return c->run(dev, argv + 2, argc - 2);
     } catch (const std::exception &e) {
         std::fprintf(stderr, "%s\n", e.what());
         return 1;

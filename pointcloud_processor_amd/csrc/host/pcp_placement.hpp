@@ -72,26 +72,12 @@ class MobileLidarPlacement {
     // The exact best triple (pcp_place_triple): every triple of the tick's candidates evaluated
     // beside zx120 and the `fixed` candidates, with the best pair, the best single and the base it
     // is compared with.
-    struct TripleResult {
-        bool ran = false;              // false: the tick did not run, or the call failed
-        int32_t n_selected = 0;        // 3: the triple beats the pair, the single and the base;
-                                       // 2, 1, 0: as PairResult
+    struct TripleResult : PairResult {   // n_selected 3: the triple beats the pair, the single
+                                         // and the base; 2, 1, 0: as PairResult
         int64_t triple[3] = {-1, -1, -1};   // candidate indices, a < b < c; -1: no admissible triple
         double triple_total = 0;
         int32_t triple_covered = 0;
-        int64_t pair[2] = {-1, -1};
-        double pair_total = 0;
-        int32_t pair_covered = 0;
-        int64_t single = -1;
-        double single_total = 0;
-        int32_t single_covered = 0;
-        double base_total = 0;         // zx120 and the fixed sensors alone
-        int32_t base_covered = 0;
-        int32_t n_fixed = 0;
-        int32_t total_cells = 0;
-        std::vector<SimplifiedDualLidarOptimizer::LidarPosition> placed;   // the n_selected chosen
-        SimplifiedDualLidarOptimizer::LidarPosition triple_pos[3], pair_pos[2], single_pos;
-        std::string log;
+        SimplifiedDualLidarOptimizer::LidarPosition triple_pos[3];   // where it exists
     };
     // min_separation is params()'s; num_mobile_lidars plays no part.  greedy (nullable): a
     // place() result for the same tick, whose first three sensors the log compares the triple with
@@ -147,12 +133,8 @@ class MobileLidarPlacement {
         int64_t candidate = -1;
         int32_t aim = -1;
     };
-    struct AimedRound {
-        int64_t candidate = -1;        // index into the tick's candidates
+    struct AimedRound : Round {
         int32_t aim = -1;              // index into AimedParams::aims
-        double total = 0, gain = 0;    // as Round's
-        int32_t covered = 0;
-        double coverage_ratio = 0;
     };
     struct AimedResult {
         bool ran = false;              // false: the tick did not run, or the call failed

@@ -1,5 +1,5 @@
-"""pcp_place_shared.hpp (what pcp_place.hip, pcp_pairs.hip and pcp_refine.hip share, DESIGN.md
-§6h/§6i) on the CPU: its first part has no HIP dependency, so
+"""pcp_place_shared.hpp (what pcp_place.hip, pcp_pairs.hip, pcp_triples.hip, pcp_refine.hip and
+pcp_aim.hip share) on the CPU: its first part has no HIP dependency, so
 tests/native/place_shared_selftest.cpp is built with the host compiler and run as a stand-alone
 program, no GPU call."""
 import os
