@@ -775,6 +775,78 @@ int pcp_simulate_scan_mounted_burst(pcp_ctx *ctx, const double *poses6, uint64_t
                                     const pcp_fan_params *fan, const double *el_table, int reps,
                                     double ms[2]);
 
+/* Placement by the terrain the scans reach: greedy maximum coverage over simulated scans, wholly
+ * on the device.
+ * N = pcp_simulate_scan's N (the input point count of the cloud the current terrain index was
+ * built from; 0 without an index).  seen(p) = the set of input indices pcp_simulate_scan reports
+ * as hit_point[p][j][i] >= 0 for the same pose and fan (the mounted twin: what
+ * pcp_simulate_scan_mounted reports for the same poses6 row and beam table) -- the march, the
+ * query point, the float accumulator and the lowest-index tie rule are the scan's.  R = the
+ * region of interest: {0 .. N-1} with roi NULL, else {i : roi[i] != 0}; *roi_points = |R|.  The
+ * separation expression and the first-maximum rule are pcp_place_sensors', applied to columns 0
+ * and 1 of the pose rows.
+ *   1. need = R.  For i = 0 .. n_fixed-1 in list order: the points of seen(fixed[i]) in need get
+ *      owner i and leave need.  *base_covered = |R| - |need|.  A pose is alive unless it is fixed
+ *      or (min_separation > 0) closer than the separation to a fixed pose.
+ *   2. Round r = 0 .. k_max-1: stop when no pose is alive; g[p] = |seen(p) & need| for the alive
+ *      p; round_gains[r][p] = g[p], -1 for the others; b = the first maximum (the lowest index
+ *      among the largest g); stop unless g[b] > 0.
+ *   3. selected[r] = b, gain[r] = g[b], covered_after[r] = base_covered + gain[0] + .. + gain[r];
+ *      the points of seen(b) in need get owner n_fixed + r and leave need; b leaves the search
+ *      and, with min_separation > 0, so does every pose closer to b than the separation.
+ *   4. *n_selected = rounds recorded (entries and rows from there on are not written).
+ *      point_owner[i] = the owner, or PCP_OWNER_NONE for the points of R nobody reaches and for
+ *      every point outside R: the blind spots of the answer are R and owner == NONE.
+ *      seen_points[p] = |seen(p)| over all N points (pcp_simulate_scan's seen_points[p]).
+ *      *n_points = N.
+ * PCP_E_INVALID before any launch, nothing written: what pcp_raycast_fan / _mounted refuse (fan
+ * dimensions, a step table past PCP_MAX_STEPS, a non-finite el_table entry), n >
+ * PCP_COVER_MAX_POSES or n * n_az * n_el > 2^31, k_max outside 1 .. PCP_PLACE_MAX, n_fixed
+ * outside 0 .. PCP_PLACE_MAX, reserved != 0, a fixed index >= n or listed twice, roi given with
+ * roi_n != N, a null required pointer (everything not marked nullable), a null context.
+ * PCP_E_CAPACITY before any launch when point_owner is given with owner_cap < N: *n_points = N is
+ * set and nothing else is written.  n == 0 or N == 0: PCP_OK, *n_selected = 0, *base_covered = 0,
+ * *roi_points as defined.
+ * One host synchronisation per call; deterministic (two calls give identical bytes); the caller's
+ * GridCell flags and the other queries' device buffers are not touched (the call's scratch is its
+ * own).  The fan launch is timed under PCP_K_RAYCAST_FAN, the rounds under PCP_K_PLACE. */
+#define PCP_COVER_MAX_POSES 1024
+typedef struct pcp_cover_params {
+    int32_t k_max;          /* sensors to place, 1 .. PCP_PLACE_MAX */
+    int32_t n_fixed;        /* sensors already placed, 0 .. PCP_PLACE_MAX */
+    int32_t reserved[2];    /* 0 */
+    double  min_separation; /* metres in XY; <= 0: none */
+    int64_t fixed[PCP_PLACE_MAX];   /* indices into the poses, first n_fixed used */
+} pcp_cover_params;
+int pcp_place_coverage(pcp_ctx *ctx, const double *poses5, uint64_t n, const pcp_fan_params *fan,
+                       const pcp_cover_params *cp,
+                       const uint8_t *roi, uint64_t roi_n,       /* nullable; [N], non-zero = counts */
+                       int64_t *selected,                        /* [k_max] */
+                       uint64_t *gain, uint64_t *covered_after,  /* [k_max] */
+                       int64_t *round_gains,                     /* nullable [k_max][n], -1: not alive */
+                       uint32_t *seen_points,                    /* nullable [n] */
+                       int32_t *point_owner, uint64_t owner_cap, /* nullable [N] */
+                       uint64_t *n_points, uint64_t *roi_points, uint64_t *base_covered,
+                       int32_t *n_selected);
+int pcp_place_coverage_mounted(pcp_ctx *ctx, const double *poses6, uint64_t n,
+                               const pcp_fan_params *fan, const double *el_table,
+                               const pcp_cover_params *cp, const uint8_t *roi, uint64_t roi_n,
+                               int64_t *selected, uint64_t *gain, uint64_t *covered_after,
+                               int64_t *round_gains, uint32_t *seen_points, int32_t *point_owner,
+                               uint64_t owner_cap, uint64_t *n_points, uint64_t *roi_points,
+                               uint64_t *base_covered, int32_t *n_selected);
+/* Kernel timing of pcp_place_coverage (the timing tool only): ms[0] = the query's production fan
+ * kernel per launch (as pcp_simulate_scan_burst), ms[1] = clear, resolve into the bitsets and
+ * counts per repetition, ms[2] = round 0's gain launch with the selection and nothing committed,
+ * per repetition; `reps` repetitions between two events each.  n >= 1, a terrain index present. */
+int pcp_place_coverage_burst(pcp_ctx *ctx, const double *poses5, uint64_t n,
+                             const pcp_fan_params *fan, const pcp_cover_params *cp,
+                             const uint8_t *roi, uint64_t roi_n, int reps, double ms[3]);
+int pcp_place_coverage_mounted_burst(pcp_ctx *ctx, const double *poses6, uint64_t n,
+                                     const pcp_fan_params *fan, const double *el_table,
+                                     const pcp_cover_params *cp, const uint8_t *roi,
+                                     uint64_t roi_n, int reps, double ms[3]);
+
 /* Diagnostic build with s_memtime stamps (shader clock) per wave: stamps[(p*W + w)*4 + i],
  * W = ceil(n_az*n_el/64), i = 0 start, 1 after direction setup, 2 after the march, 3 end.
  * For locating where wave lifetime goes; never used for timing. */

@@ -130,6 +130,15 @@ class AimParams(C.Structure):
 SCAN_MAX_POSES = 64   # PCP_SCAN_MAX_POSES: poses one pcp_simulate_scan call casts (mask bits)
 
 
+COVER_MAX_POSES = 1024   # PCP_COVER_MAX_POSES: poses one pcp_place_coverage call searches
+
+
+class CoverParams(C.Structure):
+    """pcp_cover_params."""
+    _fields_ = [("k_max", C.c_int32), ("n_fixed", C.c_int32), ("reserved", C.c_int32 * 2),
+                ("min_separation", C.c_double), ("fixed", C.c_int64 * PLACE_MAX)]
+
+
 class ScanReturn(C.Structure):
     """pcp_scan_return: one blocked ray's hit (24 bytes)."""
     _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("range", C.c_float),
@@ -287,6 +296,20 @@ _SIGS = [
                                             C.POINTER(C.c_uint64)]),
     ("pcp_simulate_scan_mounted_burst", C.c_int, [_P, _P, C.c_uint64, C.POINTER(FanParams), _P,
                                                   C.c_int, _P]),
+    ("pcp_place_coverage", C.c_int, [_P, _P, C.c_uint64, C.POINTER(FanParams),
+                                     C.POINTER(CoverParams), _P, C.c_uint64, _P, _P, _P, _P, _P,
+                                     _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                     C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),
+    ("pcp_place_coverage_mounted", C.c_int, [_P, _P, C.c_uint64, C.POINTER(FanParams), _P,
+                                             C.POINTER(CoverParams), _P, C.c_uint64, _P, _P, _P,
+                                             _P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64),
+                                             C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                             C.POINTER(C.c_int32)]),
+    ("pcp_place_coverage_burst", C.c_int, [_P, _P, C.c_uint64, C.POINTER(FanParams),
+                                           C.POINTER(CoverParams), _P, C.c_uint64, C.c_int, _P]),
+    ("pcp_place_coverage_mounted_burst", C.c_int, [_P, _P, C.c_uint64, C.POINTER(FanParams), _P,
+                                                   C.POINTER(CoverParams), _P, C.c_uint64,
+                                                   C.c_int, _P]),
     ("pcp_debug_exclusive_scan", C.c_int, [_P, _P, C.c_uint64, _P]),
     ("pcp_debug_math", C.c_int, [_P, C.c_int, _P, _P, C.c_uint64, _P, _P]),
     ("pcp_debug_fine_copy", C.c_int, [_P, C.POINTER(FineGeo), _P, C.c_uint64, _P, C.c_uint64, _P,
@@ -1477,6 +1500,97 @@ class Context:
                                                      C.byref(fan), reps, _ptr(ms)),
                     "pcp_simulate_scan_burst")
         return float(ms[0]), float(ms[1])
+
+    @staticmethod
+    def _cover_params(k_max, min_separation, fixed, reserved, n_fixed=None) -> CoverParams:
+        fixed = [int(f) for f in fixed]
+        cp = CoverParams(int(k_max), len(fixed) if n_fixed is None else int(n_fixed),
+                         (C.c_int32 * 2)(int(reserved), 0), float(min_separation))
+        for i, f in enumerate(fixed[:PLACE_MAX]):
+            cp.fixed[i] = f
+        return cp
+
+    @staticmethod
+    def _roi(roi):
+        if roi is None:
+            return None, 0
+        r = np.ascontiguousarray(np.asarray(roi).reshape(-1) != 0, np.uint8)
+        return r, r.shape[0]
+
+    def place_coverage(self, poses5, fan: FanParams, k_max: int, min_separation: float = 0.0,
+                       fixed=(), roi=None, want_round_gains: bool = False,
+                       want_owner: bool = False, reserved: int = 0, owner_cap: int | None = None,
+                       _mounted=None) -> dict:
+        """pcp_place_coverage: greedy maximum coverage over simulated scans -- each round places
+        the pose whose scan reaches the most terrain points of the region of interest `roi` (None:
+        every point; else [N], non-zero counts) that no placed or fixed sensor reaches yet.
+        -> dict: selected, gain, covered_after [n_selected], n_selected, n_points, roi_points,
+        base_covered, seen_points [P], round_gains int64 [n_selected, P] (want_round_gains, else
+        None; -1: not alive), point_owner int32 [n_points] (want_owner, else None; OWNER_NONE:
+        nobody reaches the point, or it lies outside the region)."""
+        # (_mounted: place_coverage_mounted's (el_table,), the same call on poses6 rows)
+        poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 6 if _mounted else 5)
+        what = "pcp_place_coverage_mounted" if _mounted else "pcp_place_coverage"
+        fn = getattr(self.lib, what)
+        lead = (_ptr(_mounted[0]),) if _mounted else ()
+        P = poses.shape[0]
+        K = max(int(k_max), 1)
+        cp = self._cover_params(k_max, min_separation, fixed, reserved)
+        r8, rn = self._roi(roi)
+        sel = np.zeros(min(K, PLACE_MAX), np.int64)
+        gain = np.zeros(min(K, PLACE_MAX), np.uint64)
+        cov = np.zeros(min(K, PLACE_MAX), np.uint64)
+        rg = np.zeros((min(K, PLACE_MAX), max(P, 1)), np.int64) if want_round_gains else None
+        seen = np.zeros(max(P, 1), np.uint32)
+        ocap = 0
+        if want_owner:
+            ocap = self.scan_points() if owner_cap is None else int(owner_cap)
+        own = np.zeros(max(ocap, 1), np.int32) if want_owner else None
+        npts, rpts, base = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        ns = C.c_int32()
+        self._check(fn(self.h, _ptr(poses) if P else None, P, C.byref(fan), *lead, C.byref(cp),
+                       _ptr(r8), rn, _ptr(sel), _ptr(gain), _ptr(cov), _ptr(rg), _ptr(seen),
+                       _ptr(own), ocap, C.byref(npts), C.byref(rpts), C.byref(base),
+                       C.byref(ns)), what)
+        k = ns.value
+        return {"selected": sel[:k].copy(), "gain": gain[:k].copy(),
+                "covered_after": cov[:k].copy(), "n_selected": k, "n_points": npts.value,
+                "roi_points": rpts.value, "base_covered": base.value, "seen_points": seen[:P],
+                "round_gains": rg[:k, :P] if want_round_gains else None,
+                "point_owner": own[:npts.value] if want_owner else None}
+
+    def place_coverage_mounted(self, poses6, fan: FanParams, el_table=None, k_max: int = 1,
+                               min_separation: float = 0.0, fixed=(), roi=None,
+                               want_round_gains: bool = False, want_owner: bool = False,
+                               reserved: int = 0) -> dict:
+        """pcp_place_coverage_mounted: place_coverage over tilted mounts -- poses6 rows x, y, z,
+        roll, pitch, yaw -- with an optional beam table el_table [n_el] in radians."""
+        return self.place_coverage(poses6, fan, k_max, min_separation, fixed, roi,
+                                   want_round_gains, want_owner, reserved,
+                                   _mounted=(self._el_table(fan, el_table),))
+
+    def place_coverage_burst(self, poses5, fan: FanParams, k_max: int = 1,
+                             min_separation: float = 0.0, fixed=(), roi=None, reps: int = 20,
+                             _mounted=None):
+        """pcp_place_coverage_burst -> (fan kernel ms per launch, bitset phase ms per repetition,
+        round 0's gain launch ms per repetition)."""
+        poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 6 if _mounted else 5)
+        what = "pcp_place_coverage_mounted_burst" if _mounted else "pcp_place_coverage_burst"
+        lead = (_ptr(_mounted[0]),) if _mounted else ()
+        cp = self._cover_params(k_max, min_separation, fixed, 0)
+        r8, rn = self._roi(roi)
+        ms = np.zeros(3, np.float64)
+        self._check(getattr(self.lib, what)(self.h, _ptr(poses), poses.shape[0], C.byref(fan),
+                                            *lead, C.byref(cp), _ptr(r8), rn, reps, _ptr(ms)),
+                    what)
+        return float(ms[0]), float(ms[1]), float(ms[2])
+
+    def place_coverage_mounted_burst(self, poses6, fan: FanParams, el_table=None, k_max: int = 1,
+                                     min_separation: float = 0.0, fixed=(), roi=None,
+                                     reps: int = 20):
+        """pcp_place_coverage_mounted_burst -> place_coverage_burst's triple."""
+        return self.place_coverage_burst(poses6, fan, k_max, min_separation, fixed, roi, reps,
+                                         _mounted=(self._el_table(fan, el_table),))
 
     def score_poses_stats(self, poses5, zx120_pose5, params: VlParams) -> dict:
         """pcp_score_poses_stats: the gather lane-loads of the query's visibility rays

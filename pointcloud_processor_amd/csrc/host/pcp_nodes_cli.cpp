@@ -23,6 +23,11 @@
 //   pcp_nodes_cli scan_mounted TERRAIN.f32 TN POSES(6 per sensor: x,y,z,roll,pitch,yaw) NAZ NEL
 //                         MAXD ELTABLE|- OUT_SCANS.bin ... (scan's outputs; ELTABLE: NEL radians)
 //                         OUT_OFFSETS.u64 OUT_BLIND.f32 OUT_MASK.u64
+//   pcp_nodes_cli cover   TERRAIN.f32 TN POSES(5 per candidate, or a .f64 file of them) NAZ NEL MAXD
+//                         KMAX MINSEP ROI.u8|- OUT_SELECTED.i64 OUT_OWNER.i32 OUT_BLIND.f32 [FIXED]:
+//                         KMAX sensors placed by the terrain points their scans reach, within the
+//                         region ROI.u8 (TN bytes, non-zero counts; -: every point), beside the
+//                         candidates FIXED (c,c,..); OUT_SELECTED: candidate, gain, covered per round
 //   pcp_nodes_cli drivable IN.f32 N STEP TF(7) R1(2) R2(2) OUT.i8
 //   pcp_nodes_cli replay  TERRAIN.f32 TN CELLS.f64 NORMALS.f32 CN BBOX(6) FRAMES POINTS
 //
@@ -39,6 +44,7 @@
 #include <string>
 #include <vector>
 
+#include "pcp_cover_node.hpp"
 #include "pcp_nodes.hpp"
 #include "pcp_placement.hpp"
 #include "pcp_scan_node.hpp"
@@ -456,6 +462,90 @@ static int cmd_scan(Device &dev, char **a, bool mounted = false) {
     return 0;
 }
 
+// the coverage placement of the given candidate poses against a terrain: the rounds' records, the
+// per-point owners and the blind-spot records of the region
+static int cmd_cover(Device &dev, char **a, int argc) {
+    const auto t = read_file(a[0]);
+    const size_t tn = std::strtoull(a[1], nullptr, 10);
+    std::vector<double> pv;
+    const std::string ps = a[2];
+    if (ps.size() > 4 && ps.compare(ps.size() - 4, 4, ".f64") == 0) {
+        const auto raw = read_file(a[2]);
+        pv.resize(raw.size() / 8);
+        std::memcpy(pv.data(), raw.data(), pv.size() * 8);
+        if (raw.size() % 8 != 0) pv.push_back(0.0);   // (refused below)
+    } else {
+        pv = tuple(a[2]);
+    }
+    if (pv.size() % 5 != 0) {
+        std::fprintf(stderr, "cover: POSES holds %zu numbers, not 5 per candidate\n", pv.size());
+        return 2;
+    }
+    VirtualScan::Params sp;
+    sp.n_az = std::atoi(a[3]);
+    sp.n_el = std::atoi(a[4]);
+    sp.max_distance = std::strtod(a[5], nullptr);
+    CoveragePlacement::Params cp;
+    cp.num_mobile_lidars = std::atoi(a[6]);
+    cp.min_separation = std::strtod(a[7], nullptr);
+    CoveragePlacement::Roi roi;
+    if (std::strcmp(a[8], "-") != 0) {
+        roi = CoveragePlacement::Roi(read_file(a[8]));
+        if (roi.bytes.size() != tn) {
+            std::fprintf(stderr, "cover: ROI holds %zu bytes, not TN\n", roi.bytes.size());
+            return 2;
+        }
+    }
+    std::vector<int64_t> fixed;
+    if (argc > 12)
+        for (double f : tuple(a[12])) {
+            if (f != (double)(int64_t)f || f < 0 || f >= (double)(pv.size() / 5)) {
+                std::fprintf(stderr, "cover: FIXED entry %g is no candidate\n", f);
+                return 2;
+            }
+            fixed.push_back((int64_t)f);
+        }
+    if (fixed.size() > PCP_PLACE_MAX) {
+        std::fprintf(stderr, "cover: more than %d FIXED candidates\n", PCP_PLACE_MAX);
+        return 2;
+    }
+    SimplifiedDualLidarOptimizer node(dev, SimplifiedDualLidarOptimizer::Params{});
+    const PointCloud2 terrain = cloud_from(t, tn, 32, "map");
+    node.terrainCallback(terrain);
+    std::vector<SimplifiedDualLidarOptimizer::LidarPosition> cand(pv.size() / 5);
+    for (size_t i = 0; i < cand.size(); ++i) {
+        cand[i].x = pv[5 * i];
+        cand[i].y = pv[5 * i + 1];
+        cand[i].z = pv[5 * i + 2];
+        cand[i].pitch = pv[5 * i + 3];
+        cand[i].yaw = pv[5 * i + 4];
+    }
+    CoveragePlacement place(cp);
+    const auto r = place.place(dev, terrain, cand, sp, fixed, roi);
+    if (!r.ran) {
+        std::fprintf(stderr, "cover: %s\n", place.lastError().c_str());
+        return 1;
+    }
+    std::vector<int64_t> rec;
+    for (const auto &q : r.rounds) {
+        rec.push_back(q.candidate);
+        rec.push_back((int64_t)q.gain);
+        rec.push_back((int64_t)q.covered);
+    }
+    write_file(a[9], rec.data(), rec.size() * 8);
+    write_file(a[10], r.point_owner.data(), r.point_owner.size() * 4);
+    write_file(a[11], r.blind_spots.data.data(), r.blind_spots.data.size());
+    std::fputs(r.log.c_str(), stderr);
+    std::printf("{\"n_candidates\": %zu, \"n_selected\": %zu, \"n_points\": %llu, "
+                "\"roi_points\": %llu, \"base_covered\": %llu, \"covered\": %llu, "
+                "\"n_blind\": %u}\n",
+                cand.size(), r.rounds.size(), (unsigned long long)r.n_points,
+                (unsigned long long)r.roi_points, (unsigned long long)r.base_covered,
+                (unsigned long long)(r.rounds.empty() ? r.base_covered : r.rounds.back().covered),
+                r.blind_spots.width);
+    return 0;
+}
+
 // HDL-64-like scan (64 rings, -24.9..+2 deg) of n points against a ground plane
 static std::vector<float> synth_scan(size_t n, double h, std::mt19937_64 &rng) {
     std::uniform_real_distribution<double> ua(-M_PI, M_PI), ur(1.0, 40.0);
@@ -824,7 +914,7 @@ int main(int argc, char **argv) {
         if (!hp || std::atoi(hp) != 0) setenv("HSA_ENABLE_INTERRUPT", "0", 0);
     }
     if (argc < 2) {
-        std::fprintf(stderr, "usage: pcp_nodes_cli filter|merge|vlidar|place|place_pair|place_triple|place_refine|place_aimed|scan|scan_mounted|area|drivable|replay ...\n");
+        std::fprintf(stderr, "usage: pcp_nodes_cli filter|merge|vlidar|place|place_pair|place_triple|place_refine|place_aimed|scan|scan_mounted|cover|area|drivable|replay ...\n");
         return 2;
     }
     // name, arguments required after it, the command (a: the arguments, argc: how many)
@@ -844,6 +934,7 @@ int main(int argc, char **argv) {
         {"place_aimed", 19, cmd_place_aimed},
         {"scan", 10, [](Device &d, char **a, int) { return cmd_scan(d, a); }},
         {"scan_mounted", 11, [](Device &d, char **a, int) { return cmd_scan(d, a, /*mounted=*/true); }},
+        {"cover", 12, cmd_cover},
         {"area", 10, [](Device &d, char **a, int) { return cmd_area(d, a); }},
         {"drivable", 7, [](Device &d, char **a, int) { return cmd_drivable(d, a); }},
         {"replay", 8, [](Device &d, char **a, int) { return cmd_replay(d, a); }},

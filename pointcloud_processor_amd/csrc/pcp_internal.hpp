@@ -341,6 +341,11 @@ struct pcp_ctx : pcp::CtxStreams {
     // pcp_raycast_fan leaves and expects them)
     pcp::DevBuf vscan_d;
     pcp::PinnedBuf vscan_host;
+    // pcp_place_coverage (pcp_cover.hip): its state, counts, round gains, alive mask, the need
+    // words, the poses' bitsets, the owners and the staged ROI bytes, and the pinned landing of its
+    // downloads (its own, as the scan's)
+    pcp::DevBuf cover_d;
+    pcp::PinnedBuf cover_host;
     pcp::PinnedBuf res_host;                 // pinned landing of the filter chain's sizes
     pcp::PinnedBuf fm_res_host;              // pcp_filter_merge's result sizes, stored by its
                                              // kernels themselves (fixed: a graph holds it)

@@ -12,10 +12,8 @@
 #include <algorithm>
 #include <cstring>
 
-#include "pcp_fan_dir.hpp"
-#include "pcp_fan_row.hpp"
 #include "pcp_internal.hpp"
-#include "pcp_stencil.hpp"
+#include "pcp_scan_hit.hpp"
 
 namespace pcp {
 namespace {
@@ -30,14 +28,8 @@ constexpr int kSlots = 32, kSlotWords = 128;
 static_assert(sizeof(pcp_scan_return) == 24, "pcp_scan_return is a 24-byte record");
 
 struct ResolveArgs {
-    GridView g;
-    const double *ca, *sa, *ce, *se;
-    const double *pose;                  // P x kFanRow, pcp_fan_row.hpp's rows
-                                         // (MT: P x kFanDirRow, pcp_fan_dir.hpp's rows)
-    const double *steps;
-    int n_az;
+    ScanHitQuery q;                      // the hit search's tables (pcp_scan_hit.hpp)
     uint32_t rays, waves, P;
-    float r2;
     const int16_t *first_hit;            // [P][rays], the march's
     const uint32_t *wbase;               // exclusive scan of the waves' blocked counts (mod 2^32)
     const unsigned long long *offsets;   // [P + 1]
@@ -86,9 +78,8 @@ k_scan_prepare(const uint2 *__restrict__ part, uint32_t nW, uint32_t waves, uint
 
 // One lane per ray in the fan's wave-to-ray mapping (wave w of pose p = rays 64 w .. 64 w + 63),
 // so a wave's ballot of blocked lanes counts what the march's wave counted.  A blocked lane
-// rebuilds the march's query point of its first blocked sample, walks the eight cell runs of its
-// stencil in the cell-major copy (descending z per run: a point r below q ends the run) and
-// keeps the (acc, input index) minimum over the points within r.
+// finds its hit point by pcp_scan_hit.hpp's search (the march's query point of its first blocked
+// sample, the eight cell runs of its stencil, the (acc, input index) minimum within r).
 // MT: a mounted query -- the direction is the mounted march's own fan_dir() (pcp_fan_dir.hpp).
 template <bool MT>
 __global__ void __launch_bounds__(kST) k_scan_resolve(ResolveArgs a) {
@@ -114,66 +105,11 @@ __global__ void __launch_bounds__(kST) k_scan_resolve(ResolveArgs a) {
     // (a difference of two prefix sums mod 2^32: exact, a pose has at most 2^30 rays)
     const unsigned long long slot =
         a.offsets[p] + (unsigned long long)(uint32_t)(a.wbase[gw] - a.wbase[p * a.waves]) + pre;
-    // the march's q_k (fan_body, march)
-    const uint32_t j = ray / (uint32_t)a.n_az, i = ray - j * (uint32_t)a.n_az;
-    const double cej = a.ce[j];
-    const double lx = cej * a.ca[i], ly = cej * a.sa[i], lz = a.se[j];
-    const double *Pq = a.pose + (MT ? kFanDirRow : kFanRow) * (size_t)p;
-    const double px = Pq[0], py = Pq[1], pz = Pq[2];
-    double dx, dy, dz;
-    if (MT) {
-        const FanDir d = fan_dir(Pq, lx, ly, lz);
-        dx = d.x;
-        dy = d.y;
-        dz = d.z;
-    } else {
-        const double cy = Pq[FR_CY], sy = Pq[FR_SY];
-        dx = cy * lx - sy * ly;
-        dy = sy * lx + cy * ly;
-        dz = lz;
-    }
-    const double s = a.steps[k];
-    const float qx = (float)(px + dx * s);
-    const float qy = (float)(py + dy * s);
-    const float qz = (float)(pz + dz * s);
-    float best = 0.0f;
-    uint32_t bidx = 0xFFFFFFFFu;
-    float bx = 0.0f, by = 0.0f, bz = 0.0f;
-    // one point against the running (acc, input index) minimum; true: the point lies r or more
-    // below q, so every later point of its run does too
-    auto take = [&](const float4 &v) {
-        const float d0 = qx - v.x, d1 = qy - v.y, d2 = qz - v.z;
-        float acc = 0.0f;
-        acc = acc + d0 * d0;
-        acc = acc + d1 * d1;
-        acc = acc + d2 * d2;
-        const uint32_t vi = __float_as_uint(v.w);
-        if (acc < a.r2 && (bidx == 0xFFFFFFFFu || acc < best || (acc == best && vi < bidx))) {
-            best = acc;
-            bidx = vi;
-            bx = v.x;
-            by = v.y;
-            bz = v.z;
-        }
-        return d2 >= 0.0f && d2 * d2 >= a.r2;
-    };
-    uint32_t ix, iy, iz;
-    if (stencil_cell3_fb(a.g, qx, qy, qz, ix, iy, iz)) {
-        const uint32_t nx = (uint32_t)a.g.nx, nxy = nx * (uint32_t)a.g.ny;
-        const uint32_t lin = ix + nx * iy + nxy * iz;
-        // (the rounds of independent loads the march's scan_stencil issues -- all eight first
-        // points at once, or the eight runs in lockstep -- measured the same 133 us here: the
-        // kernel is bound by the number of point gathers, not by their latency)
-#pragma unroll 1
-        for (int r = 0; r < 4; ++r) {
-            // cells c, c + 1 of one stencil row and the end of c + 1 in one directory load
-            const U3 u = ld_u3o(a.g.start, lin + (uint32_t)(r & 1) * nx + (uint32_t)(r >> 1) * nxy);
-            for (uint32_t t = u.a; t < u.b; ++t)
-                if (take(a.g.pts[t])) break;
-            for (uint32_t t = u.b; t < u.c; ++t)
-                if (take(a.g.pts[t])) break;
-        }
-    }
+    // the hit search (pcp_scan_hit.hpp): the march's q_k, the eight runs, the (acc, index) minimum
+    const ScanHit h = scan_hit<MT>(a.q, p, ray, k);
+    const uint32_t bidx = h.idx;
+    const float bx = h.x, by = h.y, bz = h.z;
+    const double px = h.px, py = h.py, pz = h.pz;
     // (bidx stays ~0 only if the blocking set were empty, which the march excludes: the record
     // is still written, so that the segment holds no unwritten row)
     float range = -1.0f;
@@ -315,19 +251,10 @@ int resolve_enqueue(pcp_ctx *ctx, const ScanPlan &s, const pcp_fan_params *fan, 
     }
     if (int rc = exclusive_scan_u32(ctx, cnt, wbase, nW, blk + s.tmp_off)) return rc;
     ResolveArgs a{};
-    if (ctx->terrain.present) a.g = ctx->terrain.view(ctx->knob);
-    const double *tab = ctx->fan_tab.as<const double>();
-    a.ca = tab;
-    a.sa = tab + fan->n_az;
-    a.ce = tab + 2 * fan->n_az;
-    a.se = tab + 2 * fan->n_az + fan->n_el;
-    a.pose = ctx->poses_d.as<const double>();
-    a.steps = ctx->steps_d.as<const double>();
-    a.n_az = fan->n_az;
+    a.q = scan_hit_query(ctx, fan);
     a.rays = s.rays;
     a.waves = s.waves;
     a.P = s.P;
-    a.r2 = (float)(kRayRadius * kRayRadius);
     a.first_hit = o.fh_d;
     a.wbase = wbase;
     a.offsets = offsets;
