@@ -12,7 +12,8 @@
  *     sin(t - m) = (y cos m - x sin m) / |(x, y)|
  * with cos m and sin m in double-double (Cody-Waite reduction by pi / 2 in three parts, Taylor
  * series to t^31 for |t| <= pi / 4), so the sign is decided unless t lies within ~2^-100 of a
- * midpoint.  Zeros, infinities, NaNs and |r| < 2^-900 return r unchanged.
+ * midpoint.  Infinities, NaNs, r == 0 and |r| < 2^-900 return r unchanged; a zero y or x (both
+ * finite) returns the IEEE special value itself, not r.
  * The scoring's acos and sin (evaluateCellScore, virtual_lidar.cpp:689-700) the same way
  * (round 6): pcp_cr_acos_fix(d, r) from ocml's acos, pcp_cr_sin(a) from the double-double sin.
  * Measured per cell (tests/test_gpu_parity.py::test_parity_bar_per_cell, 91-candidate tick):
@@ -169,8 +170,12 @@ PCP_CR int pcp_cr_side(double y, double x, pcp_dd m) {
  * they point to, up to PCP_CR_ATAN2_STEPS doubles away, all from the one sin / cos at r */
 #define PCP_CR_ATAN2_STEPS 4
 PCP_CR double pcp_cr_atan2_fix(double y, double x, double r) {
-    if (!(isfinite(y) && isfinite(x) && isfinite(r)) || y == 0.0 || x == 0.0 || r == 0.0)
-        return r;
+    if (!(isfinite(y) && isfinite(x) && isfinite(r))) return r;
+    /* an argument zero (an odd lattice over a symmetric box has dy == 0 or dx == 0): the IEEE
+     * special values, +-0, +-pi, +-pi / 2 as doubles, whatever the first result */
+    if (y == 0.0) return signbit(x) ? copysign(0x1.921fb54442d18p+1, y) : y;
+    if (x == 0.0) return copysign(0x1.921fb54442d18p+0, y);
+    if (r == 0.0) return r;
     /* angles near the underflow range (|y / x| < 2^-900): the double-double terms underflow */
     if (fabs(r) < 0x1p-900) return r;
     /* the angle does not change under a common power of two: the larger of |y|, |x| to [1, 2), so

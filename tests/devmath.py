@@ -119,7 +119,8 @@ def sin_family(n=N):
 
 def atan2_families(n=N):
     """(y, x): metre-scale pairs in +-60, ratios 2^+-40, arbitrary finite bit patterns (those
-    whose angle is below 2^-900 lie outside the fix's domain and are left out)."""
+    whose angle is below 2^-900 lie outside the fix's domain and are left out), none with a zero
+    argument; and `axes`, every pair with one."""
     g = np.random.default_rng(0xA7A2)
     fam = {"metres": (g.uniform(-60.0, 60.0, n), g.uniform(-60.0, 60.0, n)),
            "ratios": (g.uniform(-1.0, 1.0, n) * np.exp2(g.integers(-40, 40, n)),
@@ -130,7 +131,16 @@ def atan2_families(n=N):
     with np.errstate(all="ignore"):
         keep = np.abs(np.arctan2(y, x)) >= 2.0 ** -890
     fam["bits"] = (y[keep], x[keep])
-    return {k: (y[(y != 0) & (x != 0)], x[(y != 0) & (x != 0)]) for k, (y, x) in fam.items()}
+    fam = {k: (y[(y != 0) & (x != 0)], x[(y != 0) & (x != 0)]) for k, (y, x) in fam.items()}
+    # the axes: y or x = +-0 with the other finite and non-zero, in both signs (an odd candidate
+    # lattice over a symmetric box produces them); the exact value is the IEEE special value
+    m = min(n, 256)
+    a = np.concatenate([g.uniform(-60.0, 60.0, m), g.uniform(-1.0, 1.0, m) *
+                        np.exp2(g.integers(-1000, 1000, m))])
+    a = a[a != 0.0]
+    z = np.where(g.integers(0, 2, a.size) == 0, 0.0, -0.0)
+    fam["axes"] = (np.concatenate([z, a]), np.concatenate([a, z]))
+    return fam
 
 
 def hard_cases():

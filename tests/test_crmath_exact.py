@@ -12,7 +12,8 @@ uniform d from the exact first result (9 of 98,304 over the three first results,
 9 of 32,768 in (2^-20, 0.01) and (0.99, 1), and 2,092 of the 4,096 composite hard cases; glibc
 2.35 differs from the exact value on 89 of 32,768 uniform composites (acos and sin together),
 39 of 32,768 acos and 39 of 32,768 sin arguments, 33 / 3 / 0 of the metre-scale / ratio /
-bit-pattern atan2 pairs.  The census found pcp_cr_atan2_fix wrong for 9 of 90,309 bit-pattern
+bit-pattern atan2 pairs, 0 of the 1,024 axis pairs (one argument +-0: pcp_cr_atan2_fix returns the
+IEEE special value whatever the first result).  The census found pcp_cr_atan2_fix wrong for 9 of 90,309 bit-pattern
 pairs (a y next to the subnormal range: the products' low words underflowed), since fixed by
 scaling both arguments by a common power of two.
 

@@ -10,7 +10,8 @@ the production kernels call, compiled by hipcc for gfx950), against
   * the oracle's exported eigen33 / normal_from_cov on constructed covariances.
 
 Measured on an MI355X (ROCm 7.2), printed by each run:
-  * composite and candidate atan2: 0 mismatches, 0 undecided (53,258 d; 30,728 pairs);
+  * composite and candidate atan2: 0 mismatches, 0 undecided (53,258 d; 31,752 pairs, 1,024
+    of them with one argument +-0: ocml's raw results there are the IEEE special values);
   * ocml acos: worst 0.68 ulps of the true value, 6.5 % of the raw results not the correctly
     rounded double (28 % of the hard cases);
   * ocml atan2: worst 1.45 ulps of the true angle (metre-scale pairs; 1.27 at ratios 2^+-40),
@@ -59,7 +60,7 @@ def composite_inputs(hard):
 
 def atan2_inputs(hard):
     """(y, x) of the candidate generator's angles: metre-scale pairs in +-60 (all quadrants),
-    ratios 2^+-40, a level sensor's |dz| << hd, the hard cases."""
+    ratios 2^+-40, a level sensor's |dz| << hd, the axes (one argument +-0), the hard cases."""
     f = devmath.atan2_families(N)
     g = np.random.default_rng(0x1E7E1)
     n = N // 4
@@ -68,7 +69,8 @@ def atan2_inputs(hard):
     quad = (np.array([3.0, 3.0, -3.0, -3.0, 1e-9, -1e-9, 60.0, -60.0]),
             np.array([4.0, -4.0, 4.0, -4.0, -7.0, -7.0, 1e-9, -1e-9]))
     return {"metres": f["metres"], "ratios": (f["ratios"][0][:N // 2], f["ratios"][1][:N // 2]),
-            "level": level, "quadrants": quad, "hard": (hard["atan2_y"], hard["atan2_x"])}
+            "level": level, "quadrants": quad, "axes": f["axes"],
+            "hard": (hard["atan2_y"], hard["atan2_x"])}
 
 
 def _first_results(name, raw, exact, fixed, args, strict):
