@@ -847,6 +847,75 @@ int pcp_place_coverage_mounted_burst(pcp_ctx *ctx, const double *poses6, uint64_
                                      const pcp_cover_params *cp, const uint8_t *roi,
                                      uint64_t roi_n, int reps, double ms[3]);
 
+/* The exact best pair of mobile sensors by the terrain their scans reach: every pair of the poses
+ * evaluated on the device (greedy's two need not be the best two, and the
+ * best pair need not hold the best single pose).  N, seen(p), R, the separation expression and the
+ * first-maximum rule (strict '>', the lowest index wins) are pcp_place_coverage's; pp is
+ * pcp_place_pair's struct.
+ *   1. need0 = R minus the points of seen(fixed[i]), i = 0 .. n_fixed-1 in list order; those
+ *      points get owner i.  *base_covered = |R| - |need0|: pcp_place_coverage's step 1 values for
+ *      the same arguments.
+ *   2. A pose is admissible unless it is fixed or (min_separation > 0) closer than the
+ *      separation to a fixed pose.
+ *   3. g[p] = |seen(p) & need0|; single_gains[p] = g[p] for the admissible p, -1 for the others;
+ *      *best_single = the first maximum over the admissible poses, -1 when there is none;
+ *      *single_gain its g (0 without one).
+ *   4. For a < b, both admissible and (min_separation > 0) not closer to each other than it:
+ *      u[a][b] = |(seen(a) | seen(b)) & need0|; pair_gains [n][n] holds u[a][b], every other entry
+ *      -1 (the diagonal, the lower triangle, inadmissible pairs); best_pair = the first maximum in
+ *      row-major order (a ascending, then b), (-1, -1) when there is no admissible pair;
+ *      *pair_gain its u (0 without one).  partner_gain[a] = the first maximum of row a over
+ *      b > a and partner[a] = that b, both -1 where row a holds no pair.
+ *   5. *n_selected = 2 when a pair exists and *pair_gain > *single_gain; otherwise 1 when a single
+ *      exists and *single_gain > 0; otherwise 0.  point_owner describes that answer: the base's
+ *      owners, then the chosen pose, or a and then b, folded in that order with owners n_fixed and
+ *      n_fixed + 1; PCP_OWNER_NONE for the points of R nobody reaches and for every point
+ *      outside R.
+ *   6. seen_points, *n_points and *roi_points as pcp_place_coverage's.
+ * PCP_E_INVALID before any launch, nothing written: what pcp_place_coverage refuses less k_max
+ * (n > PCP_COVER_MAX_POSES included), pp->reserved != 0.  PCP_E_CAPACITY before any launch when
+ * point_owner is given with owner_cap < N: *n_points = N is set and nothing else is written.
+ * n == 0 or N == 0: PCP_OK, *n_selected = 0, the indices -1 and the gains 0, *base_covered = 0,
+ * *roi_points as defined, the tables -1.
+ * One host synchronisation per call; deterministic (identical bytes from call to call); counts are
+ * integers (32-bit accumulators on the device: N < 2^32).  The caller's GridCell flags and the
+ * other queries' device buffers, pcp_place_coverage's included, are not touched (the call's
+ * scratch is its own).  The fan launch is timed under PCP_K_RAYCAST_FAN, the pair phase (mask,
+ * tiles, selection) under PCP_K_PLACE. */
+int pcp_place_coverage_pair(pcp_ctx *ctx, const double *poses5, uint64_t n,
+                            const pcp_fan_params *fan, const pcp_pair_params *pp,
+                            const uint8_t *roi, uint64_t roi_n,       /* nullable; [N], non-zero = counts */
+                            int64_t best_pair[2], uint64_t *pair_gain,
+                            int64_t *best_single, uint64_t *single_gain,
+                            int64_t *single_gains,                    /* nullable [n], -1: not admissible */
+                            int64_t *pair_gains,                      /* nullable [n][n] */
+                            int64_t *partner, int64_t *partner_gain,  /* nullable [n] each */
+                            uint32_t *seen_points,                    /* nullable [n] */
+                            int32_t *point_owner, uint64_t owner_cap, /* nullable [N] */
+                            uint64_t *n_points, uint64_t *roi_points, uint64_t *base_covered,
+                            int32_t *n_selected);
+int pcp_place_coverage_pair_mounted(pcp_ctx *ctx, const double *poses6, uint64_t n,
+                                    const pcp_fan_params *fan, const double *el_table,
+                                    const pcp_pair_params *pp, const uint8_t *roi, uint64_t roi_n,
+                                    int64_t best_pair[2], uint64_t *pair_gain,
+                                    int64_t *best_single, uint64_t *single_gain,
+                                    int64_t *single_gains, int64_t *pair_gains, int64_t *partner,
+                                    int64_t *partner_gain, uint32_t *seen_points,
+                                    int32_t *point_owner, uint64_t owner_cap, uint64_t *n_points,
+                                    uint64_t *roi_points, uint64_t *base_covered,
+                                    int32_t *n_selected);
+/* Kernel timing of pcp_place_coverage_pair (the timing tool only): the query's fan, bitsets and
+ * fixed sensors once, then ms[0] = the mask pass with the singles per repetition, ms[1] = the pair
+ * tiles and the selection (no dense table, nothing committed) per repetition; `reps` repetitions
+ * between two events each.  n >= 1, a terrain index present. */
+int pcp_place_coverage_pair_burst(pcp_ctx *ctx, const double *poses5, uint64_t n,
+                                  const pcp_fan_params *fan, const pcp_pair_params *pp,
+                                  const uint8_t *roi, uint64_t roi_n, int reps, double ms[2]);
+int pcp_place_coverage_pair_mounted_burst(pcp_ctx *ctx, const double *poses6, uint64_t n,
+                                          const pcp_fan_params *fan, const double *el_table,
+                                          const pcp_pair_params *pp, const uint8_t *roi,
+                                          uint64_t roi_n, int reps, double ms[2]);
+
 /* Diagnostic build with s_memtime stamps (shader clock) per wave: stamps[(p*W + w)*4 + i],
  * W = ceil(n_az*n_el/64), i = 0 start, 1 after direction setup, 2 after the march, 3 end.
  * For locating where wave lifetime goes; never used for timing. */

@@ -310,6 +310,26 @@ _SIGS = [
     ("pcp_place_coverage_mounted_burst", C.c_int, [_P, _P, C.c_uint64, C.POINTER(FanParams), _P,
                                                    C.POINTER(CoverParams), _P, C.c_uint64,
                                                    C.c_int, _P]),
+    ("pcp_place_coverage_pair", C.c_int, [_P, _P, C.c_uint64, C.POINTER(FanParams),
+                                          C.POINTER(PairParams), _P, C.c_uint64, _P,
+                                          C.POINTER(C.c_uint64), C.POINTER(C.c_int64),
+                                          C.POINTER(C.c_uint64), _P, _P, _P, _P, _P, _P,
+                                          C.c_uint64, C.POINTER(C.c_uint64),
+                                          C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                          C.POINTER(C.c_int32)]),
+    ("pcp_place_coverage_pair_mounted", C.c_int, [_P, _P, C.c_uint64, C.POINTER(FanParams), _P,
+                                                  C.POINTER(PairParams), _P, C.c_uint64, _P,
+                                                  C.POINTER(C.c_uint64), C.POINTER(C.c_int64),
+                                                  C.POINTER(C.c_uint64), _P, _P, _P, _P, _P, _P,
+                                                  C.c_uint64, C.POINTER(C.c_uint64),
+                                                  C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                                  C.POINTER(C.c_int32)]),
+    ("pcp_place_coverage_pair_burst", C.c_int, [_P, _P, C.c_uint64, C.POINTER(FanParams),
+                                                C.POINTER(PairParams), _P, C.c_uint64, C.c_int,
+                                                _P]),
+    ("pcp_place_coverage_pair_mounted_burst", C.c_int, [_P, _P, C.c_uint64, C.POINTER(FanParams),
+                                                        _P, C.POINTER(PairParams), _P,
+                                                        C.c_uint64, C.c_int, _P]),
     ("pcp_debug_exclusive_scan", C.c_int, [_P, _P, C.c_uint64, _P]),
     ("pcp_debug_math", C.c_int, [_P, C.c_int, _P, _P, C.c_uint64, _P, _P]),
     ("pcp_debug_fine_copy", C.c_int, [_P, C.POINTER(FineGeo), _P, C.c_uint64, _P, C.c_uint64, _P,
@@ -1591,6 +1611,85 @@ class Context:
         """pcp_place_coverage_mounted_burst -> place_coverage_burst's triple."""
         return self.place_coverage_burst(poses6, fan, k_max, min_separation, fixed, roi, reps,
                                          _mounted=(self._el_table(fan, el_table),))
+
+    def place_coverage_pair(self, poses5, fan: FanParams, min_separation: float = 0.0, fixed=(),
+                            roi=None, want_pair_gains: bool = False, want_owner: bool = False,
+                            reserved: int = 0, owner_cap: int | None = None,
+                            _mounted=None) -> dict:
+        """pcp_place_coverage_pair: the exact best pair of the poses by the terrain points of the
+        region `roi` their scans reach beside the `fixed` poses (every admissible pair a < b
+        evaluated; the first maximum in row-major order), with the best single pose for comparison.
+        -> dict: n_selected (2: the pair beats the single, 1: only the single adds, 0), best_pair
+        (2,), pair_gain, best_single, single_gain, single_gains / partner / partner_gain int64 [P]
+        (-1: not admissible / no pair in the row), n_points, roi_points, base_covered, seen_points
+        [P], pair_gains int64 [P, P] (want_pair_gains, else None; -1 off the admissible upper
+        triangle), point_owner int32 [n_points] of the answer (want_owner, else None)."""
+        # (_mounted: place_coverage_pair_mounted's (el_table,), the same call on poses6 rows)
+        poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 6 if _mounted else 5)
+        what = "pcp_place_coverage_pair_mounted" if _mounted else "pcp_place_coverage_pair"
+        fn = getattr(self.lib, what)
+        lead = (_ptr(_mounted[0]),) if _mounted else ()
+        P = poses.shape[0]
+        pp = self._pair_params(fixed, min_separation, reserved)
+        r8, rn = self._roi(roi)
+        bp = np.full(2, -1, np.int64)
+        pg, sgn = C.c_uint64(), C.c_uint64()
+        bs = C.c_int64(-1)
+        sg = np.full(max(P, 1), -1, np.int64)
+        partner = np.full(max(P, 1), -1, np.int64)
+        pgain = np.full(max(P, 1), -1, np.int64)
+        dense = want_pair_gains and P <= COVER_MAX_POSES   # (a refused call writes nothing)
+        tab = np.full((max(P, 1), max(P, 1)), -1, np.int64) if dense else None
+        seen = np.zeros(max(P, 1), np.uint32)
+        ocap = 0
+        if want_owner:
+            ocap = self.scan_points() if owner_cap is None else int(owner_cap)
+        own = np.zeros(max(ocap, 1), np.int32) if want_owner else None
+        npts, rpts, base = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        ns = C.c_int32()
+        self._check(fn(self.h, _ptr(poses) if P else None, P, C.byref(fan), *lead, C.byref(pp),
+                       _ptr(r8), rn, _ptr(bp), C.byref(pg), C.byref(bs), C.byref(sgn), _ptr(sg),
+                       _ptr(tab), _ptr(partner), _ptr(pgain), _ptr(seen), _ptr(own), ocap,
+                       C.byref(npts), C.byref(rpts), C.byref(base), C.byref(ns)), what)
+        return {"n_selected": ns.value, "best_pair": bp, "pair_gain": pg.value,
+                "best_single": bs.value, "single_gain": sgn.value, "single_gains": sg[:P],
+                "partner": partner[:P], "partner_gain": pgain[:P], "n_points": npts.value,
+                "roi_points": rpts.value, "base_covered": base.value, "seen_points": seen[:P],
+                "pair_gains": tab[:P, :P] if want_pair_gains and dense else None,
+                "point_owner": own[:npts.value] if want_owner else None}
+
+    def place_coverage_pair_mounted(self, poses6, fan: FanParams, el_table=None,
+                                    min_separation: float = 0.0, fixed=(), roi=None,
+                                    want_pair_gains: bool = False, want_owner: bool = False,
+                                    reserved: int = 0) -> dict:
+        """pcp_place_coverage_pair_mounted: place_coverage_pair over tilted mounts -- poses6 rows
+        x, y, z, roll, pitch, yaw -- with an optional beam table el_table [n_el] in radians."""
+        return self.place_coverage_pair(poses6, fan, min_separation, fixed, roi, want_pair_gains,
+                                        want_owner, reserved,
+                                        _mounted=(self._el_table(fan, el_table),))
+
+    def place_coverage_pair_burst(self, poses5, fan: FanParams, min_separation: float = 0.0,
+                                  fixed=(), roi=None, reps: int = 20, _mounted=None):
+        """pcp_place_coverage_pair_burst -> (mask pass with the singles, pair tiles with the
+        selection), ms per repetition each."""
+        poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 6 if _mounted else 5)
+        what = ("pcp_place_coverage_pair_mounted_burst" if _mounted
+                else "pcp_place_coverage_pair_burst")
+        lead = (_ptr(_mounted[0]),) if _mounted else ()
+        pp = self._pair_params(fixed, min_separation, 0)
+        r8, rn = self._roi(roi)
+        ms = np.zeros(2, np.float64)
+        self._check(getattr(self.lib, what)(self.h, _ptr(poses), poses.shape[0], C.byref(fan),
+                                            *lead, C.byref(pp), _ptr(r8), rn, reps, _ptr(ms)),
+                    what)
+        return float(ms[0]), float(ms[1])
+
+    def place_coverage_pair_mounted_burst(self, poses6, fan: FanParams, el_table=None,
+                                          min_separation: float = 0.0, fixed=(), roi=None,
+                                          reps: int = 20):
+        """pcp_place_coverage_pair_mounted_burst -> place_coverage_pair_burst's pair."""
+        return self.place_coverage_pair_burst(poses6, fan, min_separation, fixed, roi, reps,
+                                              _mounted=(self._el_table(fan, el_table),))
 
     def score_poses_stats(self, poses5, zx120_pose5, params: VlParams) -> dict:
         """pcp_score_poses_stats: the gather lane-loads of the query's visibility rays

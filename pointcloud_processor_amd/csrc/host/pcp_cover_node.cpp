@@ -65,6 +65,18 @@ std::string coverage_log(const CoveragePlacement::Result &r) {
              (unsigned long long)r.roi_points, q.coverage_ratio * 100.0);
         covered = q.covered;
     }
+    if (r.pair_searched) {   // the exact search: the best pair beside the best single candidate
+        line(s, "%s", thin);
+        if (r.best_pair[0] >= 0)
+            line(s, "Best pair: candidates (%lld, %lld) gain %llu points; best single: candidate "
+                 "%lld gains %llu (%s)", (long long)r.best_pair[0], (long long)r.best_pair[1],
+                 (unsigned long long)r.pair_gain, (long long)r.best_single,
+                 (unsigned long long)r.single_gain,
+                 r.pair_gain > r.single_gain ? "the pair adds more" : "the pair adds no more");
+        else
+            line(s, "Best pair: none admissible; best single: candidate %lld gains %llu",
+                 (long long)r.best_single, (unsigned long long)r.single_gain);
+    }
     line(s, "%s", thin);
     line(s, "Blind spots: %llu of %llu (%.1f%%)", (unsigned long long)(r.roi_points - covered),
          (unsigned long long)r.roi_points, pct(r.roi_points - covered, r.roi_points));
@@ -109,43 +121,77 @@ CoveragePlacement::Result CoveragePlacement::place_mounted(
     return r;
 }
 
-CoveragePlacement::Result CoveragePlacement::run(Device &dev, const PointCloud2 &terrain,
-                                                 const std::vector<double> &poses, size_t n,
-                                                 bool mounted, const VirtualScan::Params &fp,
-                                                 const std::vector<int64_t> &fixed,
-                                                 const Roi &roi) {
-    Result r;
+bool CoveragePlacement::region(const PointCloud2 &terrain, size_t n, bool mounted,
+                               const VirtualScan::Params &fp, const std::vector<int64_t> &fixed,
+                               const Roi &roi, std::vector<uint8_t> &box_bytes,
+                               const std::vector<uint8_t> *&bytes) {
     err_.clear();
+    bytes = nullptr;
     if (fp.n_az <= 0 || fp.n_el <= 0 || n > PCP_COVER_MAX_POSES) {
         err_ = "CoveragePlacement: bad fan size or more than PCP_COVER_MAX_POSES candidates";
-        return r;
+        return false;
     }
     if (fixed.size() > PCP_PLACE_MAX) {
         err_ = "CoveragePlacement: more than PCP_PLACE_MAX fixed candidates";
-        return r;
+        return false;
     }
     const bool table = mounted && !fp.el_table.empty();
     if (table && fp.el_table.size() != (size_t)fp.n_el) {
         err_ = "CoveragePlacement: el_table does not hold n_el entries";
-        return r;
+        return false;
     }
-    const size_t np = terrain.size();
-    std::vector<uint8_t> box_bytes;
-    const std::vector<uint8_t> *bytes = nullptr;
     if (roi.kind == Roi::Bytes) {
         bytes = &roi.bytes;
     } else if (roi.kind == Roi::InBox) {
         std::string why;
         if (!coverage_roi_bytes(terrain, roi.box, box_bytes, &why)) {
             err_ = "CoveragePlacement: " + why;
-            return r;
+            return false;
         }
         bytes = &box_bytes;
     }
-    if (bytes && bytes->size() != np) {
+    if (bytes && bytes->size() != terrain.size()) {
         err_ = "CoveragePlacement: the region does not hold one byte per terrain point";
-        return r;
+        return false;
     }
+    return true;
+}
+
+// the blind spots: the message's own records of the region with no owner, input order
+void CoveragePlacement::blind_spots(Result &r, const PointCloud2 &terrain,
+                                    const std::vector<uint8_t> *bytes) {
+    const size_t np = terrain.size();
+    PointCloud2 &b = r.blind_spots;
+    b.frame_id = terrain.frame_id;
+    b.stamp = terrain.stamp;
+    b.fields = terrain.fields;
+    b.is_bigendian = terrain.is_bigendian;
+    b.point_step = terrain.point_step;
+    b.is_dense = terrain.is_dense;
+    const size_t step = terrain.point_step;
+    size_t w = 0;
+    for (size_t i = 0; i < np; ++i) {
+        const bool blind = r.point_owner[i] == PCP_OWNER_NONE && (!bytes || (*bytes)[i] != 0);
+        if (!blind || (i + 1) * step > terrain.data.size()) continue;
+        b.data.insert(b.data.end(), terrain.data.begin() + i * step,
+                      terrain.data.begin() + (i + 1) * step);
+        ++w;
+    }
+    b.width = (uint32_t)w;
+    b.row_step = (uint32_t)(w * step);
+}
+
+CoveragePlacement::Result CoveragePlacement::run(Device &dev, const PointCloud2 &terrain,
+                                                 const std::vector<double> &poses, size_t n,
+                                                 bool mounted, const VirtualScan::Params &fp,
+                                                 const std::vector<int64_t> &fixed,
+                                                 const Roi &roi) {
+    Result r;
+    std::vector<uint8_t> box_bytes;
+    const std::vector<uint8_t> *bytes = nullptr;
+    if (!region(terrain, n, mounted, fp, fixed, roi, box_bytes, bytes)) return r;
+    const bool table = mounted && !fp.el_table.empty();
+    const size_t np = terrain.size();
     const pcp_fan_params fan{fp.n_az, fp.n_el, fp.el_min, fp.el_max, fp.max_distance};
     pcp_cover_params cp{};
     cp.k_max = p_.num_mobile_lidars;
@@ -188,25 +234,7 @@ CoveragePlacement::Result CoveragePlacement::run(Device &dev, const PointCloud2 
         q.coverage_ratio = r.roi_points ? (double)cov[i] / (double)r.roi_points : 0.0;
         r.rounds.push_back(q);
     }
-    // the blind spots: the message's own records of the region with no owner, input order
-    PointCloud2 &b = r.blind_spots;
-    b.frame_id = terrain.frame_id;
-    b.stamp = terrain.stamp;
-    b.fields = terrain.fields;
-    b.is_bigendian = terrain.is_bigendian;
-    b.point_step = terrain.point_step;
-    b.is_dense = terrain.is_dense;
-    const size_t step = terrain.point_step;
-    size_t w = 0;
-    for (size_t i = 0; i < np; ++i) {
-        const bool blind = r.point_owner[i] == PCP_OWNER_NONE && (!bytes || (*bytes)[i] != 0);
-        if (!blind || (i + 1) * step > terrain.data.size()) continue;
-        b.data.insert(b.data.end(), terrain.data.begin() + i * step,
-                      terrain.data.begin() + (i + 1) * step);
-        ++w;
-    }
-    b.width = (uint32_t)w;
-    b.row_step = (uint32_t)(w * step);
+    blind_spots(r, terrain, bytes);
     r.ran = true;
     return r;
 }

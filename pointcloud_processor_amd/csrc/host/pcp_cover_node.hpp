@@ -1,7 +1,9 @@
 // pcp_cover_node.hpp -- mobile LiDARs placed by the terrain their scans reach, above
 // pcp_place_coverage: the greedy maximum coverage of a region of the terrain message over the
-// simulated scans of the candidates, and the blind spots the answer leaves.  A translation unit of
-// its own: pcp_nodes.cpp and pcp_placement.cpp do not reference it.
+// simulated scans of the candidates, and the blind spots the answer leaves; and above
+// pcp_place_coverage_pair the exact best pair (pcp_cover_pair_node.cpp, a unit of its own so that
+// a program using only the greedy placement links without the pair call).  Translation units of
+// their own: pcp_nodes.cpp and pcp_placement.cpp do not reference them.
 #pragma once
 
 #include <string>
@@ -58,6 +60,12 @@ class CoveragePlacement {
         // message's layout, as VirtualScan's blind spots)
         PointCloud2 blind_spots;
         std::string log;               // a table in the style of placement_log
+        // place_pair() / place_pair_mounted() only (pair_searched set): the exact search's figures
+        bool pair_searched = false;
+        int64_t best_pair[2] = {-1, -1};   // the best admissible pair, (-1, -1) without one
+        uint64_t pair_gain = 0;            // points of the region the pair adds to the fixed ones'
+        int64_t best_single = -1;          // the best admissible single candidate, -1 without one
+        uint64_t single_gain = 0;          // points of the region it adds
     };
     CoveragePlacement() = default;
     explicit CoveragePlacement(const Params &p) : p_(p) {}
@@ -76,6 +84,19 @@ class CoveragePlacement {
                          const std::vector<VirtualScan::SensorPose> &candidates,
                          const VirtualScan::Params &fan, const std::vector<int64_t> &fixed = {},
                          const Roi &roi = Roi());
+    // The exact best pair instead of the greedy rounds (pcp_place_coverage_pair; the parameters'
+    // sensor count is not used): every admissible pair of the candidates evaluated on the device.
+    // The same Result: the rounds are a, then b (or the best single candidate alone where no pair
+    // adds more than it), with the best single and the pair's gain beside them and a log line
+    // comparing the two.  Defined in pcp_cover_pair_node.cpp
+    Result place_pair(Device &dev, const PointCloud2 &terrain,
+                      const std::vector<SimplifiedDualLidarOptimizer::LidarPosition> &candidates,
+                      const VirtualScan::Params &fan, const std::vector<int64_t> &fixed = {},
+                      const Roi &roi = Roi());
+    Result place_pair_mounted(Device &dev, const PointCloud2 &terrain,
+                              const std::vector<VirtualScan::SensorPose> &candidates,
+                              const VirtualScan::Params &fan,
+                              const std::vector<int64_t> &fixed = {}, const Roi &roi = Roi());
     const std::string &lastError() const { return err_; }
 
    private:
@@ -83,6 +104,17 @@ class CoveragePlacement {
     Result run(Device &dev, const PointCloud2 &terrain, const std::vector<double> &poses, size_t n,
                bool mounted, const VirtualScan::Params &fan, const std::vector<int64_t> &fixed,
                const Roi &roi);
+    Result run_pair(Device &dev, const PointCloud2 &terrain, const std::vector<double> &poses,
+                    size_t n, bool mounted, const VirtualScan::Params &fan,
+                    const std::vector<int64_t> &fixed, const Roi &roi);
+    // what both searches refuse before the call (false: err_ says why), and the region as bytes
+    // (bytes null: every point; box_bytes holds a box's)
+    bool region(const PointCloud2 &terrain, size_t n, bool mounted, const VirtualScan::Params &fan,
+                const std::vector<int64_t> &fixed, const Roi &roi, std::vector<uint8_t> &box_bytes,
+                const std::vector<uint8_t> *&bytes);
+    // r.blind_spots from r.point_owner
+    static void blind_spots(Result &r, const PointCloud2 &terrain,
+                            const std::vector<uint8_t> *bytes);
     Params p_;
     std::string err_;
 };
@@ -91,7 +123,8 @@ class CoveragePlacement {
 // outside); false: the message has no such fields (*why says so)
 bool coverage_roi_bytes(const PointCloud2 &terrain, const CoveragePlacement::Box &box,
                         std::vector<uint8_t> &roi, std::string *why = nullptr);
-// the placement's table: host arithmetic only
+// the placement's table: host arithmetic only (after a pair search, with the comparison of the
+// pair and the best single candidate)
 std::string coverage_log(const CoveragePlacement::Result &r);
 
 }  // namespace pcp

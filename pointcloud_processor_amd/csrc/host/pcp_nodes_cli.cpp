@@ -28,6 +28,10 @@
 //                         KMAX sensors placed by the terrain points their scans reach, within the
 //                         region ROI.u8 (TN bytes, non-zero counts; -: every point), beside the
 //                         candidates FIXED (c,c,..); OUT_SELECTED: candidate, gain, covered per round
+//   pcp_nodes_cli cover_pair TERRAIN.f32 TN POSES NAZ NEL MAXD MINSEP ROI.u8|- OUT_SELECTED.i64
+//                         OUT_OWNER.i32 OUT_BLIND.f32 [FIXED]: cover's arguments less KMAX; the
+//                         exact best pair of the candidates (or the best single one where no pair
+//                         adds more), the JSON line with best_pair, pair_gain, best_single, single_gain
 //   pcp_nodes_cli drivable IN.f32 N STEP TF(7) R1(2) R2(2) OUT.i8
 //   pcp_nodes_cli replay  TERRAIN.f32 TN CELLS.f64 NORMALS.f32 CN BBOX(6) FRAMES POINTS
 //
@@ -463,8 +467,11 @@ static int cmd_scan(Device &dev, char **a, bool mounted = false) {
 }
 
 // the coverage placement of the given candidate poses against a terrain: the rounds' records, the
-// per-point owners and the blind-spot records of the region
-static int cmd_cover(Device &dev, char **a, int argc) {
+// per-point owners and the blind-spot records of the region.  pair: the exact pair search
+// (cover_pair: cover's arguments less KMAX, the JSON line with the search's figures)
+static int cover_front(Device &dev, char **a, int argc, bool pair) {
+    const char *cmd = pair ? "cover_pair" : "cover";
+    const int k = pair ? 0 : 1;   // the arguments behind MAXD: [KMAX] MINSEP ROI OUT x 3 [FIXED]
     const auto t = read_file(a[0]);
     const size_t tn = std::strtoull(a[1], nullptr, 10);
     std::vector<double> pv;
@@ -478,7 +485,7 @@ static int cmd_cover(Device &dev, char **a, int argc) {
         pv = tuple(a[2]);
     }
     if (pv.size() % 5 != 0) {
-        std::fprintf(stderr, "cover: POSES holds %zu numbers, not 5 per candidate\n", pv.size());
+        std::fprintf(stderr, "%s: POSES holds %zu numbers, not 5 per candidate\n", cmd, pv.size());
         return 2;
     }
     VirtualScan::Params sp;
@@ -486,27 +493,27 @@ static int cmd_cover(Device &dev, char **a, int argc) {
     sp.n_el = std::atoi(a[4]);
     sp.max_distance = std::strtod(a[5], nullptr);
     CoveragePlacement::Params cp;
-    cp.num_mobile_lidars = std::atoi(a[6]);
-    cp.min_separation = std::strtod(a[7], nullptr);
+    if (!pair) cp.num_mobile_lidars = std::atoi(a[6]);
+    cp.min_separation = std::strtod(a[6 + k], nullptr);
     CoveragePlacement::Roi roi;
-    if (std::strcmp(a[8], "-") != 0) {
-        roi = CoveragePlacement::Roi(read_file(a[8]));
+    if (std::strcmp(a[7 + k], "-") != 0) {
+        roi = CoveragePlacement::Roi(read_file(a[7 + k]));
         if (roi.bytes.size() != tn) {
-            std::fprintf(stderr, "cover: ROI holds %zu bytes, not TN\n", roi.bytes.size());
+            std::fprintf(stderr, "%s: ROI holds %zu bytes, not TN\n", cmd, roi.bytes.size());
             return 2;
         }
     }
     std::vector<int64_t> fixed;
-    if (argc > 12)
-        for (double f : tuple(a[12])) {
+    if (argc > 11 + k)
+        for (double f : tuple(a[11 + k])) {
             if (f != (double)(int64_t)f || f < 0 || f >= (double)(pv.size() / 5)) {
-                std::fprintf(stderr, "cover: FIXED entry %g is no candidate\n", f);
+                std::fprintf(stderr, "%s: FIXED entry %g is no candidate\n", cmd, f);
                 return 2;
             }
             fixed.push_back((int64_t)f);
         }
     if (fixed.size() > PCP_PLACE_MAX) {
-        std::fprintf(stderr, "cover: more than %d FIXED candidates\n", PCP_PLACE_MAX);
+        std::fprintf(stderr, "%s: more than %d FIXED candidates\n", cmd, PCP_PLACE_MAX);
         return 2;
     }
     SimplifiedDualLidarOptimizer node(dev, SimplifiedDualLidarOptimizer::Params{});
@@ -521,9 +528,10 @@ static int cmd_cover(Device &dev, char **a, int argc) {
         cand[i].yaw = pv[5 * i + 4];
     }
     CoveragePlacement place(cp);
-    const auto r = place.place(dev, terrain, cand, sp, fixed, roi);
+    const auto r = pair ? place.place_pair(dev, terrain, cand, sp, fixed, roi)
+                        : place.place(dev, terrain, cand, sp, fixed, roi);
     if (!r.ran) {
-        std::fprintf(stderr, "cover: %s\n", place.lastError().c_str());
+        std::fprintf(stderr, "%s: %s\n", cmd, place.lastError().c_str());
         return 1;
     }
     std::vector<int64_t> rec;
@@ -532,18 +540,35 @@ static int cmd_cover(Device &dev, char **a, int argc) {
         rec.push_back((int64_t)q.gain);
         rec.push_back((int64_t)q.covered);
     }
-    write_file(a[9], rec.data(), rec.size() * 8);
-    write_file(a[10], r.point_owner.data(), r.point_owner.size() * 4);
-    write_file(a[11], r.blind_spots.data.data(), r.blind_spots.data.size());
+    write_file(a[8 + k], rec.data(), rec.size() * 8);
+    write_file(a[9 + k], r.point_owner.data(), r.point_owner.size() * 4);
+    write_file(a[10 + k], r.blind_spots.data.data(), r.blind_spots.data.size());
     std::fputs(r.log.c_str(), stderr);
+    const unsigned long long covered =
+        (unsigned long long)(r.rounds.empty() ? r.base_covered : r.rounds.back().covered);
+    if (pair) {
+        std::printf("{\"n_candidates\": %zu, \"n_selected\": %zu, \"n_points\": %llu, "
+                    "\"roi_points\": %llu, \"base_covered\": %llu, \"covered\": %llu, "
+                    "\"n_blind\": %u, \"best_pair\": [%lld, %lld], \"pair_gain\": %llu, "
+                    "\"best_single\": %lld, \"single_gain\": %llu}\n",
+                    cand.size(), r.rounds.size(), (unsigned long long)r.n_points,
+                    (unsigned long long)r.roi_points, (unsigned long long)r.base_covered, covered,
+                    r.blind_spots.width, (long long)r.best_pair[0], (long long)r.best_pair[1],
+                    (unsigned long long)r.pair_gain, (long long)r.best_single,
+                    (unsigned long long)r.single_gain);
+        return 0;
+    }
     std::printf("{\"n_candidates\": %zu, \"n_selected\": %zu, \"n_points\": %llu, "
                 "\"roi_points\": %llu, \"base_covered\": %llu, \"covered\": %llu, "
                 "\"n_blind\": %u}\n",
                 cand.size(), r.rounds.size(), (unsigned long long)r.n_points,
                 (unsigned long long)r.roi_points, (unsigned long long)r.base_covered,
-                (unsigned long long)(r.rounds.empty() ? r.base_covered : r.rounds.back().covered),
-                r.blind_spots.width);
+                covered, r.blind_spots.width);
     return 0;
+}
+static int cmd_cover(Device &dev, char **a, int argc) { return cover_front(dev, a, argc, false); }
+static int cmd_cover_pair(Device &dev, char **a, int argc) {
+    return cover_front(dev, a, argc, true);
 }
 
 // HDL-64-like scan (64 rings, -24.9..+2 deg) of n points against a ground plane
@@ -914,7 +939,7 @@ int main(int argc, char **argv) {
         if (!hp || std::atoi(hp) != 0) setenv("HSA_ENABLE_INTERRUPT", "0", 0);
     }
     if (argc < 2) {
-        std::fprintf(stderr, "usage: pcp_nodes_cli filter|merge|vlidar|place|place_pair|place_triple|place_refine|place_aimed|scan|scan_mounted|cover|area|drivable|replay ...\n");
+        std::fprintf(stderr, "usage: pcp_nodes_cli filter|merge|vlidar|place|place_pair|place_triple|place_refine|place_aimed|scan|scan_mounted|cover|cover_pair|area|drivable|replay ...\n");
         return 2;
     }
     // name, arguments required after it, the command (a: the arguments, argc: how many)
@@ -935,6 +960,7 @@ int main(int argc, char **argv) {
         {"scan", 10, [](Device &d, char **a, int) { return cmd_scan(d, a); }},
         {"scan_mounted", 11, [](Device &d, char **a, int) { return cmd_scan(d, a, /*mounted=*/true); }},
         {"cover", 12, cmd_cover},
+        {"cover_pair", 11, cmd_cover_pair},
         {"area", 10, [](Device &d, char **a, int) { return cmd_area(d, a); }},
         {"drivable", 7, [](Device &d, char **a, int) { return cmd_drivable(d, a); }},
         {"replay", 8, [](Device &d, char **a, int) { return cmd_replay(d, a); }},

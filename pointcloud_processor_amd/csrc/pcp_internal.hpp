@@ -346,6 +346,12 @@ struct pcp_ctx : pcp::CtxStreams {
     // downloads (its own, as the scan's)
     pcp::DevBuf cover_d;
     pcp::PinnedBuf cover_host;
+    // pcp_place_coverage_pair (pcp_cover_pair.hip): the same block with one row of gains (the
+    // singles), then its result record, partners, the pairs' intersection counts and the dense
+    // table, and the pinned landing of its downloads (its own: cover_d stays as
+    // pcp_place_coverage leaves it)
+    pcp::DevBuf cpair_d;
+    pcp::PinnedBuf cpair_host;
     pcp::PinnedBuf res_host;                 // pinned landing of the filter chain's sizes
     pcp::PinnedBuf fm_res_host;              // pcp_filter_merge's result sizes, stored by its
                                              // kernels themselves (fixed: a graph holds it)
