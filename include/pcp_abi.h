@@ -916,6 +916,79 @@ int pcp_place_coverage_pair_mounted_burst(pcp_ctx *ctx, const double *poses6, ui
                                           const pcp_pair_params *pp, const uint8_t *roi,
                                           uint64_t roi_n, int reps, double ms[2]);
 
+/* A set of mobile sensors improved by single-sensor exchanges, scored by the terrain their scans
+ * reach, wholly on the device (greedy coverage keeps its bound only without
+ * a separation, and a deployment that stands can otherwise only be added to).  N, seen(p), R and
+ * *roi_points are pcp_place_coverage's; the separation expression is pcp_place_sensors' strict
+ * dx^2 + dy^2 < sep^2 on columns 0 and 1 of the pose rows; the first-maximum rule is strict '>',
+ * the lowest index wins; rp is pcp_place_refine's struct, its locked slots in the part of fixed
+ * sensors.  C(s) = |(union over j of seen(s_j)) & R|.
+ *   1. s = start (rp->start[0 .. k-1]); T = C(s) is *start_covered.
+ *   2. One evaluation: for every slot i >= n_locked, L_i = the union of seen(s_j), j != i, and
+ *      u[i][p] = |(L_i | seen(p)) & R|; u[i][p] = -1 where the move is inadmissible: slot i is
+ *      locked (i < n_locked); p is in s (any slot, i included); or, with min_separation > 0, p is
+ *      closer than it to some s_j, j != i.  Only the incoming pose is tested: the start set itself
+ *      need not respect the separation.  swap_covered[e] holds evaluation e's whole [k][n] table.
+ *   3. The best entry is the first maximum in row-major order (slot ascending, then pose).
+ *   4. If it is not > T (or there is none): *converged = 1, stop.  If max_moves moves are recorded
+ *      already: stop with *converged = 0.
+ *   5. Otherwise move m = (move_slot = i, move_from = s_i, move_to = p, move_covered = u[i][p]);
+ *      s_i = p, T = u[i][p]; evaluate again.
+ *   6. There are exactly *n_moves + 1 evaluations; T rises strictly with every move, so the
+ *      procedure ends.  Entries and tables from there on are not written.
+ *   7. selected = s, *covered = T.  slot_unique[i] = the points of R that only slot i of the final
+ *      set reaches.  point_owner[i] = the lowest slot whose scan reaches the point, for the points
+ *      of R; PCP_OWNER_NONE for the points of R nobody reaches and for every point outside R.
+ *      seen_points and *n_points as pcp_place_coverage's.
+ * A set no single move improves is "1-exchange optimal"; it need not be the best set.
+ * PCP_E_INVALID before any launch, nothing written: what pcp_place_coverage refuses about the fan,
+ * the poses, roi_n and null pointers (n > PCP_COVER_MAX_POSES and n * n_az * n_el > 2^31 included);
+ * what pcp_place_refine refuses about rp (k outside 1 .. PCP_PLACE_MAX, n_locked outside 0 .. k,
+ * max_moves outside 0 .. PCP_REFINE_MAX_MOVES, reserved != 0, a start index >= n or listed twice);
+ * a null required pointer (everything not marked nullable; the move arrays may be null when
+ * max_moves == 0); a null context.  PCP_E_CAPACITY before any launch when point_owner is given with
+ * owner_cap < N: *n_points = N is set and nothing else is written.  N == 0: PCP_OK, selected =
+ * start, the counts 0, no moves, *converged = 1; swap_covered and point_owner are not written.
+ * One host synchronisation per call (the moves never visit the host); deterministic (identical
+ * bytes from call to call); counts are integers (32-bit sums on the device: N < 2^32).  The
+ * caller's GridCell flags and the other queries' device buffers, pcp_place_coverage's and
+ * pcp_place_coverage_pair's included, are not touched (the call's scratch is its own).  The fan
+ * launch is timed under PCP_K_RAYCAST_FAN, the evaluations under PCP_K_PLACE. */
+int pcp_place_coverage_refine(pcp_ctx *ctx, const double *poses5, uint64_t n,
+                              const pcp_fan_params *fan, const pcp_refine_params *rp,
+                              const uint8_t *roi, uint64_t roi_n,       /* nullable; [N], non-zero = counts */
+                              int64_t *selected,                        /* [k] the refined set */
+                              uint64_t *covered, uint64_t *start_covered,
+                              int32_t *move_slot, int64_t *move_from, int64_t *move_to, /* [max_moves] */
+                              uint64_t *move_covered,                   /* [max_moves] */
+                              int64_t *swap_covered,                    /* nullable [max_moves + 1][k][n], -1: inadmissible */
+                              uint64_t *slot_unique,                    /* nullable [k] */
+                              uint32_t *seen_points,                    /* nullable [n] */
+                              int32_t *point_owner, uint64_t owner_cap, /* nullable [N] */
+                              uint64_t *n_points, uint64_t *roi_points, int32_t *n_moves,
+                              int32_t *converged);
+int pcp_place_coverage_refine_mounted(pcp_ctx *ctx, const double *poses6, uint64_t n,
+                                      const pcp_fan_params *fan, const double *el_table,
+                                      const pcp_refine_params *rp, const uint8_t *roi,
+                                      uint64_t roi_n, int64_t *selected, uint64_t *covered,
+                                      uint64_t *start_covered, int32_t *move_slot,
+                                      int64_t *move_from, int64_t *move_to, uint64_t *move_covered,
+                                      int64_t *swap_covered, uint64_t *slot_unique,
+                                      uint32_t *seen_points, int32_t *point_owner,
+                                      uint64_t owner_cap, uint64_t *n_points, uint64_t *roi_points,
+                                      int32_t *n_moves, int32_t *converged);
+/* Kernel timing of pcp_place_coverage_refine (the timing tool only): the query's fan and bitsets
+ * once, then ms[0] = the start set's preparation pass (the class rows and their counts) per
+ * repetition, ms[1] = its evaluation launch with the selection, nothing committed, per repetition;
+ * `reps` repetitions between two events each.  n >= 1, a terrain index present. */
+int pcp_place_coverage_refine_burst(pcp_ctx *ctx, const double *poses5, uint64_t n,
+                                    const pcp_fan_params *fan, const pcp_refine_params *rp,
+                                    const uint8_t *roi, uint64_t roi_n, int reps, double ms[2]);
+int pcp_place_coverage_refine_mounted_burst(pcp_ctx *ctx, const double *poses6, uint64_t n,
+                                            const pcp_fan_params *fan, const double *el_table,
+                                            const pcp_refine_params *rp, const uint8_t *roi,
+                                            uint64_t roi_n, int reps, double ms[2]);
+
 /* Diagnostic build with s_memtime stamps (shader clock) per wave: stamps[(p*W + w)*4 + i],
  * W = ceil(n_az*n_el/64), i = 0 start, 1 after direction setup, 2 after the march, 3 end.
  * For locating where wave lifetime goes; never used for timing. */

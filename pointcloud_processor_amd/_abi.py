@@ -330,6 +330,25 @@ _SIGS = [
     ("pcp_place_coverage_pair_mounted_burst", C.c_int, [_P, _P, C.c_uint64, C.POINTER(FanParams),
                                                         _P, C.POINTER(PairParams), _P,
                                                         C.c_uint64, C.c_int, _P]),
+    ("pcp_place_coverage_refine", C.c_int, [_P, _P, C.c_uint64, C.POINTER(FanParams),
+                                            C.POINTER(RefineParams), _P, C.c_uint64, _P,
+                                            C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _P, _P,
+                                            _P, _P, _P, _P, _P, _P, C.c_uint64,
+                                            C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                            C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("pcp_place_coverage_refine_mounted", C.c_int, [_P, _P, C.c_uint64, C.POINTER(FanParams), _P,
+                                                    C.POINTER(RefineParams), _P, C.c_uint64, _P,
+                                                    C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                                    _P, _P, _P, _P, _P, _P, _P, _P, C.c_uint64,
+                                                    C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                                    C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("pcp_place_coverage_refine_burst", C.c_int, [_P, _P, C.c_uint64, C.POINTER(FanParams),
+                                                  C.POINTER(RefineParams), _P, C.c_uint64,
+                                                  C.c_int, _P]),
+    ("pcp_place_coverage_refine_mounted_burst", C.c_int, [_P, _P, C.c_uint64,
+                                                          C.POINTER(FanParams), _P,
+                                                          C.POINTER(RefineParams), _P,
+                                                          C.c_uint64, C.c_int, _P]),
     ("pcp_debug_exclusive_scan", C.c_int, [_P, _P, C.c_uint64, _P]),
     ("pcp_debug_math", C.c_int, [_P, C.c_int, _P, _P, C.c_uint64, _P, _P]),
     ("pcp_debug_fine_copy", C.c_int, [_P, C.POINTER(FineGeo), _P, C.c_uint64, _P, C.c_uint64, _P,
@@ -1690,6 +1709,99 @@ class Context:
         """pcp_place_coverage_pair_mounted_burst -> place_coverage_pair_burst's pair."""
         return self.place_coverage_pair_burst(poses6, fan, min_separation, fixed, roi, reps,
                                               _mounted=(self._el_table(fan, el_table),))
+
+    def place_coverage_refine(self, poses5, fan: FanParams, start, n_locked: int = 0,
+                              max_moves: int = 16, min_separation: float = 0.0, roi=None,
+                              want_swap_covered: bool = False, want_owner: bool = False,
+                              reserved: int = 0, owner_cap: int | None = None,
+                              _mounted=None) -> dict:
+        """pcp_place_coverage_refine: the set `start` of poses improved by single-sensor exchanges
+        over the coverage objective (every unlocked slot tried at every other pose with the rest
+        held; the best exchange taken while it raises the count of terrain points of the region
+        `roi` the set's scans reach).  max_moves + 1 evaluations are enqueued up front and those
+        behind the stop return at once: an empty pair of launches still costs queue time, so a
+        large max_moves is paid for after an early convergence too.
+        -> dict: selected [k], covered, start_covered, n_moves, converged (1: no single move
+        raises the count; 0: max_moves ran out first), move_slot / move_from / move_to /
+        move_covered [n_moves], slot_unique [k] (the points only that slot of the final set
+        reaches), seen_points [P], n_points, roi_points, and on request swap_covered int64
+        [n_moves + 1, k, P] (-1 at inadmissible moves), point_owner int32 [n_points] (the lowest
+        slot that reaches the point; OWNER_NONE: nobody does, or it lies outside the region)."""
+        # (_mounted: place_coverage_refine_mounted's (el_table,), the same call on poses6 rows)
+        poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 6 if _mounted else 5)
+        what = "pcp_place_coverage_refine_mounted" if _mounted else "pcp_place_coverage_refine"
+        fn = getattr(self.lib, what)
+        lead = (_ptr(_mounted[0]),) if _mounted else ()
+        P = poses.shape[0]
+        rp = self._refine_params(start, n_locked, max_moves, min_separation, reserved)
+        r8, rn = self._roi(roi)
+        k = max(min(rp.k, PLACE_MAX), 1)
+        mm = max(min(int(max_moves), REFINE_MAX_MOVES), 0)
+        sel = np.full(k, -1, np.int64)
+        cov, sc = C.c_uint64(), C.c_uint64()
+        m_slot = np.zeros(max(mm, 1), np.int32)
+        m_from = np.zeros(max(mm, 1), np.int64)
+        m_to = np.zeros(max(mm, 1), np.int64)
+        m_cov = np.zeros(max(mm, 1), np.uint64)
+        dense = want_swap_covered and P <= COVER_MAX_POSES   # (a refused call writes nothing)
+        tab = np.full((mm + 1, k, max(P, 1)), -1, np.int64) if dense else None
+        uniq = np.zeros(k, np.uint64)
+        seen = np.zeros(max(P, 1), np.uint32)
+        ocap = 0
+        if want_owner:
+            ocap = self.scan_points() if owner_cap is None else int(owner_cap)
+        own = np.zeros(max(ocap, 1), np.int32) if want_owner else None
+        npts, rpts = C.c_uint64(), C.c_uint64()
+        nm, cv = C.c_int32(), C.c_int32()
+        self._check(fn(self.h, _ptr(poses) if P else None, P, C.byref(fan), *lead, C.byref(rp),
+                       _ptr(r8), rn, _ptr(sel), C.byref(cov), C.byref(sc), _ptr(m_slot),
+                       _ptr(m_from), _ptr(m_to), _ptr(m_cov), _ptr(tab), _ptr(uniq), _ptr(seen),
+                       _ptr(own), ocap, C.byref(npts), C.byref(rpts), C.byref(nm), C.byref(cv)),
+                    what)
+        n = nm.value
+        evals = n + 1 if npts.value else 0   # (without terrain nothing is evaluated: no table)
+        return {"selected": sel, "covered": cov.value, "start_covered": sc.value, "n_moves": n,
+                "converged": cv.value, "move_slot": m_slot[:n].copy(),
+                "move_from": m_from[:n].copy(), "move_to": m_to[:n].copy(),
+                "move_covered": m_cov[:n].copy(), "slot_unique": uniq, "seen_points": seen[:P],
+                "n_points": npts.value, "roi_points": rpts.value,
+                "swap_covered": tab[:evals, :, :P].copy() if dense else None,
+                "point_owner": own[:npts.value] if want_owner else None}
+
+    def place_coverage_refine_mounted(self, poses6, fan: FanParams, start, el_table=None,
+                                      n_locked: int = 0, max_moves: int = 16,
+                                      min_separation: float = 0.0, roi=None,
+                                      want_swap_covered: bool = False, want_owner: bool = False,
+                                      reserved: int = 0) -> dict:
+        """pcp_place_coverage_refine_mounted: place_coverage_refine over tilted mounts -- poses6
+        rows x, y, z, roll, pitch, yaw -- with an optional beam table el_table [n_el] in radians."""
+        return self.place_coverage_refine(poses6, fan, start, n_locked, max_moves, min_separation,
+                                          roi, want_swap_covered, want_owner, reserved,
+                                          _mounted=(self._el_table(fan, el_table),))
+
+    def place_coverage_refine_burst(self, poses5, fan: FanParams, start, n_locked: int = 0,
+                                    min_separation: float = 0.0, roi=None, reps: int = 20,
+                                    _mounted=None):
+        """pcp_place_coverage_refine_burst -> (the start set's preparation pass, its evaluation
+        launch with the selection), ms per repetition each."""
+        poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 6 if _mounted else 5)
+        what = ("pcp_place_coverage_refine_mounted_burst" if _mounted
+                else "pcp_place_coverage_refine_burst")
+        lead = (_ptr(_mounted[0]),) if _mounted else ()
+        rp = self._refine_params(start, n_locked, 0, min_separation, 0)
+        r8, rn = self._roi(roi)
+        ms = np.zeros(2, np.float64)
+        self._check(getattr(self.lib, what)(self.h, _ptr(poses), poses.shape[0], C.byref(fan),
+                                            *lead, C.byref(rp), _ptr(r8), rn, reps, _ptr(ms)),
+                    what)
+        return float(ms[0]), float(ms[1])
+
+    def place_coverage_refine_mounted_burst(self, poses6, fan: FanParams, start, el_table=None,
+                                            n_locked: int = 0, min_separation: float = 0.0,
+                                            roi=None, reps: int = 20):
+        """pcp_place_coverage_refine_mounted_burst -> place_coverage_refine_burst's pair."""
+        return self.place_coverage_refine_burst(poses6, fan, start, n_locked, min_separation, roi,
+                                                reps, _mounted=(self._el_table(fan, el_table),))
 
     def score_poses_stats(self, poses5, zx120_pose5, params: VlParams) -> dict:
         """pcp_score_poses_stats: the gather lane-loads of the query's visibility rays

@@ -77,6 +77,17 @@ std::string coverage_log(const CoveragePlacement::Result &r) {
             line(s, "Best pair: none admissible; best single: candidate %lld gains %llu",
                  (long long)r.best_single, (unsigned long long)r.single_gain);
     }
+    if (r.refined) {   // the exchanges: where the set started, a line per move, how it ended
+        line(s, "%s", thin);
+        line(s, "Exchange refinement (%d locked): start %llu points (%.1f%%)", r.n_locked,
+             (unsigned long long)r.start_covered, pct(r.start_covered, r.roi_points));
+        for (size_t m = 0; m < r.moves.size(); ++m)
+            line(s, "  Move %zu: slot %d, candidate %lld -> %lld, covered %llu (%.1f%%)", m + 1,
+                 r.moves[m].slot, (long long)r.moves[m].from, (long long)r.moves[m].to,
+                 (unsigned long long)r.moves[m].covered, pct(r.moves[m].covered, r.roi_points));
+        line(s, "  %s after %zu move%s", r.converged ? "No single move adds a point" : "Moves ran out",
+             r.moves.size(), r.moves.size() == 1 ? "" : "s");
+    }
     line(s, "%s", thin);
     line(s, "Blind spots: %llu of %llu (%.1f%%)", (unsigned long long)(r.roi_points - covered),
          (unsigned long long)r.roi_points, pct(r.roi_points - covered, r.roi_points));

@@ -1,8 +1,10 @@
 // pcp_cover_node.hpp -- mobile LiDARs placed by the terrain their scans reach, above
 // pcp_place_coverage: the greedy maximum coverage of a region of the terrain message over the
-// simulated scans of the candidates, and the blind spots the answer leaves; and above
+// simulated scans of the candidates, and the blind spots the answer leaves; above
 // pcp_place_coverage_pair the exact best pair (pcp_cover_pair_node.cpp, a unit of its own so that
-// a program using only the greedy placement links without the pair call).  Translation units of
+// a program using only the greedy placement links without the pair call); and above
+// pcp_place_coverage_refine a standing set improved by single-sensor exchanges
+// (pcp_cover_refine_node.cpp, a unit of its own for the same reason).  Translation units of
 // their own: pcp_nodes.cpp and pcp_placement.cpp do not reference them.
 #pragma once
 
@@ -42,6 +44,11 @@ class CoveragePlacement {
         uint64_t covered = 0;          // points of the region reached with sensors 0 .. r placed
         double coverage_ratio = 0;     // covered / points of the region
     };
+    struct Move {                      // one exchange of refine(): slot `slot` went from -> to
+        int32_t slot = -1;
+        int64_t from = -1, to = -1;    // indices into the candidates
+        uint64_t covered = 0;          // points of the region reached after the move
+    };
     struct Result {
         bool ran = false;              // false: the call failed (lastError)
         // the placed sensors in placement order: `placed` after place(), `placed_mounts` after
@@ -66,6 +73,13 @@ class CoveragePlacement {
         uint64_t pair_gain = 0;            // points of the region the pair adds to the fixed ones'
         int64_t best_single = -1;          // the best admissible single candidate, -1 without one
         uint64_t single_gain = 0;          // points of the region it adds
+        // refine() / refine_mounted() only (refined set): the exchanges' record
+        bool refined = false;
+        std::vector<Move> moves;           // in the order they were taken
+        bool converged = false;            // no single move adds a point (false: the moves ran out)
+        uint64_t start_covered = 0;        // points of the region the start set reaches
+        int32_t n_locked = 0;
+        std::vector<uint64_t> slot_unique; // per slot: points of the region only it reaches
     };
     CoveragePlacement() = default;
     explicit CoveragePlacement(const Params &p) : p_(p) {}
@@ -97,6 +111,20 @@ class CoveragePlacement {
                               const std::vector<VirtualScan::SensorPose> &candidates,
                               const VirtualScan::Params &fan,
                               const std::vector<int64_t> &fixed = {}, const Roi &roi = Roi());
+    // A standing set improved by single-sensor exchanges (pcp_place_coverage_refine; the
+    // parameters' sensor count is not used): start = the set as candidate indices, whose first
+    // n_locked slots never move (the part of fixed sensors).  The same Result with the slots in
+    // order as the rounds -- a round's gain = the points its slot reaches first -- the moves, the
+    // blind spots of the refined set and a log line per move.  Defined in
+    // pcp_cover_refine_node.cpp
+    Result refine(Device &dev, const PointCloud2 &terrain,
+                  const std::vector<SimplifiedDualLidarOptimizer::LidarPosition> &candidates,
+                  const VirtualScan::Params &fan, const std::vector<int64_t> &start,
+                  int n_locked = 0, int max_moves = 16, const Roi &roi = Roi());
+    Result refine_mounted(Device &dev, const PointCloud2 &terrain,
+                          const std::vector<VirtualScan::SensorPose> &candidates,
+                          const VirtualScan::Params &fan, const std::vector<int64_t> &start,
+                          int n_locked = 0, int max_moves = 16, const Roi &roi = Roi());
     const std::string &lastError() const { return err_; }
 
    private:
@@ -107,7 +135,11 @@ class CoveragePlacement {
     Result run_pair(Device &dev, const PointCloud2 &terrain, const std::vector<double> &poses,
                     size_t n, bool mounted, const VirtualScan::Params &fan,
                     const std::vector<int64_t> &fixed, const Roi &roi);
-    // what both searches refuse before the call (false: err_ says why), and the region as bytes
+    Result run_refine(Device &dev, const PointCloud2 &terrain, const std::vector<double> &poses,
+                      size_t n, bool mounted, const VirtualScan::Params &fan,
+                      const std::vector<int64_t> &start, int n_locked, int max_moves,
+                      const Roi &roi);
+    // what every search refuses before the call (false: err_ says why), and the region as bytes
     // (bytes null: every point; box_bytes holds a box's)
     bool region(const PointCloud2 &terrain, size_t n, bool mounted, const VirtualScan::Params &fan,
                 const std::vector<int64_t> &fixed, const Roi &roi, std::vector<uint8_t> &box_bytes,
@@ -124,7 +156,7 @@ class CoveragePlacement {
 bool coverage_roi_bytes(const PointCloud2 &terrain, const CoveragePlacement::Box &box,
                         std::vector<uint8_t> &roi, std::string *why = nullptr);
 // the placement's table: host arithmetic only (after a pair search, with the comparison of the
-// pair and the best single candidate)
+// pair and the best single candidate; after a refinement, with a line per move)
 std::string coverage_log(const CoveragePlacement::Result &r);
 
 }  // namespace pcp

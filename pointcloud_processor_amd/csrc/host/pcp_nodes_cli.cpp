@@ -32,6 +32,12 @@
 //                         OUT_OWNER.i32 OUT_BLIND.f32 [FIXED]: cover's arguments less KMAX; the
 //                         exact best pair of the candidates (or the best single one where no pair
 //                         adds more), the JSON line with best_pair, pair_gain, best_single, single_gain
+//   pcp_nodes_cli cover_refine cover's arguments [--start c,c,..] [--locked M] [--max-moves M]:
+//                         the set START improved by single-sensor exchanges, its first LOCKED
+//                         slots held; without --start greedy's answer of `cover` is refined in
+//                         the same process (FIXED in front of it, locked); OUT_SELECTED: candidate,
+//                         owned points, covered per slot; the JSON line adds n_locked,
+//                         start_covered, moves [slot, from, to, covered] and converged
 //   pcp_nodes_cli drivable IN.f32 N STEP TF(7) R1(2) R2(2) OUT.i8
 //   pcp_nodes_cli replay  TERRAIN.f32 TN CELLS.f64 NORMALS.f32 CN BBOX(6) FRAMES POINTS
 //
@@ -468,10 +474,57 @@ static int cmd_scan(Device &dev, char **a, bool mounted = false) {
 
 // the coverage placement of the given candidate poses against a terrain: the rounds' records, the
 // per-point owners and the blind-spot records of the region.  pair: the exact pair search
-// (cover_pair: cover's arguments less KMAX, the JSON line with the search's figures)
-static int cover_front(Device &dev, char **a, int argc, bool pair) {
-    const char *cmd = pair ? "cover_pair" : "cover";
+// (cover_pair: cover's arguments less KMAX, the JSON line with the search's figures); refine: the
+// exchanges from --start or from greedy's answer (cover_refine: the slots in order as the rounds)
+enum class CoverCmd { Greedy, Pair, Refine };
+static int cover_front(Device &dev, char **a, int argc, CoverCmd mode) {
+    const bool pair = mode == CoverCmd::Pair, refine = mode == CoverCmd::Refine;
+    const char *cmd = pair ? "cover_pair" : refine ? "cover_refine" : "cover";
     const int k = pair ? 0 : 1;   // the arguments behind MAXD: [KMAX] MINSEP ROI OUT x 3 [FIXED]
+    // cover_refine's options behind the positional arguments
+    std::vector<int64_t> start;
+    bool have_start = false;
+    int n_locked = -1, max_moves = 16;
+    if (refine) {
+        int pos = argc;
+        for (int i = 12; i < argc; ++i)
+            if (std::strncmp(a[i], "--", 2) == 0) {
+                pos = std::min(pos, i);
+                const std::string opt = a[i];
+                if (i + 1 >= argc || (opt != "--start" && opt != "--locked" && opt != "--max-moves")) {
+                    std::fprintf(stderr, "%s: bad option %s\n", cmd, a[i]);
+                    return 2;
+                }
+                const char *val = a[++i];
+                if (opt == "--start") {
+                    have_start = true;
+                    for (double f : tuple(val)) {
+                        if (f != (double)(int64_t)f) {
+                            std::fprintf(stderr, "%s: --start entry %g is no index\n", cmd, f);
+                            return 2;
+                        }
+                        start.push_back((int64_t)f);
+                    }
+                } else {
+                    char *end = nullptr;
+                    const long v = std::strtol(val, &end, 10);
+                    if (end == val || *end != '\0' || v < 0 || v > PCP_REFINE_MAX_MOVES) {
+                        std::fprintf(stderr, "%s: bad value %s for %s\n", cmd, val, a[i - 1]);
+                        return 2;
+                    }
+                    (opt == "--locked" ? n_locked : max_moves) = (int)v;
+                }
+            } else if (i > 12) {   // (a[12] alone may be FIXED)
+                std::fprintf(stderr, "%s: unexpected argument %s\n", cmd, a[i]);
+                return 2;
+            }
+        argc = std::min(pos, 13);   // (what is left: the positional arguments with FIXED)
+        if (have_start && (argc > 12 || start.empty() || start.size() > PCP_PLACE_MAX)) {
+            std::fprintf(stderr, "%s: --start holds 1 .. %d indices and takes no FIXED\n", cmd,
+                         PCP_PLACE_MAX);
+            return 2;
+        }
+    }
     const auto t = read_file(a[0]);
     const size_t tn = std::strtoull(a[1], nullptr, 10);
     std::vector<double> pv;
@@ -528,8 +581,32 @@ static int cover_front(Device &dev, char **a, int argc, bool pair) {
         cand[i].yaw = pv[5 * i + 4];
     }
     CoveragePlacement place(cp);
-    const auto r = pair ? place.place_pair(dev, terrain, cand, sp, fixed, roi)
-                        : place.place(dev, terrain, cand, sp, fixed, roi);
+    for (int64_t s : start)
+        if (s < 0 || (size_t)s >= cand.size()) {
+            std::fprintf(stderr, "%s: --start entry %lld is no candidate\n", cmd, (long long)s);
+            return 2;
+        }
+    auto r = pair ? place.place_pair(dev, terrain, cand, sp, fixed, roi)
+                  : refine && have_start ? CoveragePlacement::Result()
+                                         : place.place(dev, terrain, cand, sp, fixed, roi);
+    if (refine) {
+        // without a start: greedy's answer, the FIXED candidates in front of it as locked slots
+        if (!have_start) {
+            if (!r.ran) {
+                std::fprintf(stderr, "%s: %s\n", cmd, place.lastError().c_str());
+                return 1;
+            }
+            start = fixed;
+            for (const auto &q : r.rounds) start.push_back(q.candidate);
+            if (start.empty() || start.size() > PCP_PLACE_MAX) {
+                std::fprintf(stderr, "%s: greedy and FIXED give %zu sensors, not 1 .. %d\n", cmd,
+                             start.size(), PCP_PLACE_MAX);
+                return 1;
+            }
+            if (n_locked < 0) n_locked = (int)fixed.size();
+        }
+        r = place.refine(dev, terrain, cand, sp, start, std::max(n_locked, 0), max_moves, roi);
+    }
     if (!r.ran) {
         std::fprintf(stderr, "%s: %s\n", cmd, place.lastError().c_str());
         return 1;
@@ -558,6 +635,25 @@ static int cover_front(Device &dev, char **a, int argc, bool pair) {
                     (unsigned long long)r.single_gain);
         return 0;
     }
+    if (refine) {
+        std::string moves;
+        for (const auto &m : r.moves) {
+            char buf[128];
+            std::snprintf(buf, sizeof(buf), "%s[%d, %lld, %lld, %llu]", moves.empty() ? "" : ", ",
+                          m.slot, (long long)m.from, (long long)m.to,
+                          (unsigned long long)m.covered);
+            moves += buf;
+        }
+        std::printf("{\"n_candidates\": %zu, \"n_selected\": %zu, \"n_points\": %llu, "
+                    "\"roi_points\": %llu, \"base_covered\": %llu, \"covered\": %llu, "
+                    "\"n_blind\": %u, \"n_locked\": %d, \"start_covered\": %llu, "
+                    "\"moves\": [%s], \"converged\": %d}\n",
+                    cand.size(), r.rounds.size(), (unsigned long long)r.n_points,
+                    (unsigned long long)r.roi_points, (unsigned long long)r.base_covered, covered,
+                    r.blind_spots.width, r.n_locked, (unsigned long long)r.start_covered,
+                    moves.c_str(), r.converged ? 1 : 0);
+        return 0;
+    }
     std::printf("{\"n_candidates\": %zu, \"n_selected\": %zu, \"n_points\": %llu, "
                 "\"roi_points\": %llu, \"base_covered\": %llu, \"covered\": %llu, "
                 "\"n_blind\": %u}\n",
@@ -566,9 +662,14 @@ static int cover_front(Device &dev, char **a, int argc, bool pair) {
                 covered, r.blind_spots.width);
     return 0;
 }
-static int cmd_cover(Device &dev, char **a, int argc) { return cover_front(dev, a, argc, false); }
+static int cmd_cover(Device &dev, char **a, int argc) {
+    return cover_front(dev, a, argc, CoverCmd::Greedy);
+}
 static int cmd_cover_pair(Device &dev, char **a, int argc) {
-    return cover_front(dev, a, argc, true);
+    return cover_front(dev, a, argc, CoverCmd::Pair);
+}
+static int cmd_cover_refine(Device &dev, char **a, int argc) {
+    return cover_front(dev, a, argc, CoverCmd::Refine);
 }
 
 // HDL-64-like scan (64 rings, -24.9..+2 deg) of n points against a ground plane
@@ -939,7 +1040,7 @@ int main(int argc, char **argv) {
         if (!hp || std::atoi(hp) != 0) setenv("HSA_ENABLE_INTERRUPT", "0", 0);
     }
     if (argc < 2) {
-        std::fprintf(stderr, "usage: pcp_nodes_cli filter|merge|vlidar|place|place_pair|place_triple|place_refine|place_aimed|scan|scan_mounted|cover|cover_pair|area|drivable|replay ...\n");
+        std::fprintf(stderr, "usage: pcp_nodes_cli filter|merge|vlidar|place|place_pair|place_triple|place_refine|place_aimed|scan|scan_mounted|cover|cover_pair|cover_refine|area|drivable|replay ...\n");
         return 2;
     }
     // name, arguments required after it, the command (a: the arguments, argc: how many)
@@ -961,6 +1062,7 @@ int main(int argc, char **argv) {
         {"scan_mounted", 11, [](Device &d, char **a, int) { return cmd_scan(d, a, /*mounted=*/true); }},
         {"cover", 12, cmd_cover},
         {"cover_pair", 11, cmd_cover_pair},
+        {"cover_refine", 12, cmd_cover_refine},
         {"area", 10, [](Device &d, char **a, int) { return cmd_area(d, a); }},
         {"drivable", 7, [](Device &d, char **a, int) { return cmd_drivable(d, a); }},
         {"replay", 8, [](Device &d, char **a, int) { return cmd_replay(d, a); }},

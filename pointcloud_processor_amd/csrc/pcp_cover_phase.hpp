@@ -2,8 +2,9 @@
 // checks, k_cover_clear, k_cover_need, k_cover_resolve, k_cover_count and k_cover_commit with their
 // enqueue functions, as pcp_cover.hip held them.  pcp_place_coverage (pcp_cover.hip) runs its greedy
 // rounds behind it in ctx->cover_d; pcp_place_coverage_pair (pcp_cover_pair.hip) runs its mask, tile
-// and selection passes behind it in a block of its own.  The unnamed namespace gives each of the
-// two translation units its own copy of the kernels.
+// and selection passes behind it in a block of its own, and pcp_place_coverage_refine
+// (pcp_cover_refine.hip) its preparations and evaluations in a third.  The unnamed
+// namespace gives each of the translation units its own copy of the kernels.
 #pragma once
 
 #include <algorithm>

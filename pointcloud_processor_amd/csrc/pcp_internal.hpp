@@ -352,6 +352,11 @@ struct pcp_ctx : pcp::CtxStreams {
     // pcp_place_coverage leaves it)
     pcp::DevBuf cpair_d;
     pcp::PinnedBuf cpair_host;
+    // pcp_place_coverage_refine (pcp_cover_refine.hip): the same block again, then its state with
+    // the moves, the evaluation's sums, the class rows and the dense tables, and the pinned
+    // landing of its downloads (its own: cover_d and cpair_d stay as their calls leave them)
+    pcp::DevBuf crefine_d;
+    pcp::PinnedBuf crefine_host;
     pcp::PinnedBuf res_host;                 // pinned landing of the filter chain's sizes
     pcp::PinnedBuf fm_res_host;              // pcp_filter_merge's result sizes, stored by its
                                              // kernels themselves (fixed: a graph holds it)
