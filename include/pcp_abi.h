@@ -989,6 +989,92 @@ int pcp_place_coverage_refine_mounted_burst(pcp_ctx *ctx, const double *poses6, 
                                             const pcp_refine_params *rp, const uint8_t *roi,
                                             uint64_t roi_n, int reps, double ms[2]);
 
+/* Greedy coverage placement of sensors with a limited field of view: where to stand and which way
+ * to look, scored by the terrain the scans reach.  Every pose is searched
+ * with every aim of a table; an aim is a window of the pose's own fan, so the fan is marched and
+ * resolved once per pose whatever the aim.  All integers.  N, R, the separation expression and the
+ * strict first-maximum rule are pcp_place_coverage's.
+ *   w_az in 1 .. n_az (columns), w_el in 1 .. n_el (rings); aims[a] = (az0, el0), 0 <= az0 < n_az,
+ *   0 <= el0 <= n_el - w_el.
+ *   Window(a) = {(i, j) : ((i - az0_a) mod n_az) < w_az and el0_a <= j < el0_a + w_el}: azimuth
+ *      wraps, rings do not.  The window is in the sensor's own (i, j): for a tilted mount an aim
+ *      turns the head about its own spin axis.
+ *   seen(p, a) = {hit_point[p][j][i] >= 0 : (i, j) in Window(a)}, hit_point as pcp_simulate_scan
+ *      reports it for the same pose and fan (the mounted twin: pcp_simulate_scan_mounted for the
+ *      same poses6 row and beam table).  A point hit by rays inside and outside a window belongs
+ *      to the window; a point hit by several rays of one window counts once.  seen(p) = the union
+ *      over the whole fan, pcp_place_coverage's.
+ *   1. need = R.  For i = 0 .. n_fixed-1 in list order: the points of seen(fixed_pose[i],
+ *      fixed_aim[i]) in need get owner i and leave need.  *base_covered = |R| - |need|.  A pose is
+ *      alive unless it is fixed or (min_separation > 0) closer than the separation to a fixed pose.
+ *   2. Round r = 0 .. k_max-1: stop when no pose is alive; g[p][a] = |seen(p, a) & need| for every
+ *      aim of every alive pose; round_gains[r] holds the whole [n][n_aims] table, -1 in every row
+ *      of a pose that is not alive; (b, ab) = the first maximum in row-major order (pose ascending,
+ *      then aim); stop unless g[b][ab] > 0.
+ *   3. selected[r] = b, selected_aim[r] = ab, gain[r] = g[b][ab], covered_after[r] = base_covered
+ *      + gain[0] + .. + gain[r]; the points of seen(b, ab) in need get owner n_fixed + r and leave
+ *      need; pose b leaves the search with all its aims and, with min_separation > 0, so does
+ *      every pose closer to b than the separation.
+ *   4. *n_selected, point_owner, seen_points[p] = |seen(p)|, *n_points and *roi_points as
+ *      pcp_place_coverage's.  aim_points[p][a] = |seen(p, a)| over all N points.
+ * PCP_E_INVALID before any launch, nothing written: what pcp_place_coverage refuses; n_aims outside
+ * 1 .. PCP_COVER_AIM_MAX, n * n_aims > PCP_AIM_MAX_ROWS, w_az outside 1 .. n_az, w_el outside 1 ..
+ * n_el, an aim entry out of range, a fixed aim outside the table, a fixed pose >= n or listed
+ * twice, reserved != 0, a null required pointer (everything not marked nullable), a null context.
+ * PCP_E_CAPACITY and the n == 0 / N == 0 cases as pcp_place_coverage's (aim_points then 0).
+ * One host synchronisation per call; deterministic (identical bytes from call to call); the
+ * caller's GridCell flags and the other queries' device buffers, pcp_place_coverage's, the pair's
+ * and the refine's included, are not touched (the call's scratch is its own).  The fan launch is
+ * timed under PCP_K_RAYCAST_FAN, the rounds under PCP_K_PLACE. */
+#define PCP_COVER_AIM_MAX 64      /* aims per call (n * n_aims <= PCP_AIM_MAX_ROWS) */
+typedef struct pcp_cover_aim_params {
+    int32_t k_max;          /* sensors to place, 1 .. PCP_PLACE_MAX */
+    int32_t n_aims;         /* 1 .. PCP_COVER_AIM_MAX */
+    int32_t n_fixed;        /* aimed sensors already placed, 0 .. PCP_PLACE_MAX */
+    int32_t w_az;           /* window width in columns, 1 .. n_az */
+    int32_t w_el;           /* window height in rings, 1 .. n_el */
+    int32_t reserved[3];    /* 0 */
+    double  min_separation; /* metres in XY; <= 0: none */
+    int64_t fixed_pose[PCP_PLACE_MAX];   /* indices into the poses, first n_fixed used */
+    int32_t fixed_aim[PCP_PLACE_MAX];    /* indices into aims, first n_fixed used */
+} pcp_cover_aim_params;
+int pcp_place_coverage_aimed(pcp_ctx *ctx, const double *poses5, uint64_t n,
+                             const pcp_fan_params *fan, const pcp_cover_aim_params *ap,
+                             const int32_t *aims,                      /* [n_aims][2]: az0, el0 */
+                             const uint8_t *roi, uint64_t roi_n,       /* nullable; [N], non-zero = counts */
+                             int64_t *selected, int32_t *selected_aim, /* [k_max] */
+                             uint64_t *gain, uint64_t *covered_after,  /* [k_max] */
+                             int64_t *round_gains,                     /* nullable [k_max][n][n_aims], -1: not alive */
+                             uint32_t *seen_points,                    /* nullable [n] */
+                             uint32_t *aim_points,                     /* nullable [n][n_aims] */
+                             int32_t *point_owner, uint64_t owner_cap, /* nullable [N] */
+                             uint64_t *n_points, uint64_t *roi_points, uint64_t *base_covered,
+                             int32_t *n_selected);
+int pcp_place_coverage_aimed_mounted(pcp_ctx *ctx, const double *poses6, uint64_t n,
+                                     const pcp_fan_params *fan, const double *el_table,
+                                     const pcp_cover_aim_params *ap, const int32_t *aims,
+                                     const uint8_t *roi, uint64_t roi_n, int64_t *selected,
+                                     int32_t *selected_aim, uint64_t *gain,
+                                     uint64_t *covered_after, int64_t *round_gains,
+                                     uint32_t *seen_points, uint32_t *aim_points,
+                                     int32_t *point_owner, uint64_t owner_cap, uint64_t *n_points,
+                                     uint64_t *roi_points, uint64_t *base_covered,
+                                     int32_t *n_selected);
+/* Kernel timing of pcp_place_coverage_aimed (the timing tool only): ms[0] = the query's production
+ * fan kernel per launch, ms[1] = the whole build per repetition (clear, resolve into the bitsets,
+ * counts, ranks and the aim masks), ms[2] = round 0's launch with the selection and nothing
+ * committed, per repetition; `reps` repetitions between two events each.  n >= 1, a terrain index
+ * present. */
+int pcp_place_coverage_aimed_burst(pcp_ctx *ctx, const double *poses5, uint64_t n,
+                                   const pcp_fan_params *fan, const pcp_cover_aim_params *ap,
+                                   const int32_t *aims, const uint8_t *roi, uint64_t roi_n,
+                                   int reps, double ms[3]);
+int pcp_place_coverage_aimed_mounted_burst(pcp_ctx *ctx, const double *poses6, uint64_t n,
+                                           const pcp_fan_params *fan, const double *el_table,
+                                           const pcp_cover_aim_params *ap, const int32_t *aims,
+                                           const uint8_t *roi, uint64_t roi_n, int reps,
+                                           double ms[3]);
+
 /* Diagnostic build with s_memtime stamps (shader clock) per wave: stamps[(p*W + w)*4 + i],
  * W = ceil(n_az*n_el/64), i = 0 start, 1 after direction setup, 2 after the march, 3 end.
  * For locating where wave lifetime goes; never used for timing. */

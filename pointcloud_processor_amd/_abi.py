@@ -139,6 +139,17 @@ class CoverParams(C.Structure):
                 ("min_separation", C.c_double), ("fixed", C.c_int64 * PLACE_MAX)]
 
 
+COVER_AIM_MAX = 64   # PCP_COVER_AIM_MAX: aims one pcp_place_coverage_aimed call searches per pose
+
+
+class CoverAimParams(C.Structure):
+    """pcp_cover_aim_params."""
+    _fields_ = [("k_max", C.c_int32), ("n_aims", C.c_int32), ("n_fixed", C.c_int32),
+                ("w_az", C.c_int32), ("w_el", C.c_int32), ("reserved", C.c_int32 * 3),
+                ("min_separation", C.c_double), ("fixed_pose", C.c_int64 * PLACE_MAX),
+                ("fixed_aim", C.c_int32 * PLACE_MAX)]
+
+
 class ScanReturn(C.Structure):
     """pcp_scan_return: one blocked ray's hit (24 bytes)."""
     _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("range", C.c_float),
@@ -349,6 +360,23 @@ _SIGS = [
                                                           C.POINTER(FanParams), _P,
                                                           C.POINTER(RefineParams), _P,
                                                           C.c_uint64, C.c_int, _P]),
+    ("pcp_place_coverage_aimed", C.c_int, [_P, _P, C.c_uint64, C.POINTER(FanParams),
+                                           C.POINTER(CoverAimParams), _P, _P, C.c_uint64, _P, _P,
+                                           _P, _P, _P, _P, _P, _P, C.c_uint64,
+                                           C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                           C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),
+    ("pcp_place_coverage_aimed_mounted", C.c_int, [_P, _P, C.c_uint64, C.POINTER(FanParams), _P,
+                                                   C.POINTER(CoverAimParams), _P, _P, C.c_uint64,
+                                                   _P, _P, _P, _P, _P, _P, _P, _P, C.c_uint64,
+                                                   C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                                   C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),
+    ("pcp_place_coverage_aimed_burst", C.c_int, [_P, _P, C.c_uint64, C.POINTER(FanParams),
+                                                 C.POINTER(CoverAimParams), _P, _P, C.c_uint64,
+                                                 C.c_int, _P]),
+    ("pcp_place_coverage_aimed_mounted_burst", C.c_int, [_P, _P, C.c_uint64,
+                                                         C.POINTER(FanParams), _P,
+                                                         C.POINTER(CoverAimParams), _P, _P,
+                                                         C.c_uint64, C.c_int, _P]),
     ("pcp_debug_exclusive_scan", C.c_int, [_P, _P, C.c_uint64, _P]),
     ("pcp_debug_math", C.c_int, [_P, C.c_int, _P, _P, C.c_uint64, _P, _P]),
     ("pcp_debug_fine_copy", C.c_int, [_P, C.POINTER(FineGeo), _P, C.c_uint64, _P, C.c_uint64, _P,
@@ -1631,6 +1659,112 @@ class Context:
         return self.place_coverage_burst(poses6, fan, k_max, min_separation, fixed, roi, reps,
                                          _mounted=(self._el_table(fan, el_table),))
 
+    @staticmethod
+    def _cover_aim_params(k_max, n_aims, w_az, w_el, min_separation, fixed,
+                          reserved) -> CoverAimParams:
+        fixed = [(int(p), int(a)) for p, a in fixed]
+        ap = CoverAimParams(int(k_max), int(n_aims), len(fixed), int(w_az), int(w_el),
+                            (C.c_int32 * 3)(int(reserved), 0, 0), float(min_separation))
+        for i, (p, a) in enumerate(fixed[:PLACE_MAX]):
+            ap.fixed_pose[i] = p
+            ap.fixed_aim[i] = a
+        return ap
+
+    def place_coverage_aimed(self, poses5, fan: FanParams, w_az: int, w_el: int, aims,
+                             k_max: int, min_separation: float = 0.0, fixed=(), roi=None,
+                             want_round_gains: bool = False, want_owner: bool = False,
+                             want_aim_points: bool = False, reserved: int = 0,
+                             owner_cap: int | None = None, n_aims: int | None = None,
+                             _mounted=None) -> dict:
+        """pcp_place_coverage_aimed: greedy coverage placement of sensors with a limited field of
+        view -- every pose searched with every aim of `aims` [A, 2] (az0, el0), a window of w_az
+        columns (wrapping) by w_el rings of the pose's own fan (cover_aims() makes them from
+        angles); each round places the (pose, aim) whose window reaches the most terrain points of
+        `roi` nobody reaches yet.  fixed: (pose, aim) pairs already placed.
+        -> dict: selected, selected_aim, gain, covered_after [n_selected], n_selected, n_points,
+        roi_points, base_covered, seen_points [P], round_gains int64 [n_selected, P, A]
+        (want_round_gains, else None; -1: not alive), aim_points uint32 [P, A] (want_aim_points,
+        else None), point_owner int32 [n_points] (want_owner, else None)."""
+        # (_mounted: place_coverage_aimed_mounted's (el_table,), the same call on poses6 rows)
+        poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 6 if _mounted else 5)
+        what = "pcp_place_coverage_aimed_mounted" if _mounted else "pcp_place_coverage_aimed"
+        fn = getattr(self.lib, what)
+        lead = (_ptr(_mounted[0]),) if _mounted else ()
+        aims = np.ascontiguousarray(aims, np.int32).reshape(-1, 2)
+        A = aims.shape[0] if n_aims is None else int(n_aims)
+        P = poses.shape[0]
+        K = min(max(int(k_max), 1), PLACE_MAX)
+        ap = self._cover_aim_params(k_max, A, w_az, w_el, min_separation, fixed, reserved)
+        r8, rn = self._roi(roi)
+        sel = np.zeros(K, np.int64)
+        sel_aim = np.zeros(K, np.int32)
+        gain = np.zeros(K, np.uint64)
+        cov = np.zeros(K, np.uint64)
+        # (a refused call writes nothing: the tables' shapes need not fit it)
+        At = min(max(A, 1), COVER_AIM_MAX)
+        Pt = max(min(P, AIM_MAX_ROWS // At), 1)
+        rg = np.zeros((K, Pt, At), np.int64) if want_round_gains else None
+        apts = np.zeros((Pt, At), np.uint32) if want_aim_points else None
+        seen = np.zeros(max(P, 1), np.uint32)
+        ocap = 0
+        if want_owner:
+            ocap = self.scan_points() if owner_cap is None else int(owner_cap)
+        own = np.zeros(max(ocap, 1), np.int32) if want_owner else None
+        npts, rpts, base = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        ns = C.c_int32()
+        self._check(fn(self.h, _ptr(poses) if P else None, P, C.byref(fan), *lead, C.byref(ap),
+                       _ptr(aims), _ptr(r8), rn, _ptr(sel), _ptr(sel_aim), _ptr(gain),
+                       _ptr(cov), _ptr(rg), _ptr(seen), _ptr(apts), _ptr(own), ocap,
+                       C.byref(npts), C.byref(rpts), C.byref(base), C.byref(ns)), what)
+        k = ns.value
+        return {"selected": sel[:k].copy(), "selected_aim": sel_aim[:k].copy(),
+                "gain": gain[:k].copy(), "covered_after": cov[:k].copy(), "n_selected": k,
+                "n_points": npts.value, "roi_points": rpts.value, "base_covered": base.value,
+                "seen_points": seen[:P],
+                "round_gains": rg[:k, :P] if want_round_gains else None,
+                "aim_points": apts[:P] if want_aim_points else None,
+                "point_owner": own[:npts.value] if want_owner else None}
+
+    def place_coverage_aimed_mounted(self, poses6, fan: FanParams, w_az: int, w_el: int, aims,
+                                     el_table=None, k_max: int = 1, min_separation: float = 0.0,
+                                     fixed=(), roi=None, want_round_gains: bool = False,
+                                     want_owner: bool = False, want_aim_points: bool = False,
+                                     reserved: int = 0) -> dict:
+        """pcp_place_coverage_aimed_mounted: place_coverage_aimed over tilted mounts -- poses6 rows
+        x, y, z, roll, pitch, yaw -- with an optional beam table el_table [n_el] in radians; an
+        aim turns the head about its own spin axis."""
+        return self.place_coverage_aimed(poses6, fan, w_az, w_el, aims, k_max, min_separation,
+                                         fixed, roi, want_round_gains, want_owner,
+                                         want_aim_points, reserved,
+                                         _mounted=(self._el_table(fan, el_table),))
+
+    def place_coverage_aimed_burst(self, poses5, fan: FanParams, w_az: int, w_el: int, aims,
+                                   k_max: int = 1, min_separation: float = 0.0, fixed=(),
+                                   roi=None, reps: int = 20, _mounted=None):
+        """pcp_place_coverage_aimed_burst -> (fan kernel ms per launch, the whole build with the
+        aim masks ms per repetition, round 0's launch ms per repetition)."""
+        poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 6 if _mounted else 5)
+        what = ("pcp_place_coverage_aimed_mounted_burst" if _mounted
+                else "pcp_place_coverage_aimed_burst")
+        lead = (_ptr(_mounted[0]),) if _mounted else ()
+        aims = np.ascontiguousarray(aims, np.int32).reshape(-1, 2)
+        ap = self._cover_aim_params(k_max, aims.shape[0], w_az, w_el, min_separation, fixed, 0)
+        r8, rn = self._roi(roi)
+        ms = np.zeros(3, np.float64)
+        self._check(getattr(self.lib, what)(self.h, _ptr(poses), poses.shape[0], C.byref(fan),
+                                            *lead, C.byref(ap), _ptr(aims), _ptr(r8), rn, reps,
+                                            _ptr(ms)), what)
+        return float(ms[0]), float(ms[1]), float(ms[2])
+
+    def place_coverage_aimed_mounted_burst(self, poses6, fan: FanParams, w_az: int, w_el: int,
+                                           aims, el_table=None, k_max: int = 1,
+                                           min_separation: float = 0.0, fixed=(), roi=None,
+                                           reps: int = 20):
+        """pcp_place_coverage_aimed_mounted_burst -> place_coverage_aimed_burst's triple."""
+        return self.place_coverage_aimed_burst(poses6, fan, w_az, w_el, aims, k_max,
+                                               min_separation, fixed, roi, reps,
+                                               _mounted=(self._el_table(fan, el_table),))
+
     def place_coverage_pair(self, poses5, fan: FanParams, min_separation: float = 0.0, fixed=(),
                             roi=None, want_pair_gains: bool = False, want_owner: bool = False,
                             reserved: int = 0, owner_cap: int | None = None,
@@ -2010,3 +2144,33 @@ def default_vl_params(**kw) -> VlParams:
 def fan_params(n_az=1024, n_el=256, el_min_deg=-85.0, el_max_deg=85.0, max_distance=15.0):
     return FanParams(n_az, n_el, el_min_deg * np.pi / 180.0, el_max_deg * np.pi / 180.0,
                      max_distance)
+
+
+def cover_aims(fan: FanParams, h_fov: float, v_fov: float, yaws, pitches):
+    """Angles -> pcp_place_coverage_aimed's (w_az, w_el, aims int32 [len(yaws) * len(pitches), 2]),
+    yaw-major.  Column i of a fan looks along azimuth i * da, da = 2 pi / n_az, from the pose's
+    heading; ring j along elevation el_min + (j + 0.5) * de, de = (el_max - el_min) / n_el.
+    The rounding rule, nearest(x) = floor(x + 0.5):
+      w_az = nearest(h_fov / da) held to 1 .. n_az, w_el = nearest(v_fov / de) held to 1 .. n_el
+      (a window is at least one column by one ring, however narrow the angles);
+      az0 = nearest(yaw / da - (w_az - 1) / 2) mod n_az: the window's middle on the column
+      nearest the yaw (azimuth wraps);
+      el0 = nearest((pitch - el_min) / de - 0.5 - (w_el - 1) / 2) held to 0 .. n_el - w_el: the
+      window's middle on the ring nearest the pitch, pushed back inside the fan (rings do not
+      wrap)."""
+    n_az, n_el = int(fan.n_az), int(fan.n_el)
+    da = 2.0 * np.pi / n_az
+    de = (fan.el_max - fan.el_min) / n_el
+
+    def nearest(x):
+        return int(np.floor(x + 0.5))
+
+    w_az = min(max(nearest(h_fov / da), 1), n_az)
+    w_el = min(max(nearest(v_fov / de), 1), n_el)
+    aims = []
+    for yaw in np.asarray(yaws, np.float64).reshape(-1):
+        az0 = nearest(yaw / da - (w_az - 1) / 2.0) % n_az
+        for pitch in np.asarray(pitches, np.float64).reshape(-1):
+            el0 = nearest((pitch - fan.el_min) / de - 0.5 - (w_el - 1) / 2.0)
+            aims.append((az0, min(max(el0, 0), n_el - w_el)))
+    return w_az, w_el, np.array(aims, np.int32).reshape(-1, 2)

@@ -128,6 +128,8 @@ class CoveragePlacement {
     const std::string &lastError() const { return err_; }
 
    private:
+    // (pcp_cover_aim_node.hpp's class shares region() and blind_spots())
+    friend class AimedCoveragePlacement;
     // poses: 5 (level) or 6 (mounted) doubles per candidate
     Result run(Device &dev, const PointCloud2 &terrain, const std::vector<double> &poses, size_t n,
                bool mounted, const VirtualScan::Params &fan, const std::vector<int64_t> &fixed,

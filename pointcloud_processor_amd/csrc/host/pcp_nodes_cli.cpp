@@ -32,6 +32,12 @@
 //                         OUT_OWNER.i32 OUT_BLIND.f32 [FIXED]: cover's arguments less KMAX; the
 //                         exact best pair of the candidates (or the best single one where no pair
 //                         adds more), the JSON line with best_pair, pair_gain, best_single, single_gain
+//   pcp_nodes_cli cover_aimed TERRAIN.f32 TN POSES NAZ NEL MAXD KMAX MINSEP ROI.u8|- WAZ WEL AIMS
+//                         OUT_SELECTED.i64 OUT_OWNER.i32 OUT_BLIND.f32 [FIXED]: cover with a limited
+//                         field of view -- a window of WAZ columns x WEL rings of the fan at every
+//                         aim of AIMS (az0,el0,az0,el0,..) of every candidate; FIXED (c,a,c,a,..):
+//                         candidate and aim pairs already placed; OUT_SELECTED: candidate, aim,
+//                         gain, covered per round
 //   pcp_nodes_cli cover_refine cover's arguments [--start c,c,..] [--locked M] [--max-moves M]:
 //                         the set START improved by single-sensor exchanges, its first LOCKED
 //                         slots held; without --start greedy's answer of `cover` is refined in
@@ -54,6 +60,7 @@
 #include <string>
 #include <vector>
 
+#include "pcp_cover_aim_node.hpp"
 #include "pcp_cover_node.hpp"
 #include "pcp_nodes.hpp"
 #include "pcp_placement.hpp"
@@ -665,6 +672,134 @@ static int cover_front(Device &dev, char **a, int argc, CoverCmd mode) {
 static int cmd_cover(Device &dev, char **a, int argc) {
     return cover_front(dev, a, argc, CoverCmd::Greedy);
 }
+
+// whole numbers of a tuple argument as int64 (false: an entry is none)
+static bool whole_numbers(const char *arg, std::vector<int64_t> &out) {
+    for (double f : tuple(arg)) {
+        if (f != (double)(int64_t)f) return false;
+        out.push_back((int64_t)f);
+    }
+    return true;
+}
+
+// cover with a limited field of view: every candidate searched with every aim of a table
+// (AimedCoveragePlacement); the records hold the aim beside the candidate
+static int cmd_cover_aimed(Device &dev, char **a, int argc) {
+    const char *cmd = "cover_aimed";
+    const auto t = read_file(a[0]);
+    const size_t tn = std::strtoull(a[1], nullptr, 10);
+    std::vector<double> pv;
+    const std::string ps = a[2];
+    if (ps.size() > 4 && ps.compare(ps.size() - 4, 4, ".f64") == 0) {
+        const auto raw = read_file(a[2]);
+        pv.resize(raw.size() / 8);
+        std::memcpy(pv.data(), raw.data(), pv.size() * 8);
+        if (raw.size() % 8 != 0) pv.push_back(0.0);   // (refused below)
+    } else {
+        pv = tuple(a[2]);
+    }
+    if (pv.size() % 5 != 0) {
+        std::fprintf(stderr, "%s: POSES holds %zu numbers, not 5 per candidate\n", cmd, pv.size());
+        return 2;
+    }
+    VirtualScan::Params sp;
+    sp.n_az = std::atoi(a[3]);
+    sp.n_el = std::atoi(a[4]);
+    sp.max_distance = std::strtod(a[5], nullptr);
+    AimedCoveragePlacement::Params cp;
+    cp.num_mobile_lidars = std::atoi(a[6]);
+    cp.min_separation = std::strtod(a[7], nullptr);
+    cp.w_az = std::atoi(a[9]);
+    cp.w_el = std::atoi(a[10]);
+    if (cp.w_az < 1 || cp.w_az > sp.n_az || cp.w_el < 1 || cp.w_el > sp.n_el) {
+        std::fprintf(stderr, "%s: the window %d x %d does not fit the fan\n", cmd, cp.w_az, cp.w_el);
+        return 2;
+    }
+    std::vector<int64_t> av;
+    if (!whole_numbers(a[11], av) || av.empty() || av.size() % 2 != 0 ||
+        av.size() / 2 > PCP_COVER_AIM_MAX) {
+        std::fprintf(stderr, "%s: AIMS holds 1 .. %d pairs az0,el0 of whole numbers\n", cmd,
+                     PCP_COVER_AIM_MAX);
+        return 2;
+    }
+    for (size_t i = 0; i < av.size(); i += 2) {
+        if (av[i] < 0 || av[i] >= sp.n_az || av[i + 1] < 0 || av[i + 1] > sp.n_el - cp.w_el) {
+            std::fprintf(stderr, "%s: aim (%lld, %lld) lies outside the fan\n", cmd,
+                         (long long)av[i], (long long)av[i + 1]);
+            return 2;
+        }
+        AimedCoveragePlacement::Aim aim;
+        aim.az0 = (int32_t)av[i];
+        aim.el0 = (int32_t)av[i + 1];
+        cp.aims.push_back(aim);
+    }
+    CoveragePlacement::Roi roi;
+    if (std::strcmp(a[8], "-") != 0) {
+        roi = CoveragePlacement::Roi(read_file(a[8]));
+        if (roi.bytes.size() != tn) {
+            std::fprintf(stderr, "%s: ROI holds %zu bytes, not TN\n", cmd, roi.bytes.size());
+            return 2;
+        }
+    }
+    std::vector<AimedCoveragePlacement::Fixed> fixed;
+    if (argc > 15) {
+        std::vector<int64_t> fv;
+        if (!whole_numbers(a[15], fv) || fv.size() % 2 != 0 || fv.size() / 2 > PCP_PLACE_MAX) {
+            std::fprintf(stderr, "%s: FIXED holds at most %d pairs candidate,aim\n", cmd,
+                         PCP_PLACE_MAX);
+            return 2;
+        }
+        for (size_t i = 0; i < fv.size(); i += 2) {
+            if (fv[i] < 0 || fv[i] >= (int64_t)(pv.size() / 5) || fv[i + 1] < 0 ||
+                fv[i + 1] >= (int64_t)cp.aims.size()) {
+                std::fprintf(stderr, "%s: FIXED entry (%lld, %lld) is no candidate and aim\n", cmd,
+                             (long long)fv[i], (long long)fv[i + 1]);
+                return 2;
+            }
+            AimedCoveragePlacement::Fixed f;
+            f.candidate = fv[i];
+            f.aim = (int32_t)fv[i + 1];
+            fixed.push_back(f);
+        }
+    }
+    SimplifiedDualLidarOptimizer node(dev, SimplifiedDualLidarOptimizer::Params{});
+    const PointCloud2 terrain = cloud_from(t, tn, 32, "map");
+    node.terrainCallback(terrain);
+    std::vector<SimplifiedDualLidarOptimizer::LidarPosition> cand(pv.size() / 5);
+    for (size_t i = 0; i < cand.size(); ++i) {
+        cand[i].x = pv[5 * i];
+        cand[i].y = pv[5 * i + 1];
+        cand[i].z = pv[5 * i + 2];
+        cand[i].pitch = pv[5 * i + 3];
+        cand[i].yaw = pv[5 * i + 4];
+    }
+    AimedCoveragePlacement place(cp);
+    const auto r = place.place(dev, terrain, cand, sp, fixed, roi);
+    if (!r.ran) {
+        std::fprintf(stderr, "%s: %s\n", cmd, place.lastError().c_str());
+        return 1;
+    }
+    std::vector<int64_t> rec;
+    for (size_t i = 0; i < r.rounds.size(); ++i) {
+        rec.push_back(r.rounds[i].candidate);
+        rec.push_back((int64_t)r.aim[i]);
+        rec.push_back((int64_t)r.rounds[i].gain);
+        rec.push_back((int64_t)r.rounds[i].covered);
+    }
+    write_file(a[12], rec.data(), rec.size() * 8);
+    write_file(a[13], r.point_owner.data(), r.point_owner.size() * 4);
+    write_file(a[14], r.blind_spots.data.data(), r.blind_spots.data.size());
+    std::fputs(r.log.c_str(), stderr);
+    const unsigned long long covered =
+        (unsigned long long)(r.rounds.empty() ? r.base_covered : r.rounds.back().covered);
+    std::printf("{\"n_candidates\": %zu, \"n_aims\": %zu, \"n_selected\": %zu, "
+                "\"n_points\": %llu, \"roi_points\": %llu, \"base_covered\": %llu, "
+                "\"covered\": %llu, \"n_blind\": %u}\n",
+                cand.size(), cp.aims.size(), r.rounds.size(), (unsigned long long)r.n_points,
+                (unsigned long long)r.roi_points, (unsigned long long)r.base_covered, covered,
+                r.blind_spots.width);
+    return 0;
+}
 static int cmd_cover_pair(Device &dev, char **a, int argc) {
     return cover_front(dev, a, argc, CoverCmd::Pair);
 }
@@ -1040,7 +1175,7 @@ int main(int argc, char **argv) {
         if (!hp || std::atoi(hp) != 0) setenv("HSA_ENABLE_INTERRUPT", "0", 0);
     }
     if (argc < 2) {
-        std::fprintf(stderr, "usage: pcp_nodes_cli filter|merge|vlidar|place|place_pair|place_triple|place_refine|place_aimed|scan|scan_mounted|cover|cover_pair|cover_refine|area|drivable|replay ...\n");
+        std::fprintf(stderr, "usage: pcp_nodes_cli filter|merge|vlidar|place|place_pair|place_triple|place_refine|place_aimed|scan|scan_mounted|cover|cover_aimed|cover_pair|cover_refine|area|drivable|replay ...\n");
         return 2;
     }
     // name, arguments required after it, the command (a: the arguments, argc: how many)
@@ -1061,6 +1196,7 @@ int main(int argc, char **argv) {
         {"scan", 10, [](Device &d, char **a, int) { return cmd_scan(d, a); }},
         {"scan_mounted", 11, [](Device &d, char **a, int) { return cmd_scan(d, a, /*mounted=*/true); }},
         {"cover", 12, cmd_cover},
+        {"cover_aimed", 15, cmd_cover_aimed},
         {"cover_pair", 11, cmd_cover_pair},
         {"cover_refine", 12, cmd_cover_refine},
         {"area", 10, [](Device &d, char **a, int) { return cmd_area(d, a); }},

@@ -357,6 +357,12 @@ struct pcp_ctx : pcp::CtxStreams {
     // landing of its downloads (its own: cover_d and cpair_d stay as their calls leave them)
     pcp::DevBuf crefine_d;
     pcp::PinnedBuf crefine_host;
+    // pcp_place_coverage_aimed (pcp_cover_aim.hip): the same block again, then its aim record,
+    // the [K][n][A] gains, the aim counts, the column and ring tables, the ranks and the points'
+    // aim masks, and the pinned landing of its downloads (its own: the three above stay as their
+    // calls leave them)
+    pcp::DevBuf caim_d;
+    pcp::PinnedBuf caim_host;
     pcp::PinnedBuf res_host;                 // pinned landing of the filter chain's sizes
     pcp::PinnedBuf fm_res_host;              // pcp_filter_merge's result sizes, stored by its
                                              // kernels themselves (fixed: a graph holds it)
