@@ -1075,6 +1075,62 @@ int pcp_place_coverage_aimed_mounted_burst(pcp_ctx *ctx, const double *poses6, u
                                            const uint8_t *roi, uint64_t roi_n, int reps,
                                            double ms[3]);
 
+/* pcp_place_coverage with a weight per terrain point: a point of the pit's
+ * working face may count 200 where a point of the apron counts 1.  N, seen(p), the separation
+ * expression, the alive rule, the strict first-maximum rule, the owners, seen_points, the
+ * refusals, the capacity rule and the "one host synchronisation, deterministic, other queries'
+ * buffers untouched" clauses are pcp_place_coverage's word for word (the call's scratch is its
+ * own: pcp_place_coverage's stays as that call leaves it).  What changes:
+ *   R = {i : weight[i] != 0};  w(S) = the sum of weight[i] over i in S;  *roi_points = |R|,
+ *   *roi_weight = w(R).
+ *   1. *base_covered = w(R) - w(need) after the fixed sensors, *base_points = |R| - |need|.
+ *   2. g[p] = w(seen(p) & need); round_gains, gain and covered_after are in weight.  Stop unless
+ *      g[b] > 0: every weight in need is >= 1, so this is pcp_place_coverage's stop.
+ *   3. gain_points[r] = |seen(b) & need| at the moment b is committed.
+ *   A non-finite terrain row with a weight counts in *roi_points and *roi_weight and is never
+ *   owned.
+ * Bounds: a gain is at most 255 N < 2^40 (N < 2^32), exact in the 64-bit gains table and exact as
+ * a double in the rounds' first-maximum reduction (< 2^53).
+ * Identities: with every weight in {0, 1} every shared output equals pcp_place_coverage's with
+ * roi = weight, gain_points == gain and *roi_weight == *roi_points; with every weight in {0, c}
+ * the selection is that same one and every weight-valued output is c times it.
+ * PCP_E_INVALID before any launch, nothing written: what pcp_place_coverage refuses, weight null,
+ * weight_n != N.  n == 0 or N == 0: as pcp_place_coverage, *roi_weight the sum of the weights and
+ * *base_points = 0. */
+int pcp_place_coverage_weighted(pcp_ctx *ctx, const double *poses5, uint64_t n,
+                                const pcp_fan_params *fan, const pcp_cover_params *cp,
+                                const uint8_t *weight, uint64_t weight_n,   /* required, [N] */
+                                int64_t *selected,                          /* [k_max] */
+                                uint64_t *gain, uint64_t *covered_after,    /* [k_max], in weight */
+                                uint64_t *gain_points,                      /* nullable [k_max], in points */
+                                int64_t *round_gains,          /* nullable [k_max][n], weight, -1: not alive */
+                                uint32_t *seen_points,                      /* nullable [n] */
+                                int32_t *point_owner, uint64_t owner_cap,   /* nullable [N] */
+                                uint64_t *n_points, uint64_t *roi_points, uint64_t *roi_weight,
+                                uint64_t *base_covered, uint64_t *base_points,
+                                int32_t *n_selected);
+int pcp_place_coverage_weighted_mounted(pcp_ctx *ctx, const double *poses6, uint64_t n,
+                                        const pcp_fan_params *fan, const double *el_table,
+                                        const pcp_cover_params *cp, const uint8_t *weight,
+                                        uint64_t weight_n, int64_t *selected, uint64_t *gain,
+                                        uint64_t *covered_after, uint64_t *gain_points,
+                                        int64_t *round_gains, uint32_t *seen_points,
+                                        int32_t *point_owner, uint64_t owner_cap,
+                                        uint64_t *n_points, uint64_t *roi_points,
+                                        uint64_t *roi_weight, uint64_t *base_covered,
+                                        uint64_t *base_points, int32_t *n_selected);
+/* Kernel timing of pcp_place_coverage_weighted (the timing tool only): pcp_place_coverage_burst's
+ * three phases -- ms[0] the fan, ms[1] the build with the weight planes, ms[2] round 0's gain
+ * launch with the selection and nothing committed.  n >= 1, a terrain index present. */
+int pcp_place_coverage_weighted_burst(pcp_ctx *ctx, const double *poses5, uint64_t n,
+                                      const pcp_fan_params *fan, const pcp_cover_params *cp,
+                                      const uint8_t *weight, uint64_t weight_n, int reps,
+                                      double ms[3]);
+int pcp_place_coverage_weighted_mounted_burst(pcp_ctx *ctx, const double *poses6, uint64_t n,
+                                              const pcp_fan_params *fan, const double *el_table,
+                                              const pcp_cover_params *cp, const uint8_t *weight,
+                                              uint64_t weight_n, int reps, double ms[3]);
+
 /* Diagnostic build with s_memtime stamps (shader clock) per wave: stamps[(p*W + w)*4 + i],
  * W = ceil(n_az*n_el/64), i = 0 start, 1 after direction setup, 2 after the march, 3 end.
  * For locating where wave lifetime goes; never used for timing. */

@@ -377,6 +377,28 @@ _SIGS = [
                                                          C.POINTER(FanParams), _P,
                                                          C.POINTER(CoverAimParams), _P, _P,
                                                          C.c_uint64, C.c_int, _P]),
+    ("pcp_place_coverage_weighted", C.c_int, [_P, _P, C.c_uint64, C.POINTER(FanParams),
+                                              C.POINTER(CoverParams), _P, C.c_uint64, _P, _P, _P,
+                                              _P, _P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64),
+                                              C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                              C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                              C.POINTER(C.c_int32)]),
+    ("pcp_place_coverage_weighted_mounted", C.c_int, [_P, _P, C.c_uint64, C.POINTER(FanParams),
+                                                      _P, C.POINTER(CoverParams), _P, C.c_uint64,
+                                                      _P, _P, _P, _P, _P, _P, _P, C.c_uint64,
+                                                      C.POINTER(C.c_uint64),
+                                                      C.POINTER(C.c_uint64),
+                                                      C.POINTER(C.c_uint64),
+                                                      C.POINTER(C.c_uint64),
+                                                      C.POINTER(C.c_uint64),
+                                                      C.POINTER(C.c_int32)]),
+    ("pcp_place_coverage_weighted_burst", C.c_int, [_P, _P, C.c_uint64, C.POINTER(FanParams),
+                                                    C.POINTER(CoverParams), _P, C.c_uint64,
+                                                    C.c_int, _P]),
+    ("pcp_place_coverage_weighted_mounted_burst", C.c_int, [_P, _P, C.c_uint64,
+                                                            C.POINTER(FanParams), _P,
+                                                            C.POINTER(CoverParams), _P,
+                                                            C.c_uint64, C.c_int, _P]),
     ("pcp_debug_exclusive_scan", C.c_int, [_P, _P, C.c_uint64, _P]),
     ("pcp_debug_math", C.c_int, [_P, C.c_int, _P, _P, C.c_uint64, _P, _P]),
     ("pcp_debug_fine_copy", C.c_int, [_P, C.POINTER(FineGeo), _P, C.c_uint64, _P, C.c_uint64, _P,
@@ -1658,6 +1680,97 @@ class Context:
         """pcp_place_coverage_mounted_burst -> place_coverage_burst's triple."""
         return self.place_coverage_burst(poses6, fan, k_max, min_separation, fixed, roi, reps,
                                          _mounted=(self._el_table(fan, el_table),))
+
+    @staticmethod
+    def _weight(weight):
+        """The weights as the ABI reads them: uint8 [N], each 0 .. 255 exactly (None stays null)."""
+        if weight is None:
+            return None, 0
+        w = np.asarray(weight).reshape(-1)
+        w8 = np.ascontiguousarray(w, np.uint8)
+        if w.dtype != np.uint8 and not np.array_equal(w8, w):   # (bytes are passed as they are)
+            raise ValueError("weights must be integers 0 .. 255")
+        # (an empty array still has an address: the call tells no weights from null weights)
+        return (w8 if w8.size else np.zeros(1, np.uint8)), w8.shape[0]
+
+    def place_coverage_weighted(self, poses5, fan: FanParams, weight, k_max: int,
+                                min_separation: float = 0.0, fixed=(),
+                                want_round_gains: bool = False, want_owner: bool = False,
+                                reserved: int = 0, owner_cap: int | None = None,
+                                _mounted=None) -> dict:
+        """pcp_place_coverage_weighted: place_coverage with a weight 0 .. 255 per terrain point
+        (`weight` [N], required; 0: outside the region) -- each round places the pose whose scan
+        reaches the most weight nobody reaches yet.
+        -> place_coverage's dict with gain, covered_after, base_covered and round_gains in weight,
+        plus gain_points uint64 [n_selected] (the points each round gained), roi_weight (the
+        region's weight; roi_points stays its point count) and base_points."""
+        # (_mounted: place_coverage_weighted_mounted's (el_table,), the same call on poses6 rows)
+        poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 6 if _mounted else 5)
+        what = "pcp_place_coverage_weighted_mounted" if _mounted else "pcp_place_coverage_weighted"
+        fn = getattr(self.lib, what)
+        lead = (_ptr(_mounted[0]),) if _mounted else ()
+        P = poses.shape[0]
+        K = min(max(int(k_max), 1), PLACE_MAX)
+        cp = self._cover_params(k_max, min_separation, fixed, reserved)
+        w8, wn = self._weight(weight)
+        sel = np.zeros(K, np.int64)
+        gain, cov, gpts = np.zeros(K, np.uint64), np.zeros(K, np.uint64), np.zeros(K, np.uint64)
+        rg = np.zeros((K, max(P, 1)), np.int64) if want_round_gains else None
+        seen = np.zeros(max(P, 1), np.uint32)
+        ocap = 0
+        if want_owner:
+            ocap = self.scan_points() if owner_cap is None else int(owner_cap)
+        own = np.zeros(max(ocap, 1), np.int32) if want_owner else None
+        npts, rpts, rw = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        base, bpts = C.c_uint64(), C.c_uint64()
+        ns = C.c_int32()
+        self._check(fn(self.h, _ptr(poses) if P else None, P, C.byref(fan), *lead, C.byref(cp),
+                       _ptr(w8), wn, _ptr(sel), _ptr(gain), _ptr(cov), _ptr(gpts), _ptr(rg),
+                       _ptr(seen), _ptr(own), ocap, C.byref(npts), C.byref(rpts), C.byref(rw),
+                       C.byref(base), C.byref(bpts), C.byref(ns)), what)
+        k = ns.value
+        return {"selected": sel[:k].copy(), "gain": gain[:k].copy(),
+                "covered_after": cov[:k].copy(), "gain_points": gpts[:k].copy(), "n_selected": k,
+                "n_points": npts.value, "roi_points": rpts.value, "roi_weight": rw.value,
+                "base_covered": base.value, "base_points": bpts.value, "seen_points": seen[:P],
+                "round_gains": rg[:k, :P] if want_round_gains else None,
+                "point_owner": own[:npts.value] if want_owner else None}
+
+    def place_coverage_weighted_mounted(self, poses6, fan: FanParams, weight, el_table=None,
+                                        k_max: int = 1, min_separation: float = 0.0, fixed=(),
+                                        want_round_gains: bool = False, want_owner: bool = False,
+                                        reserved: int = 0) -> dict:
+        """pcp_place_coverage_weighted_mounted: place_coverage_weighted over tilted mounts --
+        poses6 rows x, y, z, roll, pitch, yaw -- with an optional beam table el_table [n_el]."""
+        return self.place_coverage_weighted(poses6, fan, weight, k_max, min_separation, fixed,
+                                            want_round_gains, want_owner, reserved,
+                                            _mounted=(self._el_table(fan, el_table),))
+
+    def place_coverage_weighted_burst(self, poses5, fan: FanParams, weight, k_max: int = 1,
+                                      min_separation: float = 0.0, fixed=(), reps: int = 20,
+                                      _mounted=None):
+        """pcp_place_coverage_weighted_burst -> (fan kernel ms per launch, the build with the
+        weight planes ms per repetition, round 0's gain launch ms per repetition)."""
+        poses = np.ascontiguousarray(poses5, np.float64).reshape(-1, 6 if _mounted else 5)
+        what = ("pcp_place_coverage_weighted_mounted_burst" if _mounted
+                else "pcp_place_coverage_weighted_burst")
+        lead = (_ptr(_mounted[0]),) if _mounted else ()
+        cp = self._cover_params(k_max, min_separation, fixed, 0)
+        w8, wn = self._weight(weight)
+        ms = np.zeros(3, np.float64)
+        self._check(getattr(self.lib, what)(self.h, _ptr(poses), poses.shape[0], C.byref(fan),
+                                            *lead, C.byref(cp), _ptr(w8), wn, reps, _ptr(ms)),
+                    what)
+        return float(ms[0]), float(ms[1]), float(ms[2])
+
+    def place_coverage_weighted_mounted_burst(self, poses6, fan: FanParams, weight,
+                                              el_table=None, k_max: int = 1,
+                                              min_separation: float = 0.0, fixed=(),
+                                              reps: int = 20):
+        """pcp_place_coverage_weighted_mounted_burst -> place_coverage_weighted_burst's triple."""
+        return self.place_coverage_weighted_burst(poses6, fan, weight, k_max, min_separation,
+                                                  fixed, reps,
+                                                  _mounted=(self._el_table(fan, el_table),))
 
     @staticmethod
     def _cover_aim_params(k_max, n_aims, w_az, w_el, min_separation, fixed,

@@ -128,8 +128,10 @@ class CoveragePlacement {
     const std::string &lastError() const { return err_; }
 
    private:
-    // (pcp_cover_aim_node.hpp's class shares region() and blind_spots())
+    // (pcp_cover_aim_node.hpp's and pcp_cover_weight_node.hpp's classes share region() and
+    // blind_spots())
     friend class AimedCoveragePlacement;
+    friend class WeightedCoveragePlacement;
     // poses: 5 (level) or 6 (mounted) doubles per candidate
     Result run(Device &dev, const PointCloud2 &terrain, const std::vector<double> &poses, size_t n,
                bool mounted, const VirtualScan::Params &fan, const std::vector<int64_t> &fixed,

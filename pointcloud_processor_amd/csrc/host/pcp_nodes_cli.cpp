@@ -38,6 +38,13 @@
 //                         aim of AIMS (az0,el0,az0,el0,..) of every candidate; FIXED (c,a,c,a,..):
 //                         candidate and aim pairs already placed; OUT_SELECTED: candidate, aim,
 //                         gain, covered per round
+//   pcp_nodes_cli cover_weighted TERRAIN.f32 TN POSES NAZ NEL MAXD KMAX MINSEP WEIGHTS OUT_SELECTED.i64
+//                         OUT_OWNER.i32 OUT_BLIND.f32 [FIXED]: cover by the WEIGHT of the points
+//                         reached -- WEIGHTS a .u8 file (TN bytes, 0 .. 255 each, 0: outside the
+//                         region) or BASE[/x0,x1,y0,y1,z0,z1,W]..: a base weight and boxes in map
+//                         coordinates with theirs, a later box overriding an earlier one;
+//                         OUT_SELECTED: candidate, weight gained, points gained, covered weight
+//                         per round; the JSON line adds roi_weight, base_points, blind_weight
 //   pcp_nodes_cli cover_refine cover's arguments [--start c,c,..] [--locked M] [--max-moves M]:
 //                         the set START improved by single-sensor exchanges, its first LOCKED
 //                         slots held; without --start greedy's answer of `cover` is refined in
@@ -62,6 +69,7 @@
 
 #include "pcp_cover_aim_node.hpp"
 #include "pcp_cover_node.hpp"
+#include "pcp_cover_weight_node.hpp"
 #include "pcp_nodes.hpp"
 #include "pcp_placement.hpp"
 #include "pcp_scan_node.hpp"
@@ -800,6 +808,127 @@ static int cmd_cover_aimed(Device &dev, char **a, int argc) {
                 r.blind_spots.width);
     return 0;
 }
+// cover by weight: the candidates placed by the weight of the terrain points their scans reach
+// (WeightedCoveragePlacement); the records hold the weight and the points gained
+static int cmd_cover_weighted(Device &dev, char **a, int argc) {
+    const char *cmd = "cover_weighted";
+    const auto t = read_file(a[0]);
+    const size_t tn = std::strtoull(a[1], nullptr, 10);
+    std::vector<double> pv;
+    const std::string ps = a[2];
+    if (ps.size() > 4 && ps.compare(ps.size() - 4, 4, ".f64") == 0) {
+        const auto raw = read_file(a[2]);
+        pv.resize(raw.size() / 8);
+        std::memcpy(pv.data(), raw.data(), pv.size() * 8);
+        if (raw.size() % 8 != 0) pv.push_back(0.0);   // (refused below)
+    } else {
+        pv = tuple(a[2]);
+    }
+    if (pv.size() % 5 != 0) {
+        std::fprintf(stderr, "%s: POSES holds %zu numbers, not 5 per candidate\n", cmd, pv.size());
+        return 2;
+    }
+    VirtualScan::Params sp;
+    sp.n_az = std::atoi(a[3]);
+    sp.n_el = std::atoi(a[4]);
+    sp.max_distance = std::strtod(a[5], nullptr);
+    WeightedCoveragePlacement::Params cp;
+    cp.num_mobile_lidars = std::atoi(a[6]);
+    cp.min_separation = std::strtod(a[7], nullptr);
+    // WEIGHTS: a .u8 file, or BASE[/x0,x1,y0,y1,z0,z1,W]..
+    auto byte_of = [](double f) { return f == (double)(int64_t)f && f >= 0 && f <= 255; };
+    CoverageWeights weights;
+    const std::string ws = a[8];
+    if (ws.size() > 3 && ws.compare(ws.size() - 3, 3, ".u8") == 0) {
+        weights = CoverageWeights(read_file(a[8]));
+        if (weights.bytes.size() != tn) {
+            std::fprintf(stderr, "%s: WEIGHTS holds %zu bytes, not TN\n", cmd,
+                         weights.bytes.size());
+            return 2;
+        }
+    } else {
+        std::stringstream ss(ws);
+        std::string part;
+        bool first = true;
+        while (std::getline(ss, part, '/')) {
+            const auto v = tuple(part.c_str());
+            if (first) {
+                if (v.size() != 1 || !byte_of(v[0])) {
+                    std::fprintf(stderr, "%s: WEIGHTS starts with a base weight 0 .. 255\n", cmd);
+                    return 2;
+                }
+                weights.base = (uint8_t)v[0];
+                first = false;
+                continue;
+            }
+            if (v.size() != 7 || !byte_of(v[6])) {
+                std::fprintf(stderr, "%s: a box of WEIGHTS is x0,x1,y0,y1,z0,z1,W with W 0 .. 255\n",
+                             cmd);
+                return 2;
+            }
+            CoverageWeightBox b;
+            b.box = CoverageBox{v[0], v[1], v[2], v[3], v[4], v[5]};
+            b.weight = (uint8_t)v[6];
+            weights.boxes.push_back(b);
+        }
+        if (first) {
+            std::fprintf(stderr, "%s: WEIGHTS is empty\n", cmd);
+            return 2;
+        }
+    }
+    std::vector<int64_t> fixed;
+    if (argc > 12)
+        for (double f : tuple(a[12])) {
+            if (f != (double)(int64_t)f || f < 0 || f >= (double)(pv.size() / 5)) {
+                std::fprintf(stderr, "%s: FIXED entry %g is no candidate\n", cmd, f);
+                return 2;
+            }
+            fixed.push_back((int64_t)f);
+        }
+    if (fixed.size() > PCP_PLACE_MAX) {
+        std::fprintf(stderr, "%s: more than %d FIXED candidates\n", cmd, PCP_PLACE_MAX);
+        return 2;
+    }
+    SimplifiedDualLidarOptimizer node(dev, SimplifiedDualLidarOptimizer::Params{});
+    const PointCloud2 terrain = cloud_from(t, tn, 32, "map");
+    node.terrainCallback(terrain);
+    std::vector<SimplifiedDualLidarOptimizer::LidarPosition> cand(pv.size() / 5);
+    for (size_t i = 0; i < cand.size(); ++i) {
+        cand[i].x = pv[5 * i];
+        cand[i].y = pv[5 * i + 1];
+        cand[i].z = pv[5 * i + 2];
+        cand[i].pitch = pv[5 * i + 3];
+        cand[i].yaw = pv[5 * i + 4];
+    }
+    WeightedCoveragePlacement place(cp);
+    const auto r = place.place(dev, terrain, cand, sp, weights, fixed);
+    if (!r.ran) {
+        std::fprintf(stderr, "%s: %s\n", cmd, place.lastError().c_str());
+        return 1;
+    }
+    std::vector<int64_t> rec;
+    for (size_t i = 0; i < r.rounds.size(); ++i) {
+        rec.push_back(r.rounds[i].candidate);
+        rec.push_back((int64_t)r.rounds[i].gain);
+        rec.push_back((int64_t)r.gain_points[i]);
+        rec.push_back((int64_t)r.rounds[i].covered);
+    }
+    write_file(a[9], rec.data(), rec.size() * 8);
+    write_file(a[10], r.point_owner.data(), r.point_owner.size() * 4);
+    write_file(a[11], r.blind_spots.data.data(), r.blind_spots.data.size());
+    std::fputs(r.log.c_str(), stderr);
+    const unsigned long long covered =
+        (unsigned long long)(r.rounds.empty() ? r.base_covered : r.rounds.back().covered);
+    std::printf("{\"n_candidates\": %zu, \"n_selected\": %zu, \"n_points\": %llu, "
+                "\"roi_points\": %llu, \"roi_weight\": %llu, \"base_covered\": %llu, "
+                "\"base_points\": %llu, \"covered\": %llu, \"n_blind\": %u, "
+                "\"blind_weight\": %llu}\n",
+                cand.size(), r.rounds.size(), (unsigned long long)r.n_points,
+                (unsigned long long)r.roi_points, (unsigned long long)r.roi_weight,
+                (unsigned long long)r.base_covered, (unsigned long long)r.base_points, covered,
+                r.blind_spots.width, (unsigned long long)r.blind_weight);
+    return 0;
+}
 static int cmd_cover_pair(Device &dev, char **a, int argc) {
     return cover_front(dev, a, argc, CoverCmd::Pair);
 }
@@ -1175,7 +1304,7 @@ int main(int argc, char **argv) {
         if (!hp || std::atoi(hp) != 0) setenv("HSA_ENABLE_INTERRUPT", "0", 0);
     }
     if (argc < 2) {
-        std::fprintf(stderr, "usage: pcp_nodes_cli filter|merge|vlidar|place|place_pair|place_triple|place_refine|place_aimed|scan|scan_mounted|cover|cover_aimed|cover_pair|cover_refine|area|drivable|replay ...\n");
+        std::fprintf(stderr, "usage: pcp_nodes_cli filter|merge|vlidar|place|place_pair|place_triple|place_refine|place_aimed|scan|scan_mounted|cover|cover_aimed|cover_pair|cover_refine|cover_weighted|area|drivable|replay ...\n");
         return 2;
     }
     // name, arguments required after it, the command (a: the arguments, argc: how many)
@@ -1199,6 +1328,7 @@ int main(int argc, char **argv) {
         {"cover_aimed", 15, cmd_cover_aimed},
         {"cover_pair", 11, cmd_cover_pair},
         {"cover_refine", 12, cmd_cover_refine},
+        {"cover_weighted", 12, cmd_cover_weighted},
         {"area", 10, [](Device &d, char **a, int) { return cmd_area(d, a); }},
         {"drivable", 7, [](Device &d, char **a, int) { return cmd_drivable(d, a); }},
         {"replay", 8, [](Device &d, char **a, int) { return cmd_replay(d, a); }},

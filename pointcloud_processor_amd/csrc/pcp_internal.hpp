@@ -363,6 +363,11 @@ struct pcp_ctx : pcp::CtxStreams {
     // calls leave them)
     pcp::DevBuf caim_d;
     pcp::PinnedBuf caim_host;
+    // pcp_place_coverage_weighted (pcp_cover_weight.hip): its weighted counts in front of the same
+    // block (the staged bytes are the weights), then the weight's bit planes, and the pinned
+    // landing of its downloads (its own: the four above stay as their calls leave them)
+    pcp::DevBuf cweight_d;
+    pcp::PinnedBuf cweight_host;
     pcp::PinnedBuf res_host;                 // pinned landing of the filter chain's sizes
     pcp::PinnedBuf fm_res_host;              // pcp_filter_merge's result sizes, stored by its
                                              // kernels themselves (fixed: a graph holds it)
